@@ -15,7 +15,11 @@ it was not started under torchrun (no WORLD_SIZE in the environment); under
 equal the number of ranks, N devices must be visible, and ``n_gpus`` in the JSON is the number of ranks that joined the
 timing barrier.  ``--dry-run`` rehearses the launch / barrier / exchange protocol on the CPU (gloo, no kernels).
 
-Prints ONE JSON line on rank 0 (see the contract in the task statement) with two extra objects:
+Prints ONE JSON line on rank 0: metric, value (graphs/s over the timed steps), unit, higher_is_better, dtype,
+ms_per_step (wall time of one timed step), steps, warmup, n_gpus, config and the loss of the last timed step.  A plain run
+does only that: set-up, warm-up (plus the untimed launch-mode probe of ``--launch auto``), the ``--steps`` timed steps.
+``--dump-outputs DIR`` then writes what the last timed step computed (``loss.npy``, ``grads.npy``: float32; the inputs
+are seeded, so two builds can be compared output for output).  ``--full`` adds the figures that take runs of their own:
   roofline     — the scatter-aggregate: algorithmic bytes per launch (4EH + 4E + 16NH) / the average
                  duration of the kernel that performs it in the step, timed live with HIP events attached to the kernel's
                  dispatch on the launch stream (hipExtLaunchKernelGGL start / stop events: the kernel's own execution
@@ -23,8 +27,9 @@ Prints ONE JSON line on rank 0 (see the contract in the task statement) with two
                  round 3 that kernel is the FUSED edge kernel (gnx_pna_edge_fwd: gather + pre-layer-1 product + aggregate);
                  ``roofline.fused`` adds its own algorithmic bytes, ``roofline.standalone_scatter_kernel`` the stand-alone
                  gnx_pna_aggregate_fwd on the same CSR;
+  mfma, kernels — matrix-pipe FLOPs of the step and its six costliest kernel groups, from the same instrumented steps;
   cpu_baseline — the oracle (pure-torch restatement of the reference's PyG CPU path, kind "port") timed on this
-                 box's host cores on a bounded sample of the same workload (rank 0, N=1 only).
+                 box's host cores on a bounded sample of the same workload (rank 0, N=1 only; --no-cpu-baseline).
 """
 from __future__ import annotations
 
@@ -144,6 +149,8 @@ def dry_run(args, world: int, rank: int) -> None:
                           "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "none",
                           "config": {"workload": "dry run: launch + barrier + gradient exchange protocol only (gloo, CPU)",
                                      "parallelism": f"dp{world}"}, "dry_run": True}), flush=True)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, None, flat)
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
@@ -175,12 +182,20 @@ def main():
                          "exchange has never run with more than one RCCL rank -- no multi-GPU box so far; default = ONE "
                          "all-reduce after backward)")
     ap.add_argument("--no-overlap", action="store_true", help="(default since round 3; kept for compatibility)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure roofline / mfma / kernels (instrumented steps of their own) "
+                         "and the CPU baseline; off by default: a plain run reports the timed steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (loss, parameter gradients) to DIR/<name>.npy")
     args = ap.parse_args()
     if args.graph:
         args.launch = "graph"
 
     if args.gpus < 1:
         print("[bench] --gpus must be >= 1", file=sys.stderr)
+        sys.exit(2)
+    if args.steps < 1 or args.warmup < 0:
+        print("[bench] --steps must be >= 1 and --warmup >= 0", file=sys.stderr)
         sys.exit(2)
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args))  # this process stays GPU-free; the ranks are fresh children
@@ -214,7 +229,7 @@ def main():
     main_stream = torch.cuda.Stream(device=dev)
     torch.cuda.set_stream(main_stream)
 
-    from gnnepcsaft_amd import _lib, dp, functional as Fn, ops
+    from gnnepcsaft_amd import dp, functional as Fn, ops
     from gnnepcsaft_amd.data import calc_deg, default_config, synthetic_batch
     from gnnepcsaft_amd.train.models import create_model
 
@@ -333,8 +348,6 @@ def main():
             flat.enable_overlap(overlap_was)
             step = eager_step
 
-    agg_k = _lib.K_PNA_AGG_FWD if cfg["conv"] == "PNA" else _lib.K_GINE_AGG_FWD
-    agg_bk = _lib.K_PNA_AGG_BWD if cfg["conv"] == "PNA" else _lib.K_GINE_AGG_BWD
     if dist is not None:
         dist.barrier()
     torch.cuda.synchronize()
@@ -347,6 +360,76 @@ def main():
     t1 = time.perf_counter()
     elapsed = t1 - t0
     ops.check_range(dev)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, loss, flat.flat)
+    joined = 1
+    if dist is not None:
+        t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
+        dist.all_reduce(t, op=dist.ReduceOp.MAX)
+        elapsed = float(t)
+        j = torch.ones(1, dtype=torch.float64, device=dev)
+        dist.all_reduce(j, op=dist.ReduceOp.SUM)
+        joined = int(j.item())  # ranks that took part in the timed region
+    # --full: per-kernel figures from further instrumented steps (every rank takes part: those steps exchange gradients)
+    full = full_measurements(args, cfg, dev, b, model, eager_step, rank, per_gpu, elapsed) if args.full else {}
+    loss_val = float(loss.detach())
+    if rank == 0:
+        print(f"[bench] gpu: {args.steps} steps in {elapsed:.3f}s, loss {loss_val:.6f}", file=sys.stderr, flush=True)
+    assert loss_val == loss_val, "loss is NaN"
+
+    if rank == 0:
+        assert joined == world, f"{joined} ranks joined the barrier, expected {world}"
+        graphs = per_gpu * world * args.steps
+        value = graphs / elapsed
+        out = {
+            "metric": "molecular graphs/sec (fwd+bwd)", "value": value, "unit": "graphs/s", "n_gpus": joined,
+            "steps": args.steps, "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3,
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+            "config": {"workload": f"BASELINE configs[{args.config - 1}]: {cfg['conv']} hidden={H} L={cfg['propagation_depth']} "
+                                   f"towers={T} pre={cfg['pre_layers']} post={cfg['post_layers']}, {per_gpu} graphs/GPU "
+                                   f"({N_nodes} atoms, {E_edges} directed bonds), fwd+loss+bwd incl. CSR packing",
+                       "graphs_per_gpu": per_gpu, "parallelism": f"dp{world}", "hip_graph": graphed,
+                       "launch": args.launch, "launch_autotune": autotune,
+                       "grad_allreduce_bytes": flat.nbytes if flat.collective else 0,
+                       "grad_exchange": ("rccl, %d per-layer slices overlapped with backward + 1" % len(flat.layer_slices)
+                                         if flat._overlap else ("rccl, one call after backward" if flat.collective
+                                                                else "none (1 rank)"))},
+            "loss": loss_val,
+        }
+        out.update(full)
+        if args.full and world == 1 and not args.no_cpu_baseline:
+            out["cpu_baseline"] = cpu_baseline(cfg, deg, batch_cpu, args.cpu_steps)
+        print(json.dumps(out), flush=True)
+    if dist is not None:
+        dist.barrier()
+        dist.destroy_process_group()
+
+
+def dump_outputs(path, loss, grads, max_bytes: int = 64 << 20):
+    """``--dump-outputs DIR``: what the last timed step handed its caller -- the loss and the parameter gradients (the
+    flat buffer every ``p.grad`` is a view of, in ``named_parameters()`` order) -- as float32 ``.npy`` files.  A
+    gradient buffer above the size cap is written as a fixed, seeded sample of its entries (sorted positions).  The
+    dry run has no loss: it writes its exchanged buffer only."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    g = grads.detach().float().cpu().numpy()
+    cap = (max_bytes - 4096) // 4
+    if g.size > cap:
+        g = g[np.sort(np.random.default_rng(0).permutation(g.size)[:cap])]
+    if loss is not None:
+        np.save(os.path.join(path, "loss.npy"), loss.detach().float().cpu().numpy().reshape(1))
+    np.save(os.path.join(path, "grads.npy"), g)
+
+
+def full_measurements(args, cfg, dev, b, model, eager_step, rank: int, per_gpu: int, elapsed: float) -> dict:
+    """``--full``: the per-kernel figures of the step, which take runs of their own -- ``roofline`` (the
+    scatter-aggregate kernel against HBM), ``mfma`` (matrix-pipe FLOPs) and ``kernels`` (the six costliest kernel
+    groups).  Every rank runs the instrumented steps; rank 0 returns the report, the other ranks ``{}``."""
+    from gnnepcsaft_amd import _lib, ops
+    agg_k = _lib.K_PNA_AGG_FWD if cfg["conv"] == "PNA" else _lib.K_GINE_AGG_FWD
+    agg_bk = _lib.K_PNA_AGG_BWD if cfg["conv"] == "PNA" else _lib.K_GINE_AGG_BWD
+    N_nodes, E_edges = b.x.size(0), b.edge_index.size(1)
+    H = cfg["hidden_dim"]
     # Per-kernel durations: HIP event pairs around every launch group of every kernel group, on the stream the launches
     # go to (gnx_prof_*), over `steps` further eager steps of the same workload (event records cannot live inside a
     # replayed graph).  Two passes: (1) AS RUN -- weight-gradient kernels on their own stream, overlapping the
@@ -372,129 +455,96 @@ def main():
     # stand-alone kernel (gnx_pna_aggregate_fwd: hub-heavy batches, pre_layers != 2) is then timed on this batch's CSR
     fused_fwd = cfg["conv"] == "PNA" and prof_run[_lib.K_PNA_EDGE_FWD]["launches"] > 0
     standalone = scatter_standalone(dev, cfg, b, model) if (rank == 0 and fused_fwd) else None
-    joined = 1
-    if dist is not None:
-        t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        elapsed = float(t)
-        j = torch.ones(1, dtype=torch.float64, device=dev)
-        dist.all_reduce(j, op=dist.ReduceOp.SUM)
-        joined = int(j.item())  # ranks that took part in the timed region
-    loss_val = float(loss.detach())
-    if rank == 0:
-        print(f"[bench] gpu: {args.steps} steps in {elapsed:.3f}s, loss {loss_val:.6f}", file=sys.stderr, flush=True)
-    assert loss_val == loss_val, "loss is NaN"
+    if rank != 0:
+        return {}
 
-    if rank == 0:
-        assert joined == world, f"{joined} ranks joined the barrier, expected {world}"
-        graphs = per_gpu * world * args.steps
-        value = graphs / elapsed
-        def per_launch(p, k):
-            n = max(p[k]["launches"], 1)
-            return {"launches": p[k]["launches"], "avg_us": p[k]["ms"] / n * 1e3, "bytes": p[k]["bytes"] / n,
-                    "gbs": (p[k]["bytes"] / (p[k]["ms"] * 1e-3) / 1e9) if p[k]["ms"] > 0 else 0.0}
+    def per_launch(p, k):
+        n = max(p[k]["launches"], 1)
+        return {"launches": p[k]["launches"], "avg_us": p[k]["ms"] / n * 1e3, "bytes": p[k]["bytes"] / n,
+                "gbs": (p[k]["bytes"] / (p[k]["ms"] * 1e-3) / 1e9) if p[k]["ms"] > 0 else 0.0}
 
-        f_run, f_iso = per_launch(prof_run, agg_k), per_launch(prof_iso, agg_k)
-        roof_kernel = "k_pna_agg_fwd" if cfg["conv"] == "PNA" else "k_gine_fwd"
-        fused_info = None
-        if fused_fwd:
-            # a fused gather -> MLP -> aggregate kernel is reported against the SAME algorithmic figure as
-            # the scatter-aggregate alone (4EH + 4E + 16NH per launch) and, additionally, against its own bytes
-            fr, fi = per_launch(prof_run, _lib.K_PNA_EDGE_FWD), per_launch(prof_iso, _lib.K_PNA_EDGE_FWD)
-            scatter_bytes = 4.0 * E_edges * H + 4.0 * E_edges + 16.0 * N_nodes * H
-            fused_info = {"own_alg_bytes_per_launch": fr["bytes"], "own_achieved": fr["gbs"],
-                          "own_frac": fr["gbs"] / HBM_PEAK_GBS,
-                          "what": "message assembly (gather of P, Q, Te rows) + pre-layer-1 split-bf16 product + "
-                                  "mean|min|max|std in one launch; writes h1, the messages and the aggregate once"}
-            for d_ in (fr, fi):
-                d_["bytes"] = scatter_bytes
-                d_["gbs"] = scatter_bytes / (d_["avg_us"] * 1e-6) / 1e9 if d_["avg_us"] > 0 else 0.0
-            f_run, f_iso = fr, fi
-            roof_kernel = "k_pna_edge_fwd (fused: scatter-aggregate inside the edge kernel)"
-        b_run, b_iso = per_launch(prof_run, agg_bk), per_launch(prof_iso, agg_bk)
-        # HBM traffic of the scatter kernel from the PMC counters: only if the committed counter file was collected on
-        # THIS workload (same conv, atoms, bonds, width); otherwise null
-        traffic, traffic_src = None, None
-        pmc = os.path.join(ROOT, "profiles", "pmc_scatter.json")
-        if os.path.exists(pmc):
-            try:
-                pj = json.load(open(pmc))
-                if (pj.get("conv", "PNA") == cfg["conv"] and pj.get("N") == N_nodes and pj.get("E") == E_edges
-                        and pj.get("H") == H and pj.get("kernel", "k_pna_agg_fwd").startswith(roof_kernel.split(" ")[0])):
-                    traffic = pj.get("traffic_bytes_per_launch")
-                    # PMC counters need rocprofv3: the figure is NOT measured in this run, it is read from the committed file
-                    traffic_src = f"profiles/pmc_scatter.json ({pj.get('round', 'r?')}, rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes)"
-            except Exception:  # pylint: disable=broad-except
-                traffic = None
-        # the step's products: algorithmic FLOPs executed (the restructured layers do fewer than the reference
-        # formulation), and the bf16-MFMA FLOPs the split-operand kernels issue for them (6 per algorithmic one)
-        gemm_groups = (_lib.K_GEMM_WS, _lib.K_GEMM_TILED, _lib.K_GEMM_SMALL, _lib.K_GEMM_WGRAD, _lib.K_GEMM_WGRAD_BATCHED)
-        exec_flops = sum(prof_run[k]["flops"] for k in gemm_groups) / args.steps
-        mfma_flops = sum(prof_run[k]["mfma_bf16_flops"] for k in gemm_groups) / args.steps
-        gemm_ms = sum(prof_iso[k]["ms"] for k in gemm_groups) / args.steps
-        step_s = elapsed / args.steps
-        ref_flops = 3 * ref_flops_per_graph(cfg) if args.config != 5 else None
-        kernels = []
-        for k, name in _lib.KERNEL_GROUPS.items():
-            r_, i_ = prof_run[k], prof_iso[k]
-            if r_["launches"] == 0:
-                continue
-            t_ = i_["ms"] * 1e-3
-            e = {"group": name, "launches_per_step": r_["launches"] / args.steps, "ms_per_step": r_["ms"] / args.steps,
-                 "ms_per_step_isolated": i_["ms"] / args.steps, "avg_us_isolated": i_["ms"] / max(i_["launches"], 1) * 1e3,
-                 "alg_gbs_isolated": i_["bytes"] / t_ / 1e9 if t_ > 0 else 0.0,
-                 "frac_hbm_isolated": i_["bytes"] / t_ / 1e9 / HBM_PEAK_GBS if t_ > 0 else 0.0}
-            if i_["mfma_bf16_flops"] > 0:
-                e["bf16_mfma_tflops_isolated"] = i_["mfma_bf16_flops"] / t_ / 1e12
-                e["frac_bf16_mfma_peak_isolated"] = e["bf16_mfma_tflops_isolated"] / MFMA_BF16_PEAK_TF
-            kernels.append(e)
-        kernels.sort(key=lambda e: -e["ms_per_step"])
-        out = {
-            "metric": "molecular graphs/sec (fwd+bwd)", "value": value, "unit": "graphs/s", "n_gpus": joined,
-            "steps": args.steps, "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3,
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-            "config": {"workload": f"BASELINE configs[{args.config - 1}]: {cfg['conv']} hidden={H} L={cfg['propagation_depth']} "
-                                   f"towers={T} pre={cfg['pre_layers']} post={cfg['post_layers']}, {per_gpu} graphs/GPU "
-                                   f"({N_nodes} atoms, {E_edges} directed bonds), fwd+loss+bwd incl. CSR packing",
-                       "graphs_per_gpu": per_gpu, "parallelism": f"dp{world}", "hip_graph": graphed,
-                       "launch": args.launch, "launch_autotune": autotune,
-                       "grad_allreduce_bytes": flat.nbytes if flat.collective else 0,
-                       "grad_exchange": ("rccl, %d per-layer slices overlapped with backward + 1" % len(flat.layer_slices)
-                                         if flat._overlap else ("rccl, one call after backward" if flat.collective
-                                                                else "none (1 rank)"))},
-            "loss": loss_val,
-            # the scatter-aggregate kernel: algorithmic bytes per launch / average launch duration (HIP events attached
-            # to the dispatch on the launch stream, as run); "bwd" carries both the as-run (two streams) and the isolated duration; "large"
-            # is the same forward kernel on cfg-4's per-GPU batch, whose 1.0 GB per launch does not fit the Infinity Cache
-            "roofline": {"bound": "hbm", "kernel": roof_kernel, "fused": fused_info, "standalone_scatter_kernel": standalone,
-                         "achieved": f_run["gbs"], "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": f_run["gbs"] / HBM_PEAK_GBS,
-                         "traffic": traffic, "traffic_source": traffic_src, "alg_bytes_per_launch": f_run["bytes"],
-                         "avg_us": f_run["avg_us"],
-                         "timing": "HIP events attached to the dispatch (hipExtLaunchKernelGGL start/stop)",
-                         "launches": f_run["launches"], "avg_us_isolated": f_iso["avg_us"],
-                         "bwd": {"alg_bytes_per_launch": b_run["bytes"], "avg_us": b_run["avg_us"], "achieved": b_run["gbs"],
-                                 "frac": b_run["gbs"] / HBM_PEAK_GBS, "avg_us_isolated": b_iso["avg_us"],
-                                 "achieved_isolated": b_iso["gbs"], "frac_isolated": b_iso["gbs"] / HBM_PEAK_GBS},
-                         "large": large},
-            "mfma": {"arithmetic": "fp32 operands as three bf16 pieces, six bf16 MFMAs per product, fp32 accumulation "
-                                   "(products and weight gradients with >= 4096 rows; GNX_GEMM_SPLIT=0 selects the "
-                                   "exact-fp32 MFMA kernels)",
-                     "ref_formulation_flops_per_graph_fwd_bwd": ref_flops,
-                     "executed_flops_per_graph_fwd_bwd": exec_flops / per_gpu,
-                     "executed_bf16_mfma_flops_per_graph": mfma_flops / per_gpu,
-                     "bf16_mfma_tflops_over_step": mfma_flops / step_s / 1e12,
-                     "frac_bf16_mfma_peak_over_step": mfma_flops / step_s / 1e12 / MFMA_BF16_PEAK_TF,
-                     "frac_bf16_mfma_peak_inside_product_kernels": (mfma_flops / (gemm_ms * 1e-3) / 1e12 / MFMA_BF16_PEAK_TF)
-                     if gemm_ms > 0 else None,
-                     "peak_bf16_mfma_tflops": MFMA_BF16_PEAK_TF, "product_kernels_ms_per_step_isolated": gemm_ms},
-            "kernels": kernels[:6],
-        }
-        if world == 1 and not args.no_cpu_baseline:
-            out["cpu_baseline"] = cpu_baseline(cfg, deg, batch_cpu, args.cpu_steps)
-        print(json.dumps(out), flush=True)
-    if dist is not None:
-        dist.barrier()
-        dist.destroy_process_group()
+    f_run, f_iso = per_launch(prof_run, agg_k), per_launch(prof_iso, agg_k)
+    roof_kernel = "k_pna_agg_fwd" if cfg["conv"] == "PNA" else "k_gine_fwd"
+    fused_info = None
+    if fused_fwd:
+        # a fused gather -> MLP -> aggregate kernel is reported against the SAME algorithmic figure as
+        # the scatter-aggregate alone (4EH + 4E + 16NH per launch) and, additionally, against its own bytes
+        fr, fi = per_launch(prof_run, _lib.K_PNA_EDGE_FWD), per_launch(prof_iso, _lib.K_PNA_EDGE_FWD)
+        scatter_bytes = 4.0 * E_edges * H + 4.0 * E_edges + 16.0 * N_nodes * H
+        fused_info = {"own_alg_bytes_per_launch": fr["bytes"], "own_achieved": fr["gbs"],
+                      "own_frac": fr["gbs"] / HBM_PEAK_GBS,
+                      "what": "message assembly (gather of P, Q, Te rows) + pre-layer-1 split-bf16 product + "
+                              "mean|min|max|std in one launch; writes h1, the messages and the aggregate once"}
+        for d_ in (fr, fi):
+            d_["bytes"] = scatter_bytes
+            d_["gbs"] = scatter_bytes / (d_["avg_us"] * 1e-6) / 1e9 if d_["avg_us"] > 0 else 0.0
+        f_run, f_iso = fr, fi
+        roof_kernel = "k_pna_edge_fwd (fused: scatter-aggregate inside the edge kernel)"
+    b_run, b_iso = per_launch(prof_run, agg_bk), per_launch(prof_iso, agg_bk)
+    # HBM traffic of the scatter kernel from the PMC counters: only if the committed counter file was collected on
+    # THIS workload (same conv, atoms, bonds, width); otherwise null
+    traffic, traffic_src = None, None
+    pmc = os.path.join(ROOT, "profiles", "pmc_scatter.json")
+    if os.path.exists(pmc):
+        try:
+            pj = json.load(open(pmc))
+            if (pj.get("conv", "PNA") == cfg["conv"] and pj.get("N") == N_nodes and pj.get("E") == E_edges
+                    and pj.get("H") == H and pj.get("kernel", "k_pna_agg_fwd").startswith(roof_kernel.split(" ")[0])):
+                traffic = pj.get("traffic_bytes_per_launch")
+                # PMC counters need rocprofv3: the figure is NOT measured in this run, it is read from the committed file
+                traffic_src = f"profiles/pmc_scatter.json ({pj.get('round', 'r?')}, rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes)"
+        except Exception:  # pylint: disable=broad-except
+            traffic = None
+    # the step's products: algorithmic FLOPs executed (the restructured layers do fewer than the reference
+    # formulation), and the bf16-MFMA FLOPs the split-operand kernels issue for them (6 per algorithmic one)
+    gemm_groups = (_lib.K_GEMM_WS, _lib.K_GEMM_TILED, _lib.K_GEMM_SMALL, _lib.K_GEMM_WGRAD, _lib.K_GEMM_WGRAD_BATCHED)
+    exec_flops = sum(prof_run[k]["flops"] for k in gemm_groups) / args.steps
+    mfma_flops = sum(prof_run[k]["mfma_bf16_flops"] for k in gemm_groups) / args.steps
+    gemm_ms = sum(prof_iso[k]["ms"] for k in gemm_groups) / args.steps
+    step_s = elapsed / args.steps
+    ref_flops = 3 * ref_flops_per_graph(cfg) if args.config != 5 else None
+    kernels = []
+    for k, name in _lib.KERNEL_GROUPS.items():
+        r_, i_ = prof_run[k], prof_iso[k]
+        if r_["launches"] == 0:
+            continue
+        t_ = i_["ms"] * 1e-3
+        e = {"group": name, "launches_per_step": r_["launches"] / args.steps, "ms_per_step": r_["ms"] / args.steps,
+             "ms_per_step_isolated": i_["ms"] / args.steps, "avg_us_isolated": i_["ms"] / max(i_["launches"], 1) * 1e3,
+             "alg_gbs_isolated": i_["bytes"] / t_ / 1e9 if t_ > 0 else 0.0,
+             "frac_hbm_isolated": i_["bytes"] / t_ / 1e9 / HBM_PEAK_GBS if t_ > 0 else 0.0}
+        if i_["mfma_bf16_flops"] > 0:
+            e["bf16_mfma_tflops_isolated"] = i_["mfma_bf16_flops"] / t_ / 1e12
+            e["frac_bf16_mfma_peak_isolated"] = e["bf16_mfma_tflops_isolated"] / MFMA_BF16_PEAK_TF
+        kernels.append(e)
+    kernels.sort(key=lambda e: -e["ms_per_step"])
+    return {
+        # the scatter-aggregate kernel: algorithmic bytes per launch / average launch duration (HIP events attached
+        # to the dispatch on the launch stream, as run); "bwd" carries both the as-run (two streams) and the isolated duration; "large"
+        # is the same forward kernel on cfg-4's per-GPU batch, whose 1.0 GB per launch does not fit the Infinity Cache
+        "roofline": {"bound": "hbm", "kernel": roof_kernel, "fused": fused_info, "standalone_scatter_kernel": standalone,
+                     "achieved": f_run["gbs"], "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": f_run["gbs"] / HBM_PEAK_GBS,
+                     "traffic": traffic, "traffic_source": traffic_src, "alg_bytes_per_launch": f_run["bytes"],
+                     "avg_us": f_run["avg_us"],
+                     "timing": "HIP events attached to the dispatch (hipExtLaunchKernelGGL start/stop)",
+                     "launches": f_run["launches"], "avg_us_isolated": f_iso["avg_us"],
+                     "bwd": {"alg_bytes_per_launch": b_run["bytes"], "avg_us": b_run["avg_us"], "achieved": b_run["gbs"],
+                             "frac": b_run["gbs"] / HBM_PEAK_GBS, "avg_us_isolated": b_iso["avg_us"],
+                             "achieved_isolated": b_iso["gbs"], "frac_isolated": b_iso["gbs"] / HBM_PEAK_GBS},
+                     "large": large},
+        "mfma": {"arithmetic": "fp32 operands as three bf16 pieces, six bf16 MFMAs per product, fp32 accumulation "
+                               "(products and weight gradients with >= 4096 rows; GNX_GEMM_SPLIT=0 selects the "
+                               "exact-fp32 MFMA kernels)",
+                 "ref_formulation_flops_per_graph_fwd_bwd": ref_flops,
+                 "executed_flops_per_graph_fwd_bwd": exec_flops / per_gpu,
+                 "executed_bf16_mfma_flops_per_graph": mfma_flops / per_gpu,
+                 "bf16_mfma_tflops_over_step": mfma_flops / step_s / 1e12,
+                 "frac_bf16_mfma_peak_over_step": mfma_flops / step_s / 1e12 / MFMA_BF16_PEAK_TF,
+                 "frac_bf16_mfma_peak_inside_product_kernels": (mfma_flops / (gemm_ms * 1e-3) / 1e12 / MFMA_BF16_PEAK_TF)
+                 if gemm_ms > 0 else None,
+                 "peak_bf16_mfma_tflops": MFMA_BF16_PEAK_TF, "product_kernels_ms_per_step_isolated": gemm_ms},
+        "kernels": kernels[:6],
+    }
 
 
 def scatter_standalone(dev, cfg, b, model, launches: int = 12):

@@ -305,6 +305,19 @@ def test_bench_gpus_flag_starts_that_many_ranks():
     assert out["n_gpus"] == 2 and out["config"]["parallelism"] == "dp2" and out["steps"] == 2 and out["warmup"] == 1
 
 
+def test_bench_dump_outputs_and_step_count(tmp_path):
+    import json
+    import numpy as np
+    r = _run_bench(["--gpus", "2", "--dry-run", "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path)])
+    assert r.returncode == 0, r.stderr
+    out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+    assert out["steps"] == 3 and out["ms_per_step"] > 0, out
+    g = np.load(tmp_path / "grads.npy")
+    assert g.dtype == np.float32 and g.shape == (2204931,) and np.all(g == 1.5)  # the average of ranks' 1.0 and 2.0
+    r = _run_bench(["--dry-run", "--steps", "0"])
+    assert r.returncode == 2 and "--steps" in r.stderr
+
+
 def test_bench_under_torchrun_is_one_of_the_ranks():
     """The driver's launch line: python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N."""
     import json
