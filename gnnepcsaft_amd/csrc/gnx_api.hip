@@ -264,23 +264,8 @@ extern "C" int32_t gnx_scale(gnx_handle* h, float* p, int64_t n, float v) {
 // configs/pna_msigmae_7.py:40).  Counter-based Philox4x32-10: element i of a call is decided by the 128-bit counter
 // (i / 4, offset) under the 64-bit key `seed` -- no state, so the backward pass RECOMPUTES the mask from
 // (seed, offset) instead of storing it, and forward / backward agree by construction.  One thread = 4 consecutive
-// elements = one Philox block.
+// elements = one Philox block (philox4x32_10 in gnx_common.hpp).
 // ---------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void philox4x32_10(uint32_t (&c)[4], uint32_t k0, uint32_t k1) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const uint32_t hi0 = __umulhi(0xD2511F53u, c[0]), lo0 = 0xD2511F53u * c[0];
-    const uint32_t hi1 = __umulhi(0xCD9E8D57u, c[2]), lo1 = 0xCD9E8D57u * c[2];
-    const uint32_t n0 = hi1 ^ c[1] ^ k0, n2 = hi0 ^ c[3] ^ k1;
-    c[0] = n0;
-    c[1] = lo1;
-    c[2] = n2;
-    c[3] = lo0;
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
-  }
-}
-
 __global__ void __launch_bounds__(256) k_dropout(const float* __restrict__ x, int64_t n, float p, float scale,
                                                  uint64_t seed, uint64_t offset, float* __restrict__ y) {
   const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;  // block of 4 elements

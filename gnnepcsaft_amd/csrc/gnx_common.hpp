@@ -131,6 +131,24 @@ int32_t gnx_read_flag(gnx_handle* h, int* value);
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
+// Counter-based Philox4x32-10 (Salmon et al., SC'11): the 128-bit counter c is replaced by its 10-round image under the
+// 64-bit key (k0, k1).  Shared by gnx_dropout and the attention dropout of gnx_transformer_attn_*, which both decide
+// element e of a call from the block (e / 4, offset) and its word e % 4, so a mask is recomputed instead of stored.
+__device__ __forceinline__ void philox4x32_10(uint32_t (&c)[4], uint32_t k0, uint32_t k1) {
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    const uint32_t hi0 = __umulhi(0xD2511F53u, c[0]), lo0 = 0xD2511F53u * c[0];
+    const uint32_t hi1 = __umulhi(0xCD9E8D57u, c[2]), lo1 = 0xCD9E8D57u * c[2];
+    const uint32_t n0 = hi1 ^ c[1] ^ k0, n2 = hi0 ^ c[3] ^ k1;
+    c[0] = n0;
+    c[1] = lo1;
+    c[2] = n2;
+    c[3] = lo0;
+    k0 += 0x9E3779B9u;
+    k1 += 0xBB67AE85u;
+  }
+}
+
 // Zero-fill as a kernel launch: hipMemsetAsync costs ~50 us of host time per call on this stack (it showed up as idle
 // gaps of that size between the packer's tiny kernels); a launch costs ~5 us.
 template <typename T>

@@ -948,3 +948,83 @@ class GINEConvFn(torch.autograd.Function):
         ops.finish_backward(x.device, all(k is not None for k in sk), sk)
         outs = [None if k is not None else g_ for g_, k in zip((dlw, dlb, dw0, db0, dw2, db2), sk)]
         return (dx, dBE, None, None, *outs, None, None)
+
+
+def _stacked(tensors: Sequence[torch.Tensor]) -> torch.Tensor:
+    """[sum rows, H] of 2-D tensors: a view when they are consecutive row blocks of one buffer, else a copy."""
+    t = adjacent_rows(tensors)
+    return t if t is not None else torch.cat([w.detach() for w in tensors], dim=0)
+
+
+class TransformerConvFn(torch.autograd.Function):
+    """[3P] torch_geometric.nn.TransformerConv(H, H // heads, heads, concat=True, beta=False, root_weight=True,
+    edge_dim=H) as built at models.py:497-511.  lin_edge has no bias, so lin_edge(edge_attr) is evaluated on the 60-row
+    bond table (Le[code]); the four node projections are ONE [N,H] x [H,4H] product into q|k|v|s; the segmented softmax
+    attention (dropout on alpha included) and its backward are gnx_transformer_attn_* (no [E,H] tensor).
+
+    ``cfg`` = (heads, p, seed, offset, bond_acc, layer_index): p = attention dropout (0 in eval), its mask keyed by
+    (seed, offset); ``bond_acc`` / ``layer_index`` as for GINEConvFn."""
+
+    @staticmethod
+    def forward(ctx, x, BE, pack: GraphPack, cfg, wq, bq, wk, bk, wv, bv, we, ws, bs):
+        heads, p, seed, offset, bond_acc, layer_index = cfg
+        x = x.contiguous()
+        N, H = x.shape
+        R = BE.size(0)
+        Le = ops.gemm([(BE, None, we)], _empty(R, we.size(0), x))
+        W4 = _stacked([wq, wk, wv, ws])
+        b4 = _stacked([b.view(1, -1) for b in (bq, bk, bv, bs)])
+        qkvs = ops.gemm([(x, None, W4)], _empty(N, 4 * H, x), bias=b4)
+        out, alpha, _ = ops.transformer_attn_fwd(qkvs, Le, pack, heads, p, seed, offset)
+        ctx.pack, ctx.key = pack, (int(heads), float(p), int(seed), int(offset))
+        ctx.bond_acc, ctx.layer_index = bond_acc, layer_index
+        ctx.sinks = grad_sinks([wq, bq, wk, bk, wv, bv, we, ws, bs])
+        ctx.save_for_backward(x, BE, Le, qkvs, alpha, W4, we)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        x, BE, Le, qkvs, alpha, W4, we = ctx.saved_tensors
+        pack: GraphPack = ctx.pack
+        heads, p, seed, offset = ctx.key
+        dout = dout.contiguous()
+        N, H = x.shape
+        sk = ctx.sinks
+        # gradient buffers in parameter order: wq, bq, wk, bk, wv, bv, we, ws, bs
+        shapes = [(H, H), (H,), (H, H), (H,), (H, H), (H,), tuple(we.shape), (H, H), (H,)]
+        grads = [g_ if g_ is not None else ops.zeros(*s, device=x.device) for g_, s in zip(sk, shapes)]
+        acc = ctx.bond_acc
+        dqkv, scratch, dLe = ops.transformer_attn_bwd(dout, qkvs, Le, alpha, pack, heads, p, seed, offset,
+                                                      want_dle=acc is None)
+        # weight / bias gradients of the four projections in one batched launch (the skip gradient is dout itself)
+        for t in range(3):
+            ops.queue_wgrad(dqkv[:, t * H:(t + 1) * H], x, grads[2 * t], dbias=grads[2 * t + 1])
+        ops.queue_wgrad(dout, x, grads[7], dbias=grads[8])
+        ops.flush_wgrads()
+        dx = None
+        if ctx.needs_input_grad[0]:
+            dx = ops.gemm([(dqkv, None, W4[:3 * H]), (dout, None, W4[3 * H:])], _empty(N, H, x), b_trans=False)
+        if acc is None:  # stand-alone layer: everything on the main stream, dBE handed back at once
+            ops.gemm_wgrad(dLe, BE, grads[6])
+            dBE = ops.gemm([(dLe, None, we)], _empty(BE.size(0), BE.size(1), x), b_trans=False)
+        else:
+            # the bond-table gradient (a by-code segment sum over the edges) and what hangs off it run on side stream 1
+            # into the shared accumulator, as for GINEConvFn
+            code_pos = pack.code_index(Le.size(0)) if pack.E > 0 else None  # built (once per batch) on the main stream
+            keep = [dout, qkvs, scratch, Le, BE, we, grads[6], acc.buf]
+
+            def bond_chain():
+                dLe_ = ops.transformer_attn_dle(dout, qkvs, scratch, Le, pack, heads, code_pos)
+                ops.gemm_wgrad_inline(dLe_, BE, grads[6])
+                if acc.first_in_backward(ctx.layer_index):
+                    ops.zero_(acc.buf)
+                ops.gemm([(dLe_, None, we)], acc.buf, b_trans=False, accumulate=True)
+                keep.append(dLe_)
+
+            ops.run_on_second_side_stream(dout, keep, bond_chain)
+            dBE = None
+            if ctx.layer_index == 0:
+                dBE = acc.handoff(x.device)
+        ops.finish_backward(x.device, all(k is not None for k in sk), sk)
+        outs = [None if k is not None else g_ for g_, k in zip(grads, sk)]
+        return (dx, dBE, None, None, *outs)

@@ -45,6 +45,9 @@ class InferenceEngine:
         model's ``max_degree_hint``): an upper bound of the in-degree makes packing sync-free; a batch above it trips
         the range flag (``ops.check_range``).  ``None`` reads each batch's maximum back (one sync per call)."""
         model = getattr(model, "model", model)
+        if isinstance(model.convs[0], gnn.TransformerConv):
+            raise NotImplementedError("InferenceEngine covers PNA and GINE models; evaluate a Transformer model with "
+                                      "model.eval() and its forward / pred_with_bounds")
         p0 = next(model.parameters())
         if not p0.is_cuda:
             raise ValueError("InferenceEngine needs the model on a HIP device (there is no CPU fallback)")

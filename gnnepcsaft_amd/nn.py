@@ -1,6 +1,6 @@
 """Native (HIP-backed) stand-ins for the third-party modules the reference wires in
 ``/root/reference/gnnepcsaft/train/models.py``: ogb ``AtomEncoder``/``BondEncoder`` (:12, :175-176), PyG ``PNAConv``
-(:445-457), ``GINEConv`` (:529-538), ``BatchNorm`` (:17, :184), ``aggr.Sum/Mean/MaxAggregation`` (:587-595).
+(:445-457), ``GINEConv`` (:529-538), ``TransformerConv`` (:497-511), ``BatchNorm`` (:17, :184), ``aggr.Sum/Mean/MaxAggregation`` (:587-595).
 
 Attribute and state-dict names follow upstream so that reference checkpoints' ``state_dict``s load unchanged
 (SURVEY.md §8b).  Where the reference passes ``edge_index`` / ``edge_attr[E,H]`` these modules take a ``GraphPack``
@@ -33,6 +33,11 @@ class ReLU(Module):
         raise RuntimeError("standalone ReLU is fused into the producing kernel on this path")
 
 
+# a mask counter that lives on the host cannot advance inside a captured step
+_CAPTURE_REFUSAL = ("{}(p > 0) cannot be captured into a HIP graph: its per-call mask counter lives on the host; run the "
+                    "training step eagerly (bench.py --launch eager)")
+
+
 class Dropout(Module):
     """torch.nn.Dropout(p) on the HIP path (reference models.py:177, 209).  Identity in eval mode and for p = 0 (no
     launch).  In training mode every call draws a fresh mask from a counter-based generator: key = ``seed`` (taken from
@@ -56,8 +61,7 @@ class Dropout(Module):
         if x.is_cuda and torch.cuda.is_current_stream_capturing():
             # the mask counter is a host integer passed to the kernel by value: a captured step would replay ONE mask for
             # ever (and the checkpointed counter would stop advancing) -- refuse instead of silently training wrong
-            raise RuntimeError("Dropout(p > 0) cannot be captured into a HIP graph: its per-call mask counter lives on the "
-                               "host; run the training step eagerly (bench.py --launch eager)")
+            raise RuntimeError(_CAPTURE_REFUSAL.format("Dropout"))
         self.calls += 1
         return Fn.DropoutFn.apply(x, self.p, self.seed, self.calls)
 
@@ -267,6 +271,58 @@ class GINEConv(Module):
         l0, l2 = self.nn[0], self.nn[2]
         return Fn.GINEConvFn.apply(x, edge_attr, edge_index, self.eps_value(), self.lin.weight, self.lin.bias,
                                    l0.weight, l0.bias, l2.weight, l2.bias, bond_acc, layer_index)
+
+
+class TransformerConv(Module):
+    """[3P] torch_geometric.nn.TransformerConv(in_channels, out_channels, heads, concat=True, beta=False, dropout,
+    edge_dim, bias=True, root_weight=True) as constructed at models.py:497-511 (aggregation "add", no self-loops).
+    State-dict keys as upstream: lin_key / lin_query / lin_value / lin_skip (weight, bias) and lin_edge.weight (no bias).
+
+    Attention dropout (training mode, p > 0) draws a fresh mask per call like ``Dropout``: key = ``seed`` (drawn from
+    torch's default generator at construction unless given, so ``torch.manual_seed`` makes runs repeatable and every
+    layer gets its own stream), counter = ``calls``; checkpointing ``(seed, calls)`` resumes the stream exactly."""
+
+    def __init__(self, in_channels: int, out_channels: int, heads: int = 1, concat: bool = True, beta: bool = False,
+                 dropout: float = 0.0, edge_dim: Optional[int] = None, bias: bool = True, root_weight: bool = True,
+                 seed: Optional[int] = None):
+        super().__init__()
+        if not concat or beta or not root_weight or not bias:
+            raise ValueError("native TransformerConv implements concat=True, beta=False, root_weight=True, bias=True "
+                             "(models.py:505-511)")
+        if edge_dim is None:
+            raise ValueError("native TransformerConv needs edge_dim (models.py:510)")
+        if in_channels != heads * out_channels:
+            raise ValueError("native TransformerConv needs in_channels == heads * out_channels (models.py:505-507)")
+        if dropout < 0.0 or dropout >= 1.0:
+            raise ValueError(f"attention dropout must be in [0, 1), got {dropout}")
+        self.in_channels, self.out_channels, self.heads = in_channels, out_channels, heads
+        self.concat, self.beta, self.root_weight, self.edge_dim = concat, beta, root_weight, edge_dim
+        self.dropout = float(dropout)
+        H = heads * out_channels
+        self.lin_key = Linear(in_channels, H)
+        self.lin_query = Linear(in_channels, H)
+        self.lin_value = Linear(in_channels, H)
+        self.lin_edge = Linear(edge_dim, H, bias=False)
+        self.lin_skip = Linear(in_channels, H, bias=bias)
+        self.seed = int(torch.randint(0, 2 ** 62, (1,)).item() if seed is None else seed) & (2 ** 63 - 1)
+        self.calls = 0
+
+    def forward(self, x: torch.Tensor, edge_index: GraphPack, edge_attr: torch.Tensor, bond_acc=None,
+                layer_index: int = 0) -> torch.Tensor:
+        """x fp32[N,H]; edge_index: GraphPack of the batch; edge_attr: fp32[60,H] encoded bond table; ``bond_acc`` /
+        ``layer_index`` as for ``PNAConv``."""
+        p = self.dropout if self.training else 0.0
+        if p > 0.0:
+            if x.is_cuda and torch.cuda.is_current_stream_capturing():
+                raise RuntimeError(_CAPTURE_REFUSAL.format("TransformerConv attention dropout"))
+            self.calls += 1
+        q, k, v, s = self.lin_query, self.lin_key, self.lin_value, self.lin_skip
+        cfg = (self.heads, p, self.seed, self.calls, bond_acc, layer_index)
+        return Fn.TransformerConvFn.apply(x, edge_attr, edge_index, cfg, q.weight, q.bias, k.weight, k.bias, v.weight,
+                                          v.bias, self.lin_edge.weight, s.weight, s.bias)
+
+    def extra_repr(self) -> str:
+        return f"{self.in_channels}, {self.out_channels}, heads={self.heads}, dropout={self.dropout}"
 
 
 class BatchNorm1d(torch.nn.BatchNorm1d):

@@ -827,6 +827,68 @@ def gine_dle(dout: torch.Tensor, x: torch.Tensor, Le: torch.Tensor, g: GraphPack
     return dLe
 
 
+def transformer_attn_fwd(qkvs: torch.Tensor, Le: torch.Tensor, g: GraphPack, heads: int, p: float = 0.0,
+                         seed: int = 0, offset: int = 0, want_mask: bool = False
+                         ) -> Tuple[torch.Tensor, torch.Tensor, Optional[torch.Tensor]]:
+    """TransformerConv attention over the CSR (gnx_transformer_attn_fwd): qkvs [N,4H] = q|k|v|s, Le [R,H] ->
+    (out [N,H], alpha [E,heads] in CSR order, keep mask uint8 [E,heads] if ``want_mask``).  p > 0: dropout on alpha with
+    the mask keyed by (seed, offset)."""
+    qkvs = _f32(qkvs, "qkvs").contiguous()
+    Le = _f32(Le, "Le").contiguous()
+    N, H = qkvs.size(0), qkvs.size(1) // 4
+    if qkvs.size(1) != 4 * H or Le.size(1) != H or heads <= 0 or H % heads != 0:
+        raise _lib.GnxError(_lib.GNX_E_INVALID, f"transformer_attn_fwd: qkvs {tuple(qkvs.shape)} Le {tuple(Le.shape)} "
+                                                f"heads {heads}")
+    dev = qkvs.device
+    out = torch.empty(N, H, dtype=torch.float32, device=dev)
+    alpha = torch.empty(g.E, heads, dtype=torch.float32, device=dev)
+    keep = torch.empty(g.E, heads, dtype=torch.uint8, device=dev) if want_mask else None
+    check(_lib.load().gnx_transformer_attn_fwd(handle(dev), qkvs.data_ptr(), Le.data_ptr(), g.rowptr.data_ptr(),
+                                               g.src.data_ptr(), g.code.data_ptr(), N, g.E, int(heads), H // int(heads),
+                                               float(p), int(seed) & (2 ** 64 - 1), int(offset) & (2 ** 64 - 1),
+                                               out.data_ptr(), alpha.data_ptr(), _ptr(keep)))
+    return out, alpha, keep
+
+
+def transformer_attn_bwd(dout: torch.Tensor, qkvs: torch.Tensor, Le: torch.Tensor, alpha: torch.Tensor, g: GraphPack,
+                         heads: int, p: float = 0.0, seed: int = 0, offset: int = 0, want_dle: bool = True
+                         ) -> Tuple[torch.Tensor, torch.Tensor, Optional[torch.Tensor]]:
+    """Backward of ``transformer_attn_fwd``: (dqkv [N,3H] = dq|dk|dv (deterministic), scratch [2,E,heads] for
+    ``transformer_attn_dle``, dLe [R,H] if ``want_dle``)."""
+    dout = _f32(dout, "dout").contiguous()
+    N, H = dout.shape
+    dev = dout.device
+    dqkv = torch.empty(N, 3 * H, dtype=torch.float32, device=dev)
+    scratch = torch.empty(2, g.E, heads, dtype=torch.float32, device=dev)
+    dLe = zeros(*Le.shape, device=dev) if want_dle else None
+    pos = g.code_index(Le.size(0)) if (want_dle and g.E > 0) else None
+    if want_dle and g.E > 0 and pos is None:
+        raise _lib.GnxError(_lib.GNX_E_INVALID, f"transformer_attn_bwd: {Le.size(0)} bond codes exceed the inverted index")
+    check(_lib.load().gnx_transformer_attn_bwd(handle(dev), dout.data_ptr(), qkvs.data_ptr(), Le.data_ptr(),
+                                               alpha.data_ptr(), g.rowptr.data_ptr(), g.src.data_ptr(), g.dst.data_ptr(),
+                                               g.code.data_ptr(), g.colptr.data_ptr(), g.cpos.data_ptr(), _ptr(pos), N,
+                                               g.E, int(heads), H // int(heads), Le.size(0), float(p),
+                                               int(seed) & (2 ** 64 - 1), int(offset) & (2 ** 64 - 1), dqkv.data_ptr(),
+                                               scratch.data_ptr(), _ptr(dLe)))
+    return dqkv, scratch, dLe
+
+
+def transformer_attn_dle(dout: torch.Tensor, qkvs: torch.Tensor, scratch: torch.Tensor, Le: torch.Tensor, g: GraphPack,
+                         heads: int, pos: Optional[torch.Tensor]) -> torch.Tensor:
+    """dLe [R,H] from the scratch of ``transformer_attn_bwd``, on the handle's current stream; ``pos`` =
+    ``g.code_index(R)`` fetched by the caller (it may build the index, which must not happen on a side stream)."""
+    R, H = Le.shape
+    dLe = zeros(R, H, device=dout.device)
+    if g.E == 0:
+        return dLe
+    if pos is None:
+        raise _lib.GnxError(_lib.GNX_E_INVALID, f"transformer_attn_dle: {R} bond codes exceed the inverted index")
+    check(_lib.load().gnx_transformer_attn_dle(handle(dout.device), dout.data_ptr(), qkvs.data_ptr(), scratch.data_ptr(),
+                                               g.dst.data_ptr(), g.code.data_ptr(), pos.data_ptr(), g.E, int(heads),
+                                               H // int(heads), R, dLe.data_ptr()))
+    return dLe
+
+
 _POOL = {"add": _lib.POOL_ADD, "sum": _lib.POOL_ADD, "mean": _lib.POOL_MEAN, "max": _lib.POOL_MAX}
 
 

@@ -3,7 +3,7 @@ state-dict names and config keys, with the forward/backward running on hand-writ
 
 Mirrors: ``GNNePCSAFTL`` (:23-156), ``GNNePCSAFT`` (:159-254), ``get_conv`` (:441-584), ``get_global_pool`` (:587-595),
 ``create_model`` (:598-606).  Out of scope: the HabitchNN MLP baseline (:257-438) and every conv other
-than PNA / GINE — the dispatch is kept and raises for them.
+than PNA / GINE / Transformer — the dispatch is kept and raises for them.
 """
 from __future__ import annotations
 
@@ -21,7 +21,7 @@ from ..nn import BatchNorm, BatchNorm1d, Linear, ReLU
 from ..ops import GraphPack
 from .lightning_lite import LightningModuleLite
 
-_OUT_OF_SCOPE_CONVS = ("GCN", "GAT", "GATv2", "Transformer", "SAGE", "GIN", "Edge", "GatedGraph", "Graph", "ARMA", "SG")
+_OUT_OF_SCOPE_CONVS = ("GCN", "GAT", "GATv2", "SAGE", "GIN", "Edge", "GatedGraph", "Graph", "ARMA", "SG")
 _ASSOC_DATASETS = ("esper_assoc", "esper_assoc_only")  # datasets whose label is ``graphs.assoc`` (reference :80-87)
 # parameter bounds (reference :167-172): m, sigma, epsilon/k | log10 kappa_ab (negated), log10 epsilon_ab
 _LOWER = (1.0, 1.9, 50.0, -math.log10(0.9), math.log10(200.0))
@@ -174,7 +174,7 @@ class GNNePCSAFT(torch.nn.Module):  # pylint: disable=R0902
             elif ahead is not None:
                 extra["prepared"] = ahead.wait()
                 ahead = convs[l + 1].prepare_ahead(pack, bond_table) if l + 1 < len(convs) else None
-            # PNA and GINE both take edge_attr (reference :211-214); the ReLU is fused into the BatchNorm kernel
+            # PNA, GINE and Transformer all take edge_attr (reference :211-214); the ReLU is fused into the BatchNorm kernel
             h = norm(layer(x=self.dropout(h), edge_index=pack, edge_attr=bond_table, **extra), relu=True)
         if batch is not None or pack.has_batch:
             h = self.global_pool(h, pack)
@@ -211,9 +211,13 @@ def get_conv(config: dict):
                            pre_layers=config["pre_layers"], post_layers=config["post_layers"], divide_input=True)
     if kind == "GINE":
         return gnn.GINEConv(nn=Sequential(Linear(H, H), ReLU(), Linear(H, H)), train_eps=False, edge_dim=H)
+    if kind == "Transformer":
+        assert H % config["heads"] == 0, "hidden_dim must be divisible by heads"
+        return gnn.TransformerConv(in_channels=H, out_channels=H // config["heads"], heads=config["heads"], concat=True,
+                                   dropout=config["dropout"], edge_dim=H)
     if kind in _OUT_OF_SCOPE_CONVS:
         raise NotImplementedError(
-            f"conv={config['conv']!r} is outside the MI355X hot-path scope (PNA, GINE); see SURVEY.md §2 row 2")
+            f"conv={config['conv']!r} is outside the MI355X hot-path scope (PNA, GINE, Transformer); see SURVEY.md §2 row 2")
     raise ValueError(f"Unsupported convolution: {config['conv']}.")
 
 

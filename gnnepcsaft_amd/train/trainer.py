@@ -163,6 +163,9 @@ class Trainer:
             drop = getattr(model.model, "dropout", None)
             if drop is not None and hasattr(drop, "calls"):
                 ckpt["dropout"] = {"seed": int(drop.seed), "calls": int(drop.calls)}
+            attn = [c for c in model.model.convs if hasattr(c, "calls")]  # TransformerConv attention dropout
+            if attn:
+                ckpt["attn_dropout"] = [{"seed": int(c.seed), "calls": int(c.calls)} for c in attn]
             tmp = path + ".tmp"
             torch.save(ckpt, tmp)
             os.replace(tmp, path)
@@ -216,6 +219,10 @@ class Trainer:
             drop = getattr(model.model, "dropout", None)
             if ckpt.get("dropout") and drop is not None and hasattr(drop, "calls"):
                 drop.seed, drop.calls = int(ckpt["dropout"]["seed"]), int(ckpt["dropout"]["calls"])
+            attn = [c for c in model.model.convs if hasattr(c, "calls")]
+            if ckpt.get("attn_dropout") and len(ckpt["attn_dropout"]) == len(attn):
+                for c, st in zip(attn, ckpt["attn_dropout"]):
+                    c.seed, c.calls = int(st["seed"]), int(st["calls"])
         prev_in_place = Fn._GRAD_IN_PLACE  # pylint: disable=protected-access
         prev_validate = model.model.validate_inputs
         Fn.set_grad_in_place(self.fused_optimizer)

@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define GNX_ABI_VERSION 3
+#define GNX_ABI_VERSION 4
 
 enum {
   GNX_OK = 0,
@@ -99,7 +99,9 @@ enum {
   GNX_K_EMBED = 15,             /* embedding sums, forward and backward */
   GNX_K_PNA_EDGE_FWD = 16,      /* fused message assembly -> pre-layer 1 -> scatter-aggregate (gnx_pna_edge_fwd) */
   GNX_K_PNA_EDGE_BWD = 17,      /* fused masked input gradient of pre-layer 1 + destination sums + bond-table sums (gnx_pna_edge_bwd) */
-  GNX_K_COUNT = 18
+  GNX_K_ATTN_FWD = 18,          /* TransformerConv segmented-softmax attention forward (gnx_transformer_attn_fwd) */
+  GNX_K_ATTN_BWD = 19,          /* its destination- and source-side backward passes (gnx_transformer_attn_bwd) */
+  GNX_K_COUNT = 20
 };
 /* start recording a HIP event pair around every launch of the kernels whose id bit is set in kernel_mask
  * (bit k = GNX_K_* id k).  Events go on the handle's stream, i.e. the stream the kernels run on. */
@@ -362,6 +364,37 @@ int32_t gnx_gine_aggregate_bwd(gnx_handle* h, const float* dout, const float* x,
 int32_t gnx_gine_dle(gnx_handle* h, const float* dout, const float* x, const float* Le, const int32_t* src,
                      const int32_t* dst, const int32_t* code, const int32_t* code_pos, int64_t E, int32_t H, int32_t R,
                      float* dLe);
+
+/* ---- TransformerConv attention (segmented softmax over the dst-sorted CSR) ---------------------------------- */
+/* [3P] TransformerConv(H, C, heads, concat=True, beta=False, root_weight=True, edge_dim=H) (ref: train/models.py:497-511),
+ * H = heads * C.  qkvs [N, 4H] = q | k | v | s (the four node projections, biases included); Le [R, H] = lin_edge of the
+ * bond table (edge p = j -> i with bond code c uses Le[c]).  Per head h:
+ *   score_p = <q_i, k_j + Le_c> / sqrt(C);  alpha_p = exp(score_p - max_row) / (sum_row exp(. - max_row) + 1e-16);
+ *   out_i = concat_h sum_p alpha'_p (v_j + Le_c) + s_i,  alpha'_p = alpha_p keep_p / (1 - p)  (p = 0: alpha' = alpha).
+ * keep(p, h) is Philox4x32-10 on element e = p * heads + h (counter (e / 4, offset), key seed; the scheme of gnx_dropout),
+ * recomputed by the backward.  Outputs: out [N, H]; alpha [E, heads] in CSR order (before dropout); keep uint8 [E, heads]
+ * (may be NULL; 1 = kept).  C % 4 == 0 with C / 4 a power of two up to 64 or C a multiple of 256; H <= 1024; float
+ * operands 16-byte aligned.  A node without in-edges gets out_i = s_i.  Any in-degree. */
+int32_t gnx_transformer_attn_fwd(gnx_handle* h, const float* qkvs, const float* Le, const int32_t* rowptr,
+                                 const int32_t* src, const int32_t* code, int64_t N, int64_t E, int32_t heads,
+                                 int32_t C, float p, uint64_t seed, uint64_t offset, float* out, float* alpha,
+                                 uint8_t* keep);
+/* backward of the same call given dout [N, H] and the saved alpha: dqkv [N, 3H] = dq | dk | dv, deterministic (no
+ * floating-point atomics: a destination-side pass per row writes dq and a source-side pass per node over colptr / cpos
+ * writes dk, dv).  scratch: caller-owned fp32 [2, E, heads] = dscore_p = alpha_p (dalpha_p - sum_row alpha dalpha) /
+ * sqrt(C) and alpha'_p, kept for gnx_transformer_attn_dle.  dLe [R, H] (may be NULL = not computed here) is ACCUMULATED
+ * (+=) as gnx_transformer_attn_dle does. */
+int32_t gnx_transformer_attn_bwd(gnx_handle* h, const float* dout, const float* qkvs, const float* Le,
+                                 const float* alpha, const int32_t* rowptr, const int32_t* src, const int32_t* dst,
+                                 const int32_t* code, const int32_t* colptr, const int32_t* cpos,
+                                 const int32_t* code_pos, int64_t N, int64_t E, int32_t heads, int32_t C, int32_t R,
+                                 float p, uint64_t seed, uint64_t offset, float* dqkv, float* scratch, float* dLe);
+/* dLe[c] += sum over the edges with bond code c of dscore_p q_dst + alpha'_p dout_dst, from the scratch of
+ * gnx_transformer_attn_bwd, as its own call so that it can run on a side stream; code_pos = CSR positions stably grouped
+ * by code (gnx_group_by_small_key, required).  One atomic add per channel and key run. */
+int32_t gnx_transformer_attn_dle(gnx_handle* h, const float* dout, const float* qkvs, const float* scratch,
+                                 const int32_t* dst, const int32_t* code, const int32_t* code_pos, int64_t E,
+                                 int32_t heads, int32_t C, int32_t R, float* dLe);
 
 /* ---- contiguous segment reduce: global pool (ref: train/models.py:218-225, 587-595) ------------------------ */
 enum { GNX_POOL_ADD = 0, GNX_POOL_MEAN = 1, GNX_POOL_MAX = 2 };
