@@ -10,7 +10,7 @@ import torch
 
 _LIB_PATH = Path(__file__).resolve().parent / "libgnnepcsaft_hip.so"
 
-ABI_VERSION = 4
+ABI_VERSION = 5
 GNX_OK, GNX_E_INVALID, GNX_E_HIP, GNX_E_RANGE, GNX_E_WORKSPACE = 0, -1, -2, -3, -4
 # gnx_set_option ids (include/gnx.h)
 OPT_GEMM_SPLIT, OPT_GEMM_WS, OPT_GEMM_VEC, OPT_WGRAD_VEC, OPT_WGRAD_WGS, OPT_AGG_BWD_RECOMPUTE, OPT_EMBED_BWD_MFMA, \
@@ -19,15 +19,16 @@ GEMM_RELU, GEMM_ACCUMULATE, GEMM_B_TRANS, GEMM_SPLIT_ONLY, GEMM_PRESPLIT = 1, 2,
 POOL_ADD, POOL_MEAN, POOL_MAX = 0, 1, 2
 K_NONE, K_PNA_AGG_FWD, K_PNA_AGG_BWD, K_GEMM_WS, K_GEMM_WGRAD, K_GINE_AGG_FWD, K_GINE_AGG_BWD, K_EDGE_COMBINE_FWD, \
     K_EDGE_COMBINE_BWD, K_BN_FWD, K_BN_BWD, K_GEMM_TILED, K_GEMM_SMALL, K_GEMM_WGRAD_BATCHED, K_KEY_SEGMENT_SUM, \
-    K_EMBED, K_PNA_EDGE_FWD, K_PNA_EDGE_BWD, K_ATTN_FWD, K_ATTN_BWD = range(20)
-K_COUNT = 20
+    K_EMBED, K_PNA_EDGE_FWD, K_PNA_EDGE_BWD, K_ATTN_FWD, K_ATTN_BWD, K_PCSAFT_RHO, K_PCSAFT_VP = range(22)
+K_COUNT = 22
 KERNEL_GROUPS = {K_PNA_AGG_FWD: "pna_aggregate_fwd", K_PNA_AGG_BWD: "pna_aggregate_bwd", K_GEMM_WS: "gemm_weights_stationary",
                  K_GEMM_WGRAD: "weight_gradient", K_GINE_AGG_FWD: "gine_aggregate_fwd", K_GINE_AGG_BWD: "gine_aggregate_bwd",
                  K_EDGE_COMBINE_FWD: "edge_combine_fwd", K_EDGE_COMBINE_BWD: "edge_combine_bwd", K_BN_FWD: "batchnorm_fwd",
                  K_BN_BWD: "batchnorm_bwd", K_GEMM_TILED: "gemm_tiled", K_GEMM_SMALL: "gemm_small",
                  K_GEMM_WGRAD_BATCHED: "weight_gradient_batched", K_KEY_SEGMENT_SUM: "key_segment_sum", K_EMBED: "embedding",
                  K_PNA_EDGE_FWD: "pna_edge_fused_fwd", K_PNA_EDGE_BWD: "pna_edge_fused_bwd",
-                 K_ATTN_FWD: "transformer_attn_fwd", K_ATTN_BWD: "transformer_attn_bwd"}
+                 K_ATTN_FWD: "transformer_attn_fwd", K_ATTN_BWD: "transformer_attn_bwd",
+                 K_PCSAFT_RHO: "pcsaft_density", K_PCSAFT_VP: "pcsaft_vapor_pressure"}
 
 
 class GnxError(RuntimeError):
@@ -157,6 +158,8 @@ SIGNATURES = {
     "gnx_transformer_attn_bwd": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32,
                                         _i32, _i32, _f32, C.c_uint64, C.c_uint64, _vp, _vp, _vp]),
     "gnx_transformer_attn_dle": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp]),
+    "gnx_pcsaft_density": (_i32, [_vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp]),
+    "gnx_pcsaft_vapor_pressure": (_i32, [_vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp]),
     "gnx_segment_pool_fwd": (_i32, [_vp, _vp, _vp, _i64, _i32, _i32, _vp]),
     "gnx_segment_pool_bwd": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp]),
     "gnx_batchnorm_workspace_bytes": (_sz, [_i64, _i32]),

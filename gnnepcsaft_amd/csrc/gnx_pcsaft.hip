@@ -1,0 +1,411 @@
+// Pure-component PC-SAFT liquid density and vapour pressure in fp64 (ref: train/utils.py:238-300 rho_batch / vp_batch
+// -> pcsaft/pcsaft_feos.py:349-436 pure_den_feos / pure_vp_feos; [3P] feos 0.8 State(..., density_initialization=
+// "liquid") and PhaseEquilibrium.pure).
+//
+// Model.  Reduced residual Helmholtz energy per molecule a(T, rho), rho in 1/angstrom^3, of a parameter
+// row [m, sigma, eps/k, kappa_ab, eps_ab/k, mu, na, nb, mw]:
+//   hard chain   m (4 eta - 3 eta^2) / (1 - eta)^2 - (m - 1) ln g_hs      (BMCSL for one component = Carnahan-Starling)
+//   dispersion   -2 pi rho I1 m^2 (eps/kT) sigma^3 - pi rho m C1 I2 m^2 (eps/kT)^2 sigma^3      (Gross & Sadowski 2001)
+//   association  na (ln XA - XA/2 + 1/2) + nb (ln XB - XB/2 + 1/2), A-B bonding only, XA/XB in closed form (Wertheim)
+//   dipole       A2 / (1 - A3 / A2)                                                               (Gross & Vrabec 2006)
+// with d = sigma (1 - 0.12 exp(-3 eps/kT)) and eta = (pi/6) rho m d^3.
+//
+// a is written once, as a template over its number type, and evaluated on a second-order forward dual in rho
+// (value, d/drho, d2/drho2): Z = 1 + rho a', p/kT = rho Z, d(p/kT)/drho = 1 + 2 rho a' + rho^2 a''.  Both solvers work
+// in the packing fraction eta (rho = eta / (pi/6 m d^3)) and in the reduced pressure p~ = p / kT (1/angstrom^3).
+//
+// One lane per state point; a lane loads its parameter row through owner[i].  Every loop has a fixed trip cap; a point
+// that runs into one reports a status != 0 and the value 0.0.  No atomics: same input, same bits.
+#include "gnx_common.hpp"
+#include "gnx_pcsaft_consts.hpp"
+
+#include <cmath>
+
+namespace {
+
+using namespace gnx_pcsaft;
+
+constexpr double kPi = 3.14159265358979323846;
+constexpr int kScanDensity = 512;   // downward eta scan of the density solve (step kEtaMax / 512)
+constexpr int kScanLog = 64;        // spinodal scan: 64 log-spaced points in [1e-10, 1e-2] ...
+constexpr int kScanLin = 512;       // ... then 512 linear points in (1e-2, kEtaMax]
+constexpr int kRootIters = 200;     // safeguarded Newton of one density at a given pressure
+constexpr int kBisectIters = 60;    // spinodal refinement
+constexpr int kSuccIters = 100;     // successive substitution p <- p phi_L / phi_V
+constexpr int kNewtonIters = 50;    // Newton on (eta_L, eta_V)
+constexpr double kRootTol = 1e-14;  // relative step / bracket width that ends a root solve
+// relative Newton step that ends the VLE solve: quadratic convergence leaves an error far below it after that step,
+// while a tighter bound can sit under the rounding noise of g_L for long chains (m ~ 10: |dg| ~ 1e-13)
+constexpr double kVleTol = 1e-10;
+
+enum : int32_t { ST_OK = 0, ST_NO_CONV = 1, ST_SUPERCRITICAL = 2, ST_BAD_INPUT = 3 };
+
+// ---- second-order forward dual --------------------------------------------------------------------------------------
+struct D2 {
+  double v, d, dd;
+};
+__device__ __forceinline__ D2 operator+(D2 a, D2 b) { return {a.v + b.v, a.d + b.d, a.dd + b.dd}; }
+__device__ __forceinline__ D2 operator-(D2 a, D2 b) { return {a.v - b.v, a.d - b.d, a.dd - b.dd}; }
+__device__ __forceinline__ D2 operator-(D2 a) { return {-a.v, -a.d, -a.dd}; }
+__device__ __forceinline__ D2 operator+(D2 a, double b) { return {a.v + b, a.d, a.dd}; }
+__device__ __forceinline__ D2 operator+(double b, D2 a) { return {a.v + b, a.d, a.dd}; }
+__device__ __forceinline__ D2 operator-(D2 a, double b) { return {a.v - b, a.d, a.dd}; }
+__device__ __forceinline__ D2 operator-(double b, D2 a) { return {b - a.v, -a.d, -a.dd}; }
+__device__ __forceinline__ D2 operator*(D2 a, double b) { return {a.v * b, a.d * b, a.dd * b}; }
+__device__ __forceinline__ D2 operator*(double b, D2 a) { return {a.v * b, a.d * b, a.dd * b}; }
+__device__ __forceinline__ D2 operator*(D2 a, D2 b) {
+  return {a.v * b.v, a.d * b.v + a.v * b.d, a.dd * b.v + 2.0 * a.d * b.d + a.v * b.dd};
+}
+__device__ __forceinline__ D2 operator/(D2 a, D2 b) {
+  const double q = a.v / b.v;
+  const double qd = (a.d - q * b.d) / b.v;
+  return {q, qd, (a.dd - 2.0 * qd * b.d - q * b.dd) / b.v};
+}
+__device__ __forceinline__ D2 operator/(D2 a, double b) { return {a.v / b, a.d / b, a.dd / b}; }
+__device__ __forceinline__ D2 operator/(double a, D2 b) { return D2{a, 0.0, 0.0} / b; }
+__device__ __forceinline__ D2 exp(D2 a) {
+  const double e = ::exp(a.v);
+  return {e, e * a.d, e * (a.dd + a.d * a.d)};
+}
+__device__ __forceinline__ D2 log(D2 a) { return {::log(a.v), a.d / a.v, a.dd / a.v - (a.d * a.d) / (a.v * a.v)}; }
+__device__ __forceinline__ D2 sqrt(D2 a) {
+  const double s = ::sqrt(a.v);
+  return {s, a.d / (2.0 * s), a.dd / (2.0 * s) - (a.d * a.d) / (4.0 * s * a.v)};
+}
+__device__ __forceinline__ double value_of(D2 a) { return a.v; }
+__device__ __forceinline__ double value_of(double a) { return a; }
+__device__ __forceinline__ double exp(double a) { return ::exp(a); }
+__device__ __forceinline__ double log(double a) { return ::log(a); }
+__device__ __forceinline__ double sqrt(double a) { return ::sqrt(a); }
+
+// positive root of q X^2 + u X - 1 = 0 (q > 0), the mass-action law of one site type: X_A with u = 1 + (nb - na) x,
+// q = na x.  Written so that neither branch cancels: 2 / (u + sqrt(u^2 + 4q)) for u >= 0, (sqrt(u^2 + 4q) - u) / 2q
+// for u < 0.
+template <typename R>
+__device__ __forceinline__ R site_fraction(R u, R q) {
+  const R s = sqrt(u * u + 4.0 * q);
+  if (value_of(u) >= 0.0) return 2.0 / (u + s);
+  return (s - u) / (2.0 * q);
+}
+
+// ---- one component at one temperature: everything that does not depend on rho --------------------------------------
+struct Pure {
+  double m, eps_t, sig3, na, nb;
+  double eta_per_rho;           // pi/6 m d^3
+  double ai[7], bi[7];          // a_i(m), b_i(m) of the dispersion integrals
+  double m2es3, m2e2s3;         // m^2 (eps/kT) sigma^3, m^2 (eps/kT)^2 sigma^3
+  bool assoc, polar;
+  double delta0;                // sigma^3 kappa_ab (exp(eps_ab/kT) - 1): Delta = delta0 g_hs
+  double j2[5], j3[5];          // a_n + b_n eps/kT and c_n of the dipole integrals (m capped at 2)
+  double a2c, a3c;              // A2 = a2c rho J2, A3 = a3c rho^2 J3
+  double kT_pa;                 // p [Pa] = p~ [1/angstrom^3] * kT_pa
+
+  __device__ bool init(const double* __restrict__ row, double T) {
+    m = row[0];
+    const double sigma = row[1], eps = row[2], kab = row[3], eab = row[4], mu = row[5];
+    na = row[6];
+    nb = row[7];
+    if (!(T > 0.0) || !(m > 0.0) || !(sigma > 0.0) || !(eps > 0.0) || !(kab >= 0.0) || !(eab >= 0.0) ||
+        !(mu >= 0.0) || !(na >= 0.0) || !(nb >= 0.0) || !isfinite(T) || !isfinite(m) || !isfinite(sigma) ||
+        !isfinite(eps) || !isfinite(kab) || !isfinite(eab) || !isfinite(mu) || !isfinite(na) || !isfinite(nb))
+      return false;
+    eps_t = eps / T;
+    const double d = sigma * (1.0 - 0.12 * ::exp(-3.0 * eps_t));
+    sig3 = sigma * sigma * sigma;
+    eta_per_rho = kPi / 6.0 * m * d * d * d;
+    const double f1 = (m - 1.0) / m, f2 = f1 * (m - 2.0) / m;
+    for (int i = 0; i < 7; ++i) {
+      ai[i] = kDispA[0][i] + f1 * kDispA[1][i] + f2 * kDispA[2][i];
+      bi[i] = kDispB[0][i] + f1 * kDispB[1][i] + f2 * kDispB[2][i];
+    }
+    m2es3 = m * m * eps_t * sig3;
+    m2e2s3 = m2es3 * eps_t;
+    assoc = na * nb > 0.0 && kab > 0.0;
+    delta0 = sig3 * kab * ::expm1(eab / T);
+    polar = mu > 0.0;
+    const double mc = m < 2.0 ? m : 2.0;
+    const double g1 = (mc - 1.0) / mc, g2 = g1 * (mc - 2.0) / mc;
+    for (int n = 0; n < 5; ++n) {
+      j2[n] = kDipA[0][n] + g1 * kDipA[1][n] + g2 * kDipA[2][n] +
+              (kDipB[0][n] + g1 * kDipB[1][n] + g2 * kDipB[2][n]) * eps_t;
+      j3[n] = kDipC[0][n] + g1 * kDipC[1][n] + g2 * kDipC[2][n];
+    }
+    const double mu2 = mu * mu / (m * eps * sig3) * kDipoleFactor;  // mu*^2
+    a2c = -kPi * eps_t * eps_t * sig3 * mu2 * mu2;
+    a3c = -4.0 / 3.0 * kPi * kPi * eps_t * eps_t * eps_t * sig3 * sig3 * mu2 * mu2 * mu2;
+    kT_pa = kBoltzmann * T * 1e30;
+    return true;
+  }
+
+  // reduced residual Helmholtz energy per molecule at number density rho [1/angstrom^3]
+  template <typename R>
+  __device__ R a_res(R rho) const {
+    const R eta = rho * eta_per_rho;
+    const R om = 1.0 - eta;
+    const R om2 = om * om;
+    const R ghs = 1.0 / om + 1.5 * eta / om2 + 0.5 * eta * eta / (om2 * om);
+    const R ahc = m * (eta * (4.0 - 3.0 * eta)) / om2 - (m - 1.0) * log(ghs);
+    R i1 = ai[6] + 0.0 * eta, i2 = bi[6] + 0.0 * eta;
+    for (int i = 5; i >= 0; --i) {
+      i1 = i1 * eta + ai[i];
+      i2 = i2 * eta + bi[i];
+    }
+    const R eta2 = eta * eta;
+    const R tw = om * (2.0 - eta);
+    const R c1 = 1.0 / (1.0 + m * (8.0 * eta - 2.0 * eta2) / (om2 * om2) +
+                        (1.0 - m) * (20.0 * eta - 27.0 * eta2 + 12.0 * eta2 * eta - 2.0 * eta2 * eta2) / (tw * tw));
+    R a = ahc - 2.0 * kPi * m2es3 * (rho * i1) - kPi * m * m2e2s3 * (rho * c1 * i2);
+    if (assoc) {
+      const R x = rho * delta0 * ghs;  // rho Delta
+      const R xa = site_fraction(1.0 + (nb - na) * x, na * x);
+      const R xb = site_fraction(1.0 + (na - nb) * x, nb * x);
+      a = a + na * (log(xa) - 0.5 * xa + 0.5) + nb * (log(xb) - 0.5 * xb + 0.5);
+    }
+    if (polar) {
+      R jj2 = j2[4] + 0.0 * eta, jj3 = j3[4] + 0.0 * eta;
+      for (int n = 3; n >= 0; --n) {
+        jj2 = jj2 * eta + j2[n];
+        jj3 = jj3 * eta + j3[n];
+      }
+      const R A2 = a2c * rho * jj2;
+      const R A3 = a3c * rho * rho * jj3;
+      a = a + A2 / (1.0 - A3 / A2);
+    }
+    return a;
+  }
+
+  struct Eval {
+    double p;      // p / kT [1/angstrom^3]
+    double dp;     // d(p/kT)/d eta
+    double g;      // mu / kT up to a function of T: ln rho + a + Z - 1 (= ln phi + ln p~)
+  };
+  __device__ Eval eval(double eta) const {
+    const double rho = eta / eta_per_rho;
+    const D2 a = a_res(D2{rho, 1.0, 0.0});
+    const double z = 1.0 + rho * a.d;
+    Eval e;
+    e.p = rho * z;
+    e.dp = (1.0 + 2.0 * rho * a.d + rho * rho * a.dd) / eta_per_rho;
+    e.g = ::log(rho) + a.v + z - 1.0;
+    return e;
+  }
+
+  // root of p~(eta) = pt in [lo, hi] with p~(lo) <= pt < p~(hi), by Newton from x safeguarded by bisection
+  __device__ bool root(double pt, double lo, double hi, double x, double& out) const {
+    if (!(x > lo && x < hi)) x = 0.5 * (lo + hi);
+    for (int it = 0; it < kRootIters; ++it) {
+      const Eval e = eval(x);
+      const double f = e.p - pt;
+      if (!isfinite(f)) return false;
+      if (f > 0.0)
+        hi = x;
+      else
+        lo = x;
+      if (f == 0.0) {
+        out = x;
+        return true;
+      }
+      double xn = x - f / e.dp;
+      if (!(e.dp > 0.0) || !(xn > lo && xn < hi)) xn = 0.5 * (lo + hi);
+      if (::fabs(xn - x) <= kRootTol * x || hi - lo <= kRootTol * hi) {
+        out = xn;
+        return true;
+      }
+      x = xn;
+    }
+    return false;
+  }
+};
+
+__device__ __forceinline__ bool load_row(const double* __restrict__ params, int64_t B, const int64_t* __restrict__ owner,
+                                         int64_t i, double T, Pure& c) {
+  const int64_t o = owner[i];
+  if (o < 0 || o >= B) return false;
+  double row[9];
+  for (int k = 0; k < 9; ++k) row[k] = params[o * 9 + k];
+  return c.init(row, T);
+}
+
+// density at (T, P): the highest-density root of p(eta) = P with dp/deta > 0
+__global__ void __launch_bounds__(256) k_pcsaft_density(const double* __restrict__ params, int64_t B,
+                                                        const int64_t* __restrict__ owner, const double* __restrict__ T,
+                                                        const double* __restrict__ P, int64_t n,
+                                                        double* __restrict__ rho, int32_t* __restrict__ status) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  Pure c;
+  const double t = T[i], p = P[i];
+  int32_t st = ST_BAD_INPUT;
+  double out = 0.0;
+  if (load_row(params, B, owner, i, t, c) && p > 0.0 && isfinite(p)) {
+    st = ST_NO_CONV;
+    const double pt = p / c.kT_pa;
+    // p~(kEtaMax) > pt, then scan down to the first eta with p~ <= pt: the bracket of the highest crossing
+    double hi = kEtaMax, lo = 0.0;
+    if (c.eval(hi).p - pt > 0.0) {
+      for (int k = kScanDensity - 1; k >= 1; --k) {
+        const double eta = kEtaMax * k / kScanDensity;
+        if (c.eval(eta).p - pt <= 0.0) {
+          lo = eta;
+          break;
+        }
+        hi = eta;
+      }
+      double x;
+      if (c.root(pt, lo, hi, hi, x) && x > 0.0 && c.eval(x).dp > 0.0) {
+        st = ST_OK;
+        out = x / c.eta_per_rho * 1e30 / kAvogadro;
+      }
+    }
+  }
+  rho[i] = st == ST_OK ? out : 0.0;
+  status[i] = st;
+}
+
+__device__ __forceinline__ double spinodal_grid(int k) {
+  return k < kScanLog ? 1e-10 * ::pow(1e8, (double)k / kScanLog)
+                      : 1e-2 + (kEtaMax - 1e-2) * (double)(k - kScanLog + 1) / kScanLin;
+}
+
+// first zero of dp/deta in (a, b] where the sign goes from `from_pos` to its opposite, by bisection
+__device__ double bisect_spinodal(const Pure& c, double a, double b, bool from_pos) {
+  for (int it = 0; it < kBisectIters; ++it) {
+    const double mid = 0.5 * (a + b);
+    if ((c.eval(mid).dp > 0.0) == from_pos)
+      a = mid;
+    else
+      b = mid;
+  }
+  return from_pos ? a : b;  // the end on the stable side
+}
+
+// vapour pressure at T: p_sat with equal p and mu of liquid and vapour
+__global__ void __launch_bounds__(256) k_pcsaft_vapor_pressure(const double* __restrict__ params, int64_t B,
+                                                               const int64_t* __restrict__ owner,
+                                                               const double* __restrict__ T, int64_t n,
+                                                               double* __restrict__ psat, double* __restrict__ rho_l,
+                                                               double* __restrict__ rho_v, int32_t* __restrict__ status) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  Pure c;
+  const double t = T[i];
+  int32_t st = ST_BAD_INPUT;
+  double ps = 0.0, el = 0.0, ev = 0.0;
+  if (load_row(params, B, owner, i, t, c)) {
+    // spinodals: the first eta where dp/deta turns <= 0 (vapour side), then the first where it is > 0 again (liquid)
+    double evs = 0.0, els = 0.0;
+    int kv = -1, kl = -1;
+    const int ngrid = kScanLog + kScanLin;
+    for (int k = 0; k < ngrid; ++k) {
+      const bool pos = c.eval(spinodal_grid(k)).dp > 0.0;
+      if (kv < 0 && !pos && k > 0) {
+        kv = k;
+      } else if (kv >= 0 && pos) {
+        kl = k;
+        break;
+      }
+    }
+    st = ST_SUPERCRITICAL;
+    if (kv > 0 && kl > 0) {
+      st = ST_NO_CONV;
+      evs = bisect_spinodal(c, spinodal_grid(kv - 1), spinodal_grid(kv), true);
+      els = bisect_spinodal(c, spinodal_grid(kl - 1), spinodal_grid(kl), false);
+      const double pvs = c.eval(evs).p, pls = c.eval(els).p;
+      const double plo = pls > 0.0 ? pls : 0.0;
+      bool ok = pvs > plo && c.eval(kEtaMax).p > pvs;
+      // successive substitution from a pressure between the spinodal pressures
+      double p = plo > 0.0 ? 0.5 * (plo + pvs) : 0.5 * pvs;
+      double xl = kEtaMax, xv = 0.0;
+      for (int it = 0; ok && it < kSuccIters; ++it) {
+        ok = c.root(p, els, kEtaMax, xl, xl) && c.root(p, 0.0, evs, xv > 0.0 ? xv : p * c.eta_per_rho, xv);
+        if (!ok) break;
+        // ln phi_L - ln phi_V at equal pressure = g_L - g_V: the form without ln Z, which is lost to rounding in a
+        // liquid far below its normal boiling point (Z_L ~ 1e-19 next to terms of size 1)
+        const double step = c.eval(xl).g - c.eval(xv).g;
+        if (!isfinite(step)) {
+          ok = false;
+          break;
+        }
+        double pn = p * ::exp(step);
+        if (pn >= pvs) pn = 0.5 * (p + pvs);
+        if (pn <= plo) pn = 0.5 * (p + plo);
+        p = pn;
+        if (::fabs(step) < 1e-8) break;
+      }
+      // Newton on (eta_L, eta_V): p~_L = p~_V and g_L = g_V
+      bool conv = false;
+      if (ok) {
+        ok = c.root(p, els, kEtaMax, xl, xl) && c.root(p, 0.0, evs, xv, xv);
+      }
+      for (int it = 0; ok && it < kNewtonIters; ++it) {
+        const Pure::Eval L = c.eval(xl), V = c.eval(xv);
+        const double rl = xl / c.eta_per_rho, rv = xv / c.eta_per_rho;
+        const double f1 = L.p - V.p, f2 = L.g - V.g;
+        const double j11 = L.dp, j12 = -V.dp, j21 = L.dp / rl, j22 = -V.dp / rv;
+        const double det = j11 * j22 - j12 * j21;
+        if (!isfinite(f1) || !isfinite(f2) || !(det != 0.0) || !isfinite(det)) {
+          ok = false;
+          break;
+        }
+        const double dl = -(j22 * f1 - j12 * f2) / det, dv = -(j11 * f2 - j21 * f1) / det;
+        double s = 1.0;
+        int h = 0;
+        while (h < 30 && !(xl + s * dl > els && xl + s * dl < kEtaMax && xv + s * dv > 0.0 && xv + s * dv < evs)) {
+          s *= 0.5;
+          ++h;
+        }
+        if (h == 30) {
+          ok = false;
+          break;
+        }
+        xl += s * dl;
+        xv += s * dv;
+        if (s == 1.0 && ::fabs(dl) <= kVleTol * xl && ::fabs(dv) <= kVleTol * xv) {
+          conv = true;
+          break;
+        }
+      }
+      if (ok && conv) {
+        const double pv = c.eval(xv).p;
+        if (pv > 0.0 && isfinite(pv)) {
+          st = ST_OK;
+          ps = pv * c.kT_pa;
+          el = xl / c.eta_per_rho * 1e30 / kAvogadro;
+          ev = xv / c.eta_per_rho * 1e30 / kAvogadro;
+        }
+      }
+    }
+  }
+  const bool good = st == ST_OK;
+  psat[i] = good ? ps : 0.0;
+  if (rho_l) rho_l[i] = good ? el : 0.0;
+  if (rho_v) rho_v[i] = good ? ev : 0.0;
+  status[i] = st;
+}
+
+}  // namespace
+
+extern "C" int32_t gnx_pcsaft_density(gnx_handle* h, const double* params, int64_t B, const int64_t* owner,
+                                      const double* T, const double* P, int64_t n, double* rho, int32_t* status) {
+  GNX_CHECK_ARG(h && n >= 0 && B >= 0, "gnx_pcsaft_density: bad argument");
+  if (n == 0) return GNX_OK;
+  GNX_CHECK_ARG(params && owner && T && P && rho && status, "gnx_pcsaft_density: NULL argument");
+  gnx_prof_scope prof(h, GNX_K_PCSAFT_RHO, 36.0 * n, 0.0, 0.0, true);
+  GNX_LAUNCH_TIMED(prof, k_pcsaft_density, dim3((unsigned)gnx_cdiv(n, 256)), dim3(256), 0, h->stream, params, B, owner,
+                   T, P, n, rho, status);
+  GNX_LAUNCH_CHECK();
+  return GNX_OK;
+}
+
+extern "C" int32_t gnx_pcsaft_vapor_pressure(gnx_handle* h, const double* params, int64_t B, const int64_t* owner,
+                                             const double* T, int64_t n, double* psat, double* rho_l, double* rho_v,
+                                             int32_t* status) {
+  GNX_CHECK_ARG(h && n >= 0 && B >= 0, "gnx_pcsaft_vapor_pressure: bad argument");
+  if (n == 0) return GNX_OK;
+  GNX_CHECK_ARG(params && owner && T && psat && status, "gnx_pcsaft_vapor_pressure: NULL argument");
+  gnx_prof_scope prof(h, GNX_K_PCSAFT_VP, 44.0 * n, 0.0, 0.0, true);
+  GNX_LAUNCH_TIMED(prof, k_pcsaft_vapor_pressure, dim3((unsigned)gnx_cdiv(n, 256)), dim3(256), 0, h->stream, params, B,
+                   owner, T, n, psat, rho_l, rho_v, status);
+  GNX_LAUNCH_CHECK();
+  return GNX_OK;
+}

@@ -889,6 +889,55 @@ def transformer_attn_dle(dout: torch.Tensor, qkvs: torch.Tensor, scratch: torch.
     return dLe
 
 
+def _f64_on(t: torch.Tensor, name: str, dev: torch.device) -> torch.Tensor:
+    if t.dtype != torch.float64 or t.device != dev:
+        raise _lib.GnxError(_lib.GNX_E_INVALID, f"{name}: expected float64 on {dev}, got {t.dtype} on {t.device}")
+    return t.contiguous()
+
+
+def _pcsaft_args(params: torch.Tensor, owner: torch.Tensor, T: torch.Tensor, name: str):
+    dev = params.device
+    params = _f64_on(params, f"{name}: params", dev)
+    if params.dim() != 2 or params.size(1) != 9:
+        raise _lib.GnxError(_lib.GNX_E_INVALID, f"{name}: params must be [B, 9], got {tuple(params.shape)}")
+    if owner.dtype != torch.int64 or owner.device != dev or owner.dim() != 1:
+        raise _lib.GnxError(_lib.GNX_E_INVALID, f"{name}: owner must be a 1-D int64 tensor on {dev}")
+    T = _f64_on(T, f"{name}: T", dev)
+    if T.shape != owner.shape:
+        raise _lib.GnxError(_lib.GNX_E_INVALID, f"{name}: T {tuple(T.shape)} and owner {tuple(owner.shape)} differ")
+    return params, owner.contiguous(), T
+
+
+def pcsaft_density(params: torch.Tensor, owner: torch.Tensor, T: torch.Tensor, P: torch.Tensor
+                   ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """PC-SAFT liquid density (gnx_pcsaft_density): params [B, 9] fp64 rows, owner [n] int64, T [n] K, P [n] Pa ->
+    (rho [n] fp64 mol/m^3, status [n] int32); rho is 0.0 where status != 0.  One launch, no host synchronisation."""
+    params, owner, T = _pcsaft_args(params, owner, T, "pcsaft_density")
+    P = _f64_on(P, "pcsaft_density: P", params.device)
+    if P.shape != T.shape:
+        raise _lib.GnxError(_lib.GNX_E_INVALID, f"pcsaft_density: P {tuple(P.shape)} and T {tuple(T.shape)} differ")
+    n, dev = T.numel(), params.device
+    rho = torch.empty(n, dtype=torch.float64, device=dev)
+    status = torch.empty(n, dtype=torch.int32, device=dev)
+    check(_lib.load().gnx_pcsaft_density(handle(dev), params.data_ptr(), params.size(0), owner.data_ptr(),
+                                         T.data_ptr(), P.data_ptr(), n, rho.data_ptr(), status.data_ptr()))
+    return rho, status
+
+
+def pcsaft_vapor_pressure(params: torch.Tensor, owner: torch.Tensor, T: torch.Tensor
+                          ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """PC-SAFT vapour pressure (gnx_pcsaft_vapor_pressure): params [B, 9] fp64, owner [n] int64, T [n] K ->
+    (psat [n] Pa, rho_l [n], rho_v [n] mol/m^3, status [n] int32); all 0.0 where status != 0 (2 = supercritical)."""
+    params, owner, T = _pcsaft_args(params, owner, T, "pcsaft_vapor_pressure")
+    n, dev = T.numel(), params.device
+    out = torch.empty(3, n, dtype=torch.float64, device=dev)
+    status = torch.empty(n, dtype=torch.int32, device=dev)
+    check(_lib.load().gnx_pcsaft_vapor_pressure(handle(dev), params.data_ptr(), params.size(0), owner.data_ptr(),
+                                                T.data_ptr(), n, out[0].data_ptr(), out[1].data_ptr(),
+                                                out[2].data_ptr(), status.data_ptr()))
+    return out[0], out[1], out[2], status
+
+
 _POOL = {"add": _lib.POOL_ADD, "sum": _lib.POOL_ADD, "mean": _lib.POOL_MEAN, "max": _lib.POOL_MAX}
 
 

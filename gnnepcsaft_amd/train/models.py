@@ -52,7 +52,8 @@ class GNNePCSAFTL(LightningModuleLite):
         super().__init__()
         self.save_hyperparameters()
         self.config, self.model = config, GNNePCSAFT(config)
-        # hooks for the CPU PC-SAFT label oracle (feos), which stays outside this package (north star)
+        # PC-SAFT solvers of validation_step (reference train/utils.py:252-300); None = validation off.  The native ones:
+        # self.rho_batch, self.vp_batch = gnnepcsaft_amd.pcsaft.rho_batch, gnnepcsaft_amd.pcsaft.vp_batch
         self.rho_batch = self.vp_batch = None
 
     def forward(self, x: torch.Tensor, edge_index: torch.Tensor, edge_attr: torch.Tensor,
@@ -89,14 +90,14 @@ class GNNePCSAFTL(LightningModuleLite):
 
     def validation_step(self, graphs, batch_idx, dataloader_idx: int = 0):  # pylint: disable=W0613
         """Same contract as the reference (:110-153): mean absolute percentage errors of liquid density and vapour
-        pressure computed from the predicted parameters.  That evaluation needs the CPU PC-SAFT solver (``rho_batch`` /
-        ``vp_batch`` of the reference's train/utils.py:252-300, feos), which is out of this package's scope: assign
-        callables to ``self.rho_batch`` / ``self.vp_batch`` to enable it."""
+        pressure computed from the predicted parameters.  That evaluation needs a PC-SAFT solver with the contract of
+        ``rho_batch`` / ``vp_batch`` of the reference's train/utils.py:252-300 (feos there): assign callables to
+        ``self.rho_batch`` / ``self.vp_batch`` to enable it, e.g. the GPU solver of ``gnnepcsaft_amd.pcsaft``."""
         import numpy as np
 
         if self.rho_batch is None or self.vp_batch is None:
-            raise RuntimeError("validation_step needs the CPU PC-SAFT oracle: set .rho_batch and .vp_batch "
-                               "(reference gnnepcsaft/train/utils.py:252-300); it is out of scope here")
+            raise RuntimeError("validation_step needs PC-SAFT solvers: set .rho_batch and .vp_batch, e.g. to "
+                               "gnnepcsaft_amd.pcsaft.rho_batch / vp_batch (reference gnnepcsaft/train/utils.py:252-300)")
         predicted = self.model.pred_with_bounds(graphs).squeeze().detach()
         signs = torch.tensor([-1.0, 1.0], device=predicted.device)  # labels hold (-log10 kappa_ab, log10 epsilon_ab)
         if self.config["num_para"] == 2:  # the model predicts the association pair, m/sigma/epsilon come as labels

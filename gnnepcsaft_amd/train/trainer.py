@@ -288,7 +288,7 @@ class Trainer:
 
     def _validate(self, model, val_dataloaders) -> None:
         if model.rho_batch is None or model.vp_batch is None:
-            return  # the CPU PC-SAFT oracle is not wired in: nothing to evaluate (see GNNePCSAFTL.validation_step)
+            return  # no PC-SAFT solvers set: nothing to evaluate (see GNNePCSAFTL.validation_step, gnnepcsaft_amd.pcsaft)
         was_training = model.training
         model.eval()
         with torch.no_grad():

@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define GNX_ABI_VERSION 4
+#define GNX_ABI_VERSION 5
 
 enum {
   GNX_OK = 0,
@@ -101,7 +101,9 @@ enum {
   GNX_K_PNA_EDGE_BWD = 17,      /* fused masked input gradient of pre-layer 1 + destination sums + bond-table sums (gnx_pna_edge_bwd) */
   GNX_K_ATTN_FWD = 18,          /* TransformerConv segmented-softmax attention forward (gnx_transformer_attn_fwd) */
   GNX_K_ATTN_BWD = 19,          /* its destination- and source-side backward passes (gnx_transformer_attn_bwd) */
-  GNX_K_COUNT = 20
+  GNX_K_PCSAFT_RHO = 20,        /* PC-SAFT liquid density at (T, P), fp64 (gnx_pcsaft_density) */
+  GNX_K_PCSAFT_VP = 21,         /* PC-SAFT vapour pressure at T, fp64 (gnx_pcsaft_vapor_pressure) */
+  GNX_K_COUNT = 22
 };
 /* start recording a HIP event pair around every launch of the kernels whose id bit is set in kernel_mask
  * (bit k = GNX_K_* id k).  Events go on the handle's stream, i.e. the stream the kernels run on. */
@@ -395,6 +397,22 @@ int32_t gnx_transformer_attn_bwd(gnx_handle* h, const float* dout, const float* 
 int32_t gnx_transformer_attn_dle(gnx_handle* h, const float* dout, const float* qkvs, const float* scratch,
                                  const int32_t* dst, const int32_t* code, const int32_t* code_pos, int64_t E,
                                  int32_t heads, int32_t C, int32_t R, float* dLe);
+
+/* ---- pure-component PC-SAFT (fp64; the exception to "all float tensors are fp32") --------------------------- */
+/* [3P] feos 0.8 PC-SAFT (ref: train/utils.py:238-300 rho_batch / vp_batch -> pcsaft/pcsaft_feos.py:349-436
+ * pure_den_feos / pure_vp_feos).  params [B, 9] fp64 rows [m, sigma (angstrom), eps/k (K), kappa_ab, eps_ab/k (K),
+ * mu (debye), na, nb, mw] (mw unused); point i uses row owner[i] (int64; outside [0, B) -> status 3).  T in K, P in Pa,
+ * densities in mol/m^3.  One lane per point, one launch, no atomics (same input, same bits).  status per point:
+ * 0 = ok, 1 = no root / not converged within the fixed iteration caps, 2 = T at or above the critical temperature
+ * (vapour pressure only), 3 = invalid input (non-finite or non-positive T, P, m, sigma, eps/k; negative others).
+ * Every output of a point with status != 0 is exactly 0.0.  DESIGN.md §4b. */
+/* rho[i] = the highest-density root of P(rho; T[i]) = P[i] with dP/drho > 0 (feos density_initialization="liquid") */
+int32_t gnx_pcsaft_density(gnx_handle* h, const double* params, int64_t B, const int64_t* owner, const double* T,
+                           const double* P, int64_t n, double* rho, int32_t* status);
+/* psat[i], rho_l[i], rho_v[i]: the saturated state at T[i] (equal pressure and chemical potential; feos
+ * PhaseEquilibrium.pure).  rho_l / rho_v may be NULL. */
+int32_t gnx_pcsaft_vapor_pressure(gnx_handle* h, const double* params, int64_t B, const int64_t* owner, const double* T,
+                                  int64_t n, double* psat, double* rho_l, double* rho_v, int32_t* status);
 
 /* ---- contiguous segment reduce: global pool (ref: train/models.py:218-225, 587-595) ------------------------ */
 enum { GNX_POOL_ADD = 0, GNX_POOL_MEAN = 1, GNX_POOL_MAX = 2 };

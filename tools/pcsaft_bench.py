@@ -1,0 +1,97 @@
+"""Times the PC-SAFT kernels of csrc/gnx_pcsaft.hip: 1e3 / 1e5 / 1e6 points per call for the liquid
+density and the vapour pressure, kernel time (events around the launch) and end-to-end ``rho_batch`` / ``vp_batch``
+time (upload, launch, download), next to the CPU oracle (tests/pcsaft_ref.py) timed on a sample of the same points and
+scaled to the call size.  Points: the ThermoML fixture's molecules and states, repeated.
+
+Usage: python tools/pcsaft_bench.py [--sizes 1000,100000,1000000] [--oracle-sample 20] [--out FILE.json]
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+from gnnepcsaft_amd import pcsaft  # noqa: E402
+from tests import pcsaft_ref as R  # noqa: E402
+
+
+def _kernel_ms(fn, reps=3):
+    fn()
+    torch.cuda.synchronize()
+    best = float("inf")
+    for _ in range(reps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        torch.cuda.synchronize()
+        best = min(best, a.elapsed_time(b))
+    return best
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--sizes", default="1000,100000,1000000")
+    ap.add_argument("--oracle-sample", type=int, default=20)
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    mols = json.load(open(os.path.join(ROOT, "tests", "golden", "pcsaft_thermoml.json")))["molecules"]
+    rows = np.array([m["params"] for m in mols])
+    rho_pts = np.array([(i, s[0], s[1]) for i, m in enumerate(mols) for s in m["rho"]])
+    vp_pts = np.array([(i, s[0]) for i, m in enumerate(mols) for s in m["vp"]])
+    dev = torch.device("cuda", torch.cuda.current_device())
+    d_rows = torch.from_numpy(rows).to(dev)
+    # CPU oracle per point, on a sample
+    t0 = time.perf_counter()
+    for i, T, P in rho_pts[:args.oracle_sample]:
+        R.density(rows[int(i)], T, P)
+    oracle_rho = (time.perf_counter() - t0) / args.oracle_sample
+    t0 = time.perf_counter()
+    for i, T in vp_pts[:args.oracle_sample]:
+        R.vle(rows[int(i)], T)
+    oracle_vp = (time.perf_counter() - t0) / args.oracle_sample
+    res = []
+    for n in [int(s) for s in args.sizes.split(",")]:
+        pr = rho_pts[np.arange(n) % len(rho_pts)]
+        pv = vp_pts[np.arange(n) % len(vp_pts)]
+        o_r = torch.from_numpy(pr[:, 0].astype(np.int64)).to(dev)
+        T_r, P_r = torch.from_numpy(pr[:, 1].copy()).to(dev), torch.from_numpy(pr[:, 2].copy()).to(dev)
+        o_v = torch.from_numpy(pv[:, 0].astype(np.int64)).to(dev)
+        T_v = torch.from_numpy(pv[:, 1].copy()).to(dev)
+        k_rho = _kernel_ms(lambda: pcsaft.density(d_rows, T_r, P_r, o_r))
+        k_vp = _kernel_ms(lambda: pcsaft.vapor_pressure(d_rows, T_v, o_v))
+        # end to end through the reference-shaped call: one table per molecule
+        params = rows.tolist()
+        tab_r = [np.zeros((0, 5))] * len(rows)
+        tab_v = [np.zeros((0, 5))] * len(rows)
+        for i in range(len(rows)):
+            sel = pr[pr[:, 0] == i]
+            tab_r[i] = np.column_stack([sel[:, 1], sel[:, 2], np.ones(len(sel)), np.ones(len(sel)), np.ones(len(sel))])
+            sel = pv[pv[:, 0] == i]
+            tab_v[i] = np.column_stack([sel[:, 1], np.ones(len(sel)), np.ones(len(sel)), 3 * np.ones(len(sel)),
+                                        np.ones(len(sel))])
+        e2e = {}
+        for name, fn, tab in (("rho_batch", pcsaft.rho_batch, tab_r), ("vp_batch", pcsaft.vp_batch, tab_v)):
+            fn(params, tab)
+            t0 = time.perf_counter()
+            fn(params, tab)
+            e2e[name] = (time.perf_counter() - t0) * 1e3
+        rec = dict(points=n, density_kernel_ms=k_rho, vp_kernel_ms=k_vp, rho_batch_ms=e2e["rho_batch"],
+                   vp_batch_ms=e2e["vp_batch"], oracle_density_ms_est=oracle_rho * n * 1e3,
+                   oracle_vp_ms_est=oracle_vp * n * 1e3)
+        print(json.dumps(rec))
+        res.append(rec)
+    if args.out:
+        with open(args.out, "w") as fh:
+            json.dump(dict(device=torch.cuda.get_device_name(dev), oracle_sample=args.oracle_sample, results=res), fh,
+                      indent=1)
+
+
+if __name__ == "__main__":
+    main()
