@@ -125,6 +125,19 @@ struct gnx_prof_scope {
 
 static inline int64_t gnx_cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
+// Raises KERNEL's dynamic-LDS limit to `bytes` on the first call for that kernel (later calls do nothing); launches of
+// KERNEL may then ask for up to that much dynamic LDS.
+template <auto KERNEL>
+static inline hipError_t gnx_raise_lds_limit(int bytes) {
+  static bool done = false;
+  if (!done) {
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(KERNEL), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    if (e != hipSuccess) return e;
+    done = true;
+  }
+  return hipSuccess;
+}
+
 // reads + clears the sticky range flag (synchronises the stream)
 int32_t gnx_read_flag(gnx_handle* h, int* value);
 

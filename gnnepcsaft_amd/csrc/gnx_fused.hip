@@ -469,12 +469,7 @@ extern "C" int32_t gnx_pna_edge_fwd(gnx_handle* h, const float* P, const float* 
 #ifdef EF_STAMP
   g.stamps = ef_stamp_buf;
 #endif
-  static bool attr_set = false;
-  if (!attr_set) {
-    GNX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_pna_edge_fwd), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)(160 * 1024)));
-    attr_set = true;
-  }
+  GNX_HIP(gnx_raise_lds_limit<&k_pna_edge_fwd>(160 * 1024));
   const double H = (double)T * F;
   // own algorithmic bytes: P and Q rows once (8NH), indices + CSR (16E + 4N), A (16NH), h1 / m if kept (4EH each)
   const double bytes = 24.0 * N * H + 16.0 * E + 4.0 * N + 4.0 * E * H * ((h1 ? 1 : 0) + (m ? 1 : 0));
@@ -830,12 +825,7 @@ extern "C" int32_t gnx_pna_edge_bwd(gnx_handle* h, const float* ge, const float*
   g.dP = dP;
   g.dTe = dTe;
   g.flag = h->d_flag;
-  static bool attr_set = false;
-  if (!attr_set) {
-    GNX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_pna_edge_bwd), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)(160 * 1024)));
-    attr_set = true;
-  }
+  GNX_HIP(gnx_raise_lds_limit<&k_pna_edge_bwd>(160 * 1024));
   const double Hd = (double)T * F;
   // ge and h1 read once, gh1 and dP written once, codes + CSR
   const double bytes = 12.0 * E * Hd + 4.0 * N * Hd + 4.0 * E + 4.0 * N;

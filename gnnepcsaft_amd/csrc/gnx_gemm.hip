@@ -1,12 +1,12 @@
 // Dense feature x weight contractions on the fp32 matrix cores (v_mfma_f32_32x32x2_f32: exact fp32, 64 FLOP/clk/SIMD).
 //
-// Shapes on this path are tall-skinny: M = #edges or #nodes (1e5..1e6), N = 32..512, K = 32..13*F.  Three kernels:
+// Shapes on this path are tall-skinny: M = #edges or #nodes (1e5..1e6), N = 32..512, K = 32..13*F.  The base kernels:
 //   k_gemm       tiled 128 x 128 x 32, multi-segment (K-concatenated operands with per-row scale), optional row
 //                gather/scatter over degree-class tiles with per-class weights.
 //   k_gemm_ws    weights-stationary persistent kernel for ONE segment with K, N <= 128 (the most frequent shape):
 //                the weight image stays in LDS for the workgroup's lifetime, 64-row A tiles stream through a double
 //                buffer, one barrier per tile.
-//   k_gemm_wgrad dW += dC^T (rs * A): contraction over the rows, split over M, fp32 atomics.
+// Their split-operand forms and the small / mid-size products follow; the weight gradients are in gnx_wgrad.hip.
 //
 // Lesson baked into the structure (measured, tools/gemm_diag.py + the ISA): any runtime-conditional global load in the
 // epilogue ("if (mask) v *= mask[...]", "if (accumulate) v += C[...]") makes hipcc put `s_waitcnt vmcnt(0)` in front of
@@ -22,19 +22,25 @@
 //        the 16 lanes of every ds_read_b128 group hit 16 distinct 16-byte slots (MI355X_MICROARCH.md, LDS table).
 //   "k-row" image  T[k][col]  (B when the weight is [k][n], i.e. NN; both operands of the weight gradient):
 //        row stride 128 floats, read with ds_read_b32 (32 consecutive columns per half-wave: conflict-free).
-#include "gnx_common.hpp"
+#include "gnx_split.hpp"
 
 #include <cstdlib>
 #include <type_traits>
 
-#define BM 128
-#define BN 128
-#define BK 32
-#define LDK 36    // row stride of the row-k image
-#define LDN 128   // row stride of the k-row image
 #define MAX_SEGS 4
 
 enum { EPI_PLAIN = 0, EPI_ACCUM = 1, EPI_MASK = 2 };
+
+// Calls f(B_TRANS, EPI) with the run-time (b_trans, epi) pair turned into compile-time constants (std::integral_constant).
+template <typename F>
+static auto epi_dispatch(bool bt, int epi, F&& f) {
+  auto with_bt = [&](auto BT) {
+    if (epi == EPI_MASK) return f(BT, std::integral_constant<int, EPI_MASK>{});
+    if (epi == EPI_ACCUM) return f(BT, std::integral_constant<int, EPI_ACCUM>{});
+    return f(BT, std::integral_constant<int, EPI_PLAIN>{});
+  };
+  return bt ? with_bt(std::true_type{}) : with_bt(std::false_type{});
+}
 
 struct seg_dev {
   const float* a;
@@ -71,20 +77,6 @@ struct gemm_args {
   int steps;           // K-tiles per output tile
 };
 
-__device__ __forceinline__ f32x4 ld4(const float* p, bool vec, int valid) {
-  // valid = number of in-range elements (0..4) starting at p
-  f32x4 v = {0.f, 0.f, 0.f, 0.f};
-  if (valid >= 4 && vec) {
-    v = *reinterpret_cast<const f32x4*>(p);
-  } else {
-    if (valid > 0) v.x = p[0];
-    if (valid > 1) v.y = p[1];
-    if (valid > 2) v.z = p[2];
-    if (valid > 3) v.w = p[3];
-  }
-  return v;
-}
-
 // Epilogue of one 32x32 accumulator tile (C/D map: col = lane&31, row = (r&3) + 8*(r>>2) + 4*(lane>>5)).
 // rows[r] = global row of accumulator register r (-1 = padding); every lane of a half-wave shares it.
 template <int EPI>
@@ -111,13 +103,6 @@ __device__ __forceinline__ void epilogue_tile(const f32x16& acc, const int (&row
     if (col_ok && rows[r] >= 0) C[(int64_t)rows[r] * ldc + gc] = v;
   }
 }
-
-// Row scale of segments that have none (pointer-select, no branch).  A __device__ (global address space) variable on
-// purpose: selecting between a kernel-argument pointer and a __constant__ address yields a GENERIC pointer, i.e. a
-// flat_load, and one outstanding flat load turns every counted s_waitcnt vmcnt(N) of the loop into vmcnt(0).
-__device__ float c_one = 1.0f;
-__device__ float c_zero = 0.0f;
-__device__ __attribute__((aligned(16))) float c_zero4[4] = {0.f, 0.f, 0.f, 0.f};
 
 // VEC = every operand is 16-B aligned with leading dimensions / k / class strides multiples of 4 (always true for the
 // model's shapes): loads are unconditional float4 from clamped addresses + a select, so all 8 loads of a K-tile are in
@@ -335,8 +320,6 @@ __global__ void __launch_bounds__(256, 2) k_gemm(gemm_args g) {
   }
 }
 
-static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 // ---------------------------------------------------------------------------------------------------------------
 // Weights-stationary persistent GEMM: ONE segment, K <= 128, N <= 128, M = #nodes or #edges.
 //   LDS: B image [128][132] (NT) or [128][128] (NN) + 2 x A image [64][132]  = 135 KB (dynamic), 1 workgroup / CU.
@@ -511,13 +494,8 @@ __global__ void __launch_bounds__(512, 1) k_gemm_ws(ws_args g) {
 
 template <bool BT, int EPI>
 static hipError_t ws_launch_one(gnx_handle* h, const ws_args& g, int grid, size_t lds_bytes) {
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gemm_ws<BT, EPI>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)(160 * 1024));
-    if (e != hipSuccess) return e;
-    attr_set = true;
-  }
+  const hipError_t e = gnx_raise_lds_limit<&k_gemm_ws<BT, EPI>>(160 * 1024);
+  if (e != hipSuccess) return e;
   hipLaunchKernelGGL((k_gemm_ws<BT, EPI>), dim3(grid), dim3(512), lds_bytes, h->stream, g);
   return hipGetLastError();
 }
@@ -557,8 +535,6 @@ static hipError_t ws_launch_one(gnx_handle* h, const ws_args& g, int grid, size_
 //     itself, not this kernel's structure, sets the per-tile time; what would remove work is a producer that writes the
 //     three bf16 images instead of fp32 (no split, half the staging LDS traffic in every consumer).
 // ---------------------------------------------------------------------------------------------------------------
-#include "gnx_split.hpp"
-
 //
 // Round 3, measured and rejected: the split of tile t + G issued BETWEEN the MFMA slabs of tile t (two register stages of
 // loads, the k_gemm3p scheme; bit-identical): 27.4 vs 27.2 us at 81 920 rows, 42.3 vs 43.6 at 163 840, +1.5 us at 8 192
@@ -826,9 +802,6 @@ __global__ void __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) k_gemm_ws3(ws_args g
 // Per 16-deep slab a wave (64 x 64 outputs) reads 12 fragments and issues 24 bf16 MFMAs (fp32: 64 MFMAs, 2x the time
 // each): 6/16 of the matrix-core time of k_gemm.
 // ---------------------------------------------------------------------------------------------------------------
-#define G3_LDB 80                   // bytes per image row
-#define G3_PIECE (128 * G3_LDB)     // 10240 B: one bf16 image of a 128 x 32 K-tile
-#define G3_OP (3 * G3_PIECE)        // the three images of one operand
 
 // Weight images for k_gemm3: every segment's B (either layout, any class) is split ONCE per call into three bf16
 // images, zero padded (n to 128, every segment's k to 32, segments concatenated) and stored TILE-MAJOR
@@ -1094,14 +1067,7 @@ __global__ void __launch_bounds__(256, 2) k_gemm3(gemm_args g) {
 #pragma unroll
       for (int mi = 0; mi < 2; ++mi)
 #pragma unroll
-        for (int ni = 0; ni < 2; ++ni) {
-          acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[mi][0], b[ni][2], acc[mi][ni], 0, 0, 0);
-          acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[mi][2], b[ni][0], acc[mi][ni], 0, 0, 0);
-          acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[mi][1], b[ni][1], acc[mi][ni], 0, 0, 0);
-          acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[mi][0], b[ni][1], acc[mi][ni], 0, 0, 0);
-          acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[mi][1], b[ni][0], acc[mi][ni], 0, 0, 0);
-          acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[mi][0], b[ni][0], acc[mi][ni], 0, 0, 0);
-        }
+        for (int ni = 0; ni < 2; ++ni) mfma_3x3(acc[mi][ni], a[mi], b[ni]);
     }
   };
 
@@ -1416,15 +1382,6 @@ __global__ void __launch_bounds__(256, 2) k_gemm3p(gemm_args g) {
 #pragma unroll
     for (int mi = 0; mi < MI; ++mi) read_a1(A3, sl, mi, a[mi]);
   };
-  auto mfma_group = [&](f32x16& c, const bf16x8 (&a)[3], const bf16x8 (&b)[3]) {
-    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[2], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[2], b[0], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1], b[1], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[1], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1], b[0], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[0], c, 0, 0, 0);
-  };
-
   float bv;
   auto fetch_bias = [&](int nn0) {
     const int gc = nn0 + wave * 32 + li;
@@ -1460,13 +1417,13 @@ __global__ void __launch_bounds__(256, 2) k_gemm3p(gemm_args g) {
     read_a(Ac, 0, af);
 #pragma unroll
     for (int mi = 0; mi < MI; ++mi) {
-      mfma_group(acc[mi], af[mi], bfr[0]);
+      mfma_3x3(acc[mi], af[mi], bfr[0]);
       read_a1(Ac, 1, mi, af[mi]);
     }
     load_b(0);
     store_a(PC, As);
 #pragma unroll
-    for (int mi = 0; mi < MI; ++mi) mfma_group(acc[mi], af[mi], bfr[1]);
+    for (int mi = 0; mi < MI; ++mi) mfma_3x3(acc[mi], af[mi], bfr[1]);
     load_b(1);
     b_step();
     load_a(PC);  // A K-tile j + 3 (register stage P was stored just above)
@@ -1697,17 +1654,8 @@ __global__ void __launch_bounds__(256, 3) k_gemm_as3(gemm_args g) {
       const int kt = ks >> 1, sl = ks & 1;
       read_a((ks + 1) & 1, afrag, (ks + 1) & 7);
       __builtin_amdgcn_sched_barrier(0);
-      const bf16x8(&b)[3] = bq[kt & 1][sl];
 #pragma unroll
-      for (int mi = 0; mi < 2; ++mi) {
-        const bf16x8(&a)[3] = af[ks & 1][mi];
-        acc[mi] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[2], acc[mi], 0, 0, 0);
-        acc[mi] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[2], b[0], acc[mi], 0, 0, 0);
-        acc[mi] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1], b[1], acc[mi], 0, 0, 0);
-        acc[mi] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[1], acc[mi], 0, 0, 0);
-        acc[mi] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1], b[0], acc[mi], 0, 0, 0);
-        acc[mi] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[0], acc[mi], 0, 0, 0);
-      }
+      for (int mi = 0; mi < 2; ++mi) mfma_3x3(acc[mi], af[ks & 1][mi], bq[kt & 1][sl]);
       load_b(kt & 1, sl, nt * 4 + kt + 2);
       __builtin_amdgcn_sched_barrier(0);
     }
@@ -1755,48 +1703,30 @@ __global__ void __launch_bounds__(256, 3) k_gemm_as3(gemm_args g) {
 #endif
 }
 
-template <int EPI>
-static hipError_t as3_launch_one(gnx_handle* h, const gemm_args& g, unsigned grid) {
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gemm_as3<EPI>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)AS_LDS);
-    if (e != hipSuccess) return e;
-    attr_set = true;
-  }
-  hipLaunchKernelGGL((k_gemm_as3<EPI>), dim3(grid), dim3(256), AS_LDS, h->stream, g);
-  return hipSuccess;
-}
-
 template <bool BT, int EPI, bool FAST, int NW>
 static hipError_t ws3_launch_fast(gnx_handle* h, const ws_args& g, int grid) {
   // LDS: two stages of a TM-row tile, and at least the 64 KB the NN weight staging image needs
   constexpr size_t lds = (NW == 8) ? (size_t)(2 * W3_BUF) : (size_t)(64 * 1024);
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gemm_ws3<BT, EPI, FAST, NW>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)(NW == 8 ? 160 * 1024 : 64 * 1024));
-    if (e != hipSuccess) return e;
-    attr_set = true;
-  }
+  const hipError_t e = gnx_raise_lds_limit<&k_gemm_ws3<BT, EPI, FAST, NW>>(NW == 8 ? 160 * 1024 : 64 * 1024);
+  if (e != hipSuccess) return e;
   hipLaunchKernelGGL((k_gemm_ws3<BT, EPI, FAST, NW>), dim3(grid), dim3(64 * NW), lds, h->stream, g);
   return hipGetLastError();
 }
 
 template <bool BT, int EPI>
 static hipError_t ws3_launch_one(gnx_handle* h, const ws_args& g, int grid) {
-  // the predicate-free kernel: all 128 columns, 16-byte stores (and mask loads), no read-modify-write of C
-  const bool fast = h->opt[GNX_OPT_GEMM_WS_FAST] != 0 && EPI != EPI_ACCUM && g.N == 128 && aligned16(g.C) && g.ldc % 4 == 0 &&
-                    (g.mask == nullptr || (aligned16(g.mask) && g.ldmask % 4 == 0));
-  if (EPI != EPI_ACCUM && fast) {
-    if (h->opt[GNX_OPT_GEMM_WS_FAST] == 2) {  // two 4-wave workgroups per CU on 32-row tiles
+  if constexpr (EPI != EPI_ACCUM) {
+    // the predicate-free kernel: all 128 columns, 16-byte stores (and mask loads), no read-modify-write of C
+    const bool fast = h->opt[GNX_OPT_GEMM_WS_FAST] != 0 && g.N == 128 && aligned16(g.C) && g.ldc % 4 == 0 &&
+                      (g.mask == nullptr || (aligned16(g.mask) && g.ldmask % 4 == 0));
+    if (fast && h->opt[GNX_OPT_GEMM_WS_FAST] == 2) {  // two 4-wave workgroups per CU on 32-row tiles
       ws_args g2 = g;
       g2.ntiles = (int)gnx_cdiv(g.M, (int64_t)32);
       const int cus = h->num_cus > 0 ? h->num_cus : 256;
       const int grid2 = g2.ntiles < 2 * cus ? g2.ntiles : 2 * cus;
-      return ws3_launch_fast<BT, EPI, EPI != EPI_ACCUM, 4>(h, g2, grid2);
+      return ws3_launch_fast<BT, EPI, true, 4>(h, g2, grid2);
     }
-    return ws3_launch_fast<BT, EPI, EPI != EPI_ACCUM, 8>(h, g, grid);
+    if (fast) return ws3_launch_fast<BT, EPI, true, 8>(h, g, grid);
   }
   return ws3_launch_fast<BT, EPI, false, 8>(h, g, grid);
 }
@@ -1827,24 +1757,9 @@ static int32_t gemm_ws_launch(gnx_handle* h, const gnx_gemm_seg& s, int64_t M, i
   const double fl = 2.0 * (double)M * N * s.k;
   gnx_prof_scope prof(h, GNX_K_GEMM_WS, 4.0 * M * (s.k + N) + ((mask || (flags & GNX_GEMM_ACCUMULATE)) ? 4.0 * M * N : 0.0) +
                                             4.0 * N * s.k, fl, split ? 6.0 * fl : 0.0);
-  hipError_t e;
-  if (split) {
-    if (bt)
-      e = epi == EPI_MASK    ? ws3_launch_one<true, EPI_MASK>(h, g, grid)
-          : epi == EPI_ACCUM ? ws3_launch_one<true, EPI_ACCUM>(h, g, grid)
-                             : ws3_launch_one<true, EPI_PLAIN>(h, g, grid);
-    else
-      e = epi == EPI_MASK    ? ws3_launch_one<false, EPI_MASK>(h, g, grid)
-          : epi == EPI_ACCUM ? ws3_launch_one<false, EPI_ACCUM>(h, g, grid)
-                             : ws3_launch_one<false, EPI_PLAIN>(h, g, grid);
-  } else if (bt)
-    e = epi == EPI_MASK    ? ws_launch_one<true, EPI_MASK>(h, g, grid, lds_bytes)
-        : epi == EPI_ACCUM ? ws_launch_one<true, EPI_ACCUM>(h, g, grid, lds_bytes)
-                           : ws_launch_one<true, EPI_PLAIN>(h, g, grid, lds_bytes);
-  else
-    e = epi == EPI_MASK    ? ws_launch_one<false, EPI_MASK>(h, g, grid, lds_bytes)
-        : epi == EPI_ACCUM ? ws_launch_one<false, EPI_ACCUM>(h, g, grid, lds_bytes)
-                           : ws_launch_one<false, EPI_PLAIN>(h, g, grid, lds_bytes);
+  const hipError_t e = epi_dispatch(bt, epi, [&](auto BT, auto EPI) {
+    return split ? ws3_launch_one<BT, EPI>(h, g, grid) : ws_launch_one<BT, EPI>(h, g, grid, lds_bytes);
+  });
   if (e != hipSuccess) {
     gnx_set_error("gnx_gemm (weights-stationary): %s", hipGetErrorString(e));
     return GNX_E_HIP;
@@ -1864,62 +1779,10 @@ static bool gemm_ws_eligible(const gnx_handle* h, int32_t nseg, const gnx_gemm_s
   return h->opt[GNX_OPT_GEMM_WS] != 0;
 }
 
-
-// ---------------------------------------------------------------------------------------------------------------
-// Small-M product (M <= 256: the 60-row bond-table chain  BondEmb -> edge_encoder -> pre-layer-0 slice and its
-// gradients).  The tiled kernel spends ~22 us of pure load/barrier latency on such a problem in ONE workgroup; here a
-// 16 x 16 output patch per 256-thread workgroup stages its A rows and B rows/columns in LDS once and every thread does
-// one K-long dot product: ~M/16 * N/16 workgroups in parallel, a few microseconds.  One segment, no row scale / mask.
-// ---------------------------------------------------------------------------------------------------------------
-#define SM_T 16
-#define SM_KC 128  // K chunk staged per pass
-
-template <bool B_TRANS>
-__global__ void __launch_bounds__(256) k_gemm_small(const float* __restrict__ A, int64_t lda,
-                                                     const float* __restrict__ B, int64_t ldb, int M, int N, int K,
-                                                     const float* __restrict__ bias, float* __restrict__ C, int64_t ldc,
-                                                     int relu, int accumulate) {
-  __shared__ float As[SM_T][SM_KC + 1];
-  __shared__ float Bs[SM_T][SM_KC + 1];  // Bs[n][k]
-  const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
-  const int m0 = blockIdx.x * SM_T, n0 = blockIdx.y * SM_T;
-  float acc = 0.f;
-  for (int k0 = 0; k0 < K; k0 += SM_KC) {
-    const int kc = (K - k0) < SM_KC ? (K - k0) : SM_KC;
-    // stage A[m0..+16][k0..+kc] : consecutive threads along k
-    for (int i = threadIdx.x; i < SM_T * SM_KC; i += 256) {
-      const int r = i / SM_KC, k = i % SM_KC;
-      As[r][k] = (m0 + r < M && k < kc) ? A[(int64_t)(m0 + r) * lda + k0 + k] : 0.f;
-    }
-    if (B_TRANS) {  // B[n][k]
-      for (int i = threadIdx.x; i < SM_T * SM_KC; i += 256) {
-        const int r = i / SM_KC, k = i % SM_KC;
-        Bs[r][k] = (n0 + r < N && k < kc) ? B[(int64_t)(n0 + r) * ldb + k0 + k] : 0.f;
-      }
-    } else {  // B[k][n] : consecutive threads along n
-      for (int i = threadIdx.x; i < SM_T * SM_KC; i += 256) {
-        const int k = i / SM_T, r = i % SM_T;
-        Bs[r][k] = (n0 + r < N && k < kc) ? B[(int64_t)(k0 + k) * ldb + n0 + r] : 0.f;
-      }
-    }
-    __syncthreads();
-#pragma unroll 8
-    for (int k = 0; k < SM_KC; ++k) acc = fmaf(As[ty][k], Bs[tx][k], acc);  // same k-ordered fmaf chain as the MFMA
-    __syncthreads();
-  }
-  const int gm = m0 + ty, gn = n0 + tx;
-  if (gm < M && gn < N) {
-    float v = acc + (bias != nullptr ? bias[gn] : 0.f);
-    float* cp = C + (int64_t)gm * ldc + gn;
-    if (accumulate) v += *cp;
-    *cp = relu ? fmaxf(v, 0.f) : v;
-  }
-}
-
 // ---------------------------------------------------------------------------------------------------------------
 // Mid-size product (M < 4096 rows and few 128 x 128 tiles: a 32-graph batch's 640 atoms / 1 280 bonds): the whole gnx_gemm
 // contract (segments, row scale, degree-class grouping, every epilogue) on 16 x 16 output patches, one output per thread,
-// the k-ordered fp32 fmaf chain of k_gemm_small.  The tiled kernel gives such a problem 5-10 workgroups that walk K
+// the k-ordered fp32 fmaf chain of k_gemm_small_batched.  The tiled kernel gives such a problem 5-10 workgroups that walk K
 // serially, two barriers per 32 k: 40 us per launch, 78 launches = 3.3 of the 4.4 ms of a cfg-1 (B = 32) step; here
 // M / 16 x N / 16 workgroups stage 128 k per barrier pair with 16-byte loads and read LDS 16 bytes at a time.
 // ---------------------------------------------------------------------------------------------------------------
@@ -2067,13 +1930,21 @@ __global__ void __launch_bounds__(256) k_gemm_mid(gemm_args g) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// Batched small products: up to GNX_SMALL_BATCH independent problems of k_gemm_small's kind in ONE launch (the 60-row
-// bond-table chain, the merged lin o last-post weights and their gradients for ALL layers of a model; VERDICT r2 #4:
-// ~360 launches per step, 54 of them 16 x 16-patch products of ~8 us each).  blockIdx.y = problem, blockIdx.x = output
-// patch.  Either operand may be read transposed (the weight gradients of these tiny layers are A^T B products), the
-// result may be accumulated plainly (problems of one launch must then write disjoint outputs) or with fp32 atomics.
-// Same k-ordered fmaf chain and K chunking as k_gemm_small: bit-identical results for the untransposed forms.
+// Small products (M <= 256: the 60-row bond-table chain  BondEmb -> edge_encoder -> pre-layer-0 slice and its
+// gradients).  The tiled kernel spends ~22 us of pure load/barrier latency on such a problem in ONE workgroup; here a
+// 16 x 16 output patch per 256-thread workgroup stages its A rows and B rows/columns in LDS once and every thread does
+// one K-long dot product (the k-ordered fmaf chain of the fp32 MFMA): ~M/16 * N/16 workgroups in parallel, a few
+// microseconds.  One segment, no row scale / mask.
+// Up to GNX_SMALL_BATCH independent problems in ONE launch (the bond-table chain, the merged lin o last-post weights
+// and their gradients for ALL layers of a model; VERDICT r2 #4: ~360 launches per step, 54 of them 16 x 16-patch
+// products of ~8 us each); gnx_gemm's own small path (GNX_OPT_GEMM_MID = 0) is a batch of one.  blockIdx.y = problem,
+// blockIdx.x = output patch.  Either operand may be read transposed (the weight gradients of these tiny layers are
+// A^T B products), the result may be accumulated plainly (problems of one launch must then write disjoint outputs) or
+// with fp32 atomics.
 // ---------------------------------------------------------------------------------------------------------------
+#define SM_T 16
+#define SM_KC 128  // K chunk staged per pass
+
 struct small_batch_args {
   gnx_small_prob p[GNX_SMALL_BATCH];
   int n;
@@ -2238,16 +2109,10 @@ static int32_t gemm_launch(gnx_handle* h, int32_t nseg, const gnx_gemm_seg* segs
       h->opt[GNX_OPT_GEMM_MID] == 0) {  // (k_gemm_mid below computes the same k-ordered chain with 16-byte staging loads and
                                         // the next chunk prefetched: 3-4 us instead of 7-10 us for a 20-row product)
     const gnx_gemm_seg& s0 = segs[0];
-    dim3 grid((unsigned)gnx_cdiv(M, SM_T), (unsigned)gnx_cdiv(N, SM_T));
-    gnx_prof_scope prof(h, GNX_K_GEMM_SMALL, 4.0 * (M * (double)(s0.k + N) + (double)N * s0.k), 2.0 * M * N * s0.k, 0.0);
-    if (bt)
-      hipLaunchKernelGGL(k_gemm_small<true>, grid, dim3(256), 0, h->stream, s0.a, s0.lda, s0.b, s0.ldb, (int)M, (int)N,
-                         (int)s0.k, bias, C, ldc, (flags & GNX_GEMM_RELU) ? 1 : 0, (flags & GNX_GEMM_ACCUMULATE) ? 1 : 0);
-    else
-      hipLaunchKernelGGL(k_gemm_small<false>, grid, dim3(256), 0, h->stream, s0.a, s0.lda, s0.b, s0.ldb, (int)M, (int)N,
-                         (int)s0.k, bias, C, ldc, (flags & GNX_GEMM_RELU) ? 1 : 0, (flags & GNX_GEMM_ACCUMULATE) ? 1 : 0);
-    GNX_LAUNCH_CHECK();
-    return GNX_OK;
+    const gnx_small_prob p = {s0.a, s0.lda, s0.b, s0.ldb, bias, C, ldc, (int32_t)M, N, s0.k,
+                              (bt ? GNX_SB_B_TRANS : 0) | ((flags & GNX_GEMM_RELU) ? GNX_SB_RELU : 0) |
+                                  ((flags & GNX_GEMM_ACCUMULATE) ? GNX_SB_ACCUMULATE : 0)};
+    return gnx_gemm_small_batched(h, 1, &p);
   }
 
   gemm_args g;
@@ -2288,20 +2153,7 @@ static int32_t gemm_launch(gnx_handle* h, int32_t nseg, const gnx_gemm_seg* segs
     for (int q = 0; q < nseg; ++q) ktot += g.seg[q].k;
     gnx_prof_scope prof(h, GNX_K_GEMM_SMALL, 4.0 * M * (ktot + N) + 4.0 * N * ktot, 2.0 * (double)M * N * ktot, 0.0);
     const dim3 gm((unsigned)(tile_info ? max_tiles * 8 : gnx_cdiv(M, MID_T)), (unsigned)gnx_cdiv(N, MID_T));
-#define GNX_LAUNCH_MID(BT)                                                                              \
-  do {                                                                                                  \
-    if (epi == EPI_MASK)                                                                                \
-      hipLaunchKernelGGL((k_gemm_mid<BT, EPI_MASK>), gm, dim3(256), 0, h->stream, g);                   \
-    else if (epi == EPI_ACCUM)                                                                          \
-      hipLaunchKernelGGL((k_gemm_mid<BT, EPI_ACCUM>), gm, dim3(256), 0, h->stream, g);                  \
-    else                                                                                                \
-      hipLaunchKernelGGL((k_gemm_mid<BT, EPI_PLAIN>), gm, dim3(256), 0, h->stream, g);                  \
-  } while (0)
-    if (bt)
-      GNX_LAUNCH_MID(true);
-    else
-      GNX_LAUNCH_MID(false);
-#undef GNX_LAUNCH_MID
+    epi_dispatch(bt, epi, [&](auto BT, auto EPI) { hipLaunchKernelGGL((k_gemm_mid<BT, EPI>), gm, dim3(256), 0, h->stream, g); });
     GNX_LAUNCH_CHECK();
     return GNX_OK;
   }
@@ -2379,39 +2231,26 @@ static int32_t gemm_launch(gnx_handle* h, int32_t nseg, const gnx_gemm_seg* segs
     g.steps = sa.Kpad / BK;
   }
   if (split_only) return GNX_OK;  // (this call takes a kernel that needs no images)
-#define GNX_LAUNCH_GEMM(BT, EPI)                                                          \
-  do {                                                                                    \
-    if (split) {                                                                          \
-      if (as3) {                                                                          \
-        const unsigned ga = tile_info ? (unsigned)(2 * max_tiles) : (unsigned)gnx_cdiv(M, AS_BM); \
-        GNX_HIP(as3_launch_one<EPI>(h, g, ga));                                           \
-      } else if (pipe && mi3)                                                             \
-        hipLaunchKernelGGL((k_gemm3p<EPI, 3>), grid3, dim3(256), G3P_LDS(3), h->stream, g); \
-      else if (pipe)                                                                      \
-        hipLaunchKernelGGL((k_gemm3p<EPI, 4>), grid3, dim3(256), G3P_LDS(4), h->stream, g); \
-      else                                                                                \
-        hipLaunchKernelGGL((k_gemm3<EPI>), grid3, dim3(256), 0, h->stream, g);            \
-    } else if (vec)                                                                       \
-      hipLaunchKernelGGL((k_gemm<BT, EPI, true>), grid, dim3(256), 0, h->stream, g);      \
-    else                                                                                  \
-      hipLaunchKernelGGL((k_gemm<BT, EPI, false>), grid, dim3(256), 0, h->stream, g);     \
-  } while (0)
-  if (bt) {
-    if (epi == EPI_MASK)
-      GNX_LAUNCH_GEMM(true, EPI_MASK);
-    else if (epi == EPI_ACCUM)
-      GNX_LAUNCH_GEMM(true, EPI_ACCUM);
-    else
-      GNX_LAUNCH_GEMM(true, EPI_PLAIN);
-  } else {
-    if (epi == EPI_MASK)
-      GNX_LAUNCH_GEMM(false, EPI_MASK);
-    else if (epi == EPI_ACCUM)
-      GNX_LAUNCH_GEMM(false, EPI_ACCUM);
-    else
-      GNX_LAUNCH_GEMM(false, EPI_PLAIN);
-  }
-#undef GNX_LAUNCH_GEMM
+  const hipError_t lds_limit = epi_dispatch(bt, epi, [&](auto BT, auto EPI) {
+    if (split && as3) {
+      const hipError_t e = gnx_raise_lds_limit<&k_gemm_as3<EPI>>((int)AS_LDS);
+      if (e != hipSuccess) return e;
+      const unsigned ga = tile_info ? (unsigned)(2 * max_tiles) : (unsigned)gnx_cdiv(M, AS_BM);
+      hipLaunchKernelGGL((k_gemm_as3<EPI>), dim3(ga), dim3(256), AS_LDS, h->stream, g);
+    } else if (split && pipe && mi3) {
+      hipLaunchKernelGGL((k_gemm3p<EPI, 3>), grid3, dim3(256), G3P_LDS(3), h->stream, g);
+    } else if (split && pipe) {
+      hipLaunchKernelGGL((k_gemm3p<EPI, 4>), grid3, dim3(256), G3P_LDS(4), h->stream, g);
+    } else if (split) {
+      hipLaunchKernelGGL((k_gemm3<EPI>), grid3, dim3(256), 0, h->stream, g);
+    } else if (vec) {
+      hipLaunchKernelGGL((k_gemm<BT, EPI, true>), grid, dim3(256), 0, h->stream, g);
+    } else {
+      hipLaunchKernelGGL((k_gemm<BT, EPI, false>), grid, dim3(256), 0, h->stream, g);
+    }
+    return hipSuccess;
+  });
+  GNX_HIP(lds_limit);
   GNX_LAUNCH_CHECK();
   return GNX_OK;
 }
@@ -2452,1280 +2291,3 @@ extern "C" int32_t gnx_gemm_grouped_rows(gnx_handle* h, int32_t nseg, const gnx_
                      tile_info, ntiles, max_tiles, ws, ws_bytes, tile_rows);
 }
 
-// ---------------------------------------------------------------------------------------------------------------
-// Weight gradient  dW[n,k] += sum_m dC[m,n] * rs[m]*A[m,k]   (both operands k-row images: the contraction index m is the
-// row of both).  grid = (M chunks, n tiles, k tiles); fp32 atomics into dW; the k-tile-0 workgroups also reduce dbias.
-// ---------------------------------------------------------------------------------------------------------------
-struct wgrad_args {
-  const float* X;  // dC [M, N]
-  int64_t ldx;
-  const float* Y;  // A  [M, K]
-  int64_t ldy;
-  const float* rs;
-  int64_t M;
-  int N, K;
-  float* dW;
-  int64_t lddw;
-  float* dbias;
-  int64_t rows_per_block;
-  int vec_x, vec_y;
-  // grouped mode: blockIdx.x = chunk; rows row_index[chunk_info[3b] .. +chunk_info[3b+1]) add into dW + class * stride
-  const int* row_index;
-  const int* chunk_info;
-  const int* nchunks;
-  int64_t dw_cls_stride;
-  const float* zero;  // 16 readable zero bytes (k_gemm_wgrad3p: target of masked-out loads)
-};
-
-template <bool VEC, bool GROUPED>
-__device__ __forceinline__ void wgrad_body(const wgrad_args& g, const int bx, const int by, const int bz, float* Xs,
-                                           float* Ys) {
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = tid >> 6;
-  const int wm = wave >> 1, wn = wave & 1;
-  const int li = lane & 31, lh = lane >> 5;
-  const int n0 = by * BN;  // dW row tile (output features)
-  const int c0 = bz * BN;  // dW col tile (input features)
-  if (n0 >= g.N || c0 >= g.K) return;
-  int64_t r_begin = (int64_t)bx * g.rows_per_block;
-  int64_t r_end = r_begin + g.rows_per_block;
-  if (r_end > g.M) r_end = g.M;
-  float* dW = g.dW;
-  if constexpr (GROUPED) {
-    if (bx >= g.nchunks[0]) return;
-    r_begin = g.chunk_info[3 * bx];
-    r_end = r_begin + g.chunk_info[3 * bx + 1];
-    dW += (int64_t)g.chunk_info[3 * bx + 2] * g.dw_cls_stride;
-  }
-  if (r_begin >= r_end) return;  // (workgroup-uniform) nothing to contribute: skip the zero-valued atomic flush
-
-  f32x16 acc[2][2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-  float bsum = 0.f;  // threads 0..127: column n0+tid of dC
-
-  const int br = tid >> 5;
-  const int bc = (tid & 31) * 4;
-  f32x4 rx[4], ry[4];
-  int okmask = 0;
-  float rsv[4] = {1.f, 1.f, 1.f, 1.f};
-
-  auto load_tile = [&](int64_t r0) {
-    if constexpr (VEC) {
-      // raw loads; select / row scale deferred to the LDS store (see k_gemm)
-      const int xn = n0 + bc, yk = c0 + bc;
-      const bool x_ok = xn < g.N, y_ok = yk < g.K;
-      const int xc = x_ok ? xn : 0, yc = y_ok ? yk : 0;
-      int64_t rowi[4];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int64_t pos = r0 + br + 8 * i;
-        const int64_t pc = pos < r_end ? pos : r_begin;  // clamped (r_begin < r_end here)
-        rowi[i] = GROUPED ? (int64_t)g.row_index[pc] : pc;
-      }
-      okmask = 0;
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const bool rv = r0 + br + 8 * i < r_end;
-        rx[i] = *reinterpret_cast<const f32x4*>(g.X + rowi[i] * g.ldx + xc);
-        ry[i] = *reinterpret_cast<const f32x4*>(g.Y + rowi[i] * g.ldy + yc);
-        rsv[i] = *(g.rs != nullptr ? g.rs + rowi[i] : &c_one);
-        okmask |= (rv && x_ok) ? (1 << i) : 0;
-        okmask |= (rv && y_ok) ? (16 << i) : 0;
-      }
-      return;
-    }
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      int64_t gm = r0 + br + 8 * i;
-      bool rv = gm < r_end;
-      if (GROUPED && rv) gm = g.row_index[gm];
-      int nv = rv ? g.N - (n0 + bc) : 0;
-      rx[i] = ld4(g.X + gm * g.ldx + n0 + bc, g.vec_x, nv);
-      int kv = rv ? g.K - (c0 + bc) : 0;
-      f32x4 v = ld4(g.Y + gm * g.ldy + c0 + bc, g.vec_y, kv);
-      if (g.rs != nullptr && rv) {
-        float sc = g.rs[gm];
-        v.x *= sc;
-        v.y *= sc;
-        v.z *= sc;
-        v.w *= sc;
-      }
-      ry[i] = v;
-    }
-  };
-
-  int64_t r0 = r_begin;
-  if (r0 < r_end) load_tile(r0);
-  while (r0 < r_end) {
-    __syncthreads();
-    if constexpr (VEC) {
-      const f32x4 z = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        f32x4 v = ry[i];
-        v.x *= rsv[i];
-        v.y *= rsv[i];
-        v.z *= rsv[i];
-        v.w *= rsv[i];
-        rx[i] = ((okmask >> i) & 1) ? rx[i] : z;
-        ry[i] = ((okmask >> (4 + i)) & 1) ? v : z;
-      }
-    }
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      int kr = br + 8 * i;
-      *reinterpret_cast<f32x4*>(&Xs[kr * LDN + bc]) = rx[i];
-      *reinterpret_cast<f32x4*>(&Ys[kr * LDN + bc]) = ry[i];
-    }
-    __syncthreads();
-    r0 += BK;
-    if (r0 < r_end) load_tile(r0);
-
-    if (g.dbias != nullptr && bz == 0 && tid < BN) {
-#pragma unroll 8
-      for (int r = 0; r < BK; ++r) bsum += Xs[r * LDN + tid];
-    }
-#pragma unroll
-    for (int kk = 0; kk < 4; ++kk) {
-      f32x4 a[2], b[2];
-#pragma unroll
-      for (int mi = 0; mi < 2; ++mi) {
-        const float* p = &Xs[(kk * 8 + 4 * lh) * LDN + wm * 64 + mi * 32 + li];
-        a[mi].x = p[0];
-        a[mi].y = p[LDN];
-        a[mi].z = p[2 * LDN];
-        a[mi].w = p[3 * LDN];
-      }
-#pragma unroll
-      for (int ni = 0; ni < 2; ++ni) {
-        const float* p = &Ys[(kk * 8 + 4 * lh) * LDN + wn * 64 + ni * 32 + li];
-        b[ni].x = p[0];
-        b[ni].y = p[LDN];
-        b[ni].z = p[2 * LDN];
-        b[ni].w = p[3 * LDN];
-      }
-#pragma unroll
-      for (int t = 0; t < 4; ++t)
-#pragma unroll
-        for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-          for (int ni = 0; ni < 2; ++ni)
-            acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[mi][t], b[ni][t], acc[mi][ni], 0, 0, 0);
-    }
-  }
-
-#pragma unroll
-  for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-    for (int ni = 0; ni < 2; ++ni) {
-      int gc = c0 + wn * 64 + ni * 32 + li;
-      if (gc >= g.K) continue;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        int gr = n0 + wm * 64 + mi * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-        if (gr >= g.N) continue;
-        atomicAdd(dW + (int64_t)gr * g.lddw + gc, acc[mi][ni][r]);
-      }
-    }
-  if (g.dbias != nullptr && bz == 0 && tid < BN && n0 + tid < g.N) atomicAdd(g.dbias + n0 + tid, bsum);
-}
-
-template <bool VEC, bool GROUPED>
-__global__ void __launch_bounds__(256, 2) k_gemm_wgrad(wgrad_args g) {
-  __shared__ __attribute__((aligned(16))) float Xs[BK * LDN];
-  __shared__ __attribute__((aligned(16))) float Ys[BK * LDN];
-  wgrad_body<VEC, GROUPED>(g, blockIdx.x, blockIdx.y, blockIdx.z, Xs, Ys);
-}
-
-// ---------------------------------------------------------------------------------------------------------------
-// Split-operand weight gradient (same contract as wgrad_body<true, GROUPED> without a row scale; see the split-operand
-// notes at k_gemm_ws3).  dW[n,k] = sum_m dC[m,n] A[m,k] contracts over the ROW index of both operands, so both bf16
-// images must be column-major for the matrix core (a lane needs 8 consecutive m of one column).  The transpose is done
-// by the loader: thread = (column tid & 127, 16 rows), 16 four-byte loads per operand and 32-row step (each wave
-// instruction reads 256 contiguous bytes of one row); the 16 values of a column are split and stored with two
-// ds_write_b128 per image into [3][128 columns][32 m (+8 pad)] -- the same images and the same multiply loop as
-// k_gemm3.  The fp32-MFMA version above runs at ~70 TF and was the largest group of kernels of the step.
-// ---------------------------------------------------------------------------------------------------------------
-template <bool GROUPED>
-__device__ __forceinline__ void wgrad3_body(const wgrad_args& g, const int bx, const int by, const int bz,
-                                            unsigned char* A3, unsigned char* B3, unsigned* offs) {
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = tid >> 6;
-  const int wm = wave >> 1, wn = wave & 1;
-  const int li = lane & 31, lh = lane >> 5;
-  const int n0 = by * BN;  // dW row tile (output features)
-  const int c0 = bz * BN;  // dW col tile (input features)
-  if (n0 >= g.N || c0 >= g.K) return;
-  int64_t r_begin = (int64_t)bx * g.rows_per_block;
-  int64_t r_end = r_begin + g.rows_per_block;
-  if (r_end > g.M) r_end = g.M;
-  float* dW = g.dW;
-  if constexpr (GROUPED) {
-    if (bx >= g.nchunks[0]) return;
-    r_begin = g.chunk_info[3 * bx];
-    r_end = r_begin + g.chunk_info[3 * bx + 1];
-    dW += (int64_t)g.chunk_info[3 * bx + 2] * g.dw_cls_stride;
-  }
-  if (r_begin >= r_end) return;  // (workgroup-uniform) nothing to contribute: skip the zero-valued atomic flush
-
-  f32x16 acc[2][2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-  float bsum = 0.f;  // column n0 + col of dC, this thread's 16-row half
-
-  const int col = tid & 127, rh = (tid >> 7) * 16;
-  const bool x_ok = n0 + col < g.N, y_ok = c0 + col < g.K;
-  const float* xp = g.X + (x_ok ? n0 + col : 0);
-  const float* yp = g.Y + (y_ok ? c0 + col : 0);
-  float gx[16], gy[16];
-  int nvalid = 0;  // valid rows among this thread's 16 of the tile in flight
-
-  // GROUPED: rows are gathered through row_index.  The element offsets row * ld of a step's 32 rows are computed once
-  // per workgroup (threads 0..31, two steps ahead, into a double-buffered LDS array offs[parity][X|Y][32]) instead of
-  // 32 index loads + 32 64-bit multiplies per thread and step; the host guarantees M * ld < 2^32.
-  auto stage_offsets = [&](int64_t r0, int par) {
-    if constexpr (GROUPED) {
-      if (tid < 32) {
-        const int64_t pos = r0 + tid < r_end ? r0 + tid : r_begin;
-        const unsigned row = (unsigned)g.row_index[pos];
-        offs[par * 64 + tid] = row * (unsigned)g.ldx;
-        offs[par * 64 + 32 + tid] = row * (unsigned)g.ldy;
-      }
-    }
-  };
-  auto load_tile = [&](int64_t r0, int par) {
-    const int64_t first = r0 + rh;
-    const int64_t left = r_end - first;
-    nvalid = left >= 16 ? 16 : (left > 0 ? (int)left : 0);
-    if constexpr (GROUPED) {
-      const unsigned* ox = offs + par * 64 + rh;
-      const unsigned* oy = ox + 32;
-#pragma unroll
-      for (int j = 0; j < 16; ++j) {
-        gx[j] = xp[ox[j]];
-        gy[j] = yp[oy[j]];
-      }
-    } else if (r0 + BK <= r_end) {  // full step (workgroup-uniform): one 64-bit product per operand, uniform strides
-      const float* xb = xp + first * g.ldx;
-      const float* yb = yp + first * g.ldy;
-#pragma unroll
-      for (int j = 0; j < 16; ++j) {
-        gx[j] = xb[j * g.ldx];
-        gy[j] = yb[j * g.ldy];
-      }
-    } else {
-#pragma unroll
-      for (int j = 0; j < 16; ++j) {
-        const int64_t row = first + j < r_end ? first + j : r_begin;  // clamped (r_begin < r_end here)
-        gx[j] = xp[row * g.ldx];
-        gy[j] = yp[row * g.ldy];
-      }
-    }
-  };
-
-  auto store_tile = [&]() {
-#pragma unroll
-    for (int hgrp = 0; hgrp < 2; ++hgrp) {
-      float xa[8], ya[8];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const bool ok = 8 * hgrp + j < nvalid;
-        xa[j] = (ok && x_ok) ? gx[8 * hgrp + j] : 0.f;
-        ya[j] = (ok && y_ok) ? gy[8 * hgrp + j] : 0.f;
-        bsum += xa[j];
-      }
-      bf16x8 p1, p2, p3;
-      split3(xa, p1, p2, p3);
-      unsigned char* q = A3 + col * G3_LDB + (rh + 8 * hgrp) * 2;
-      *reinterpret_cast<bf16x8*>(q) = p1;
-      *reinterpret_cast<bf16x8*>(q + G3_PIECE) = p2;
-      *reinterpret_cast<bf16x8*>(q + 2 * G3_PIECE) = p3;
-      split3(ya, p1, p2, p3);
-      q = B3 + col * G3_LDB + (rh + 8 * hgrp) * 2;
-      *reinterpret_cast<bf16x8*>(q) = p1;
-      *reinterpret_cast<bf16x8*>(q + G3_PIECE) = p2;
-      *reinterpret_cast<bf16x8*>(q + 2 * G3_PIECE) = p3;
-    }
-  };
-
-  int64_t r0 = r_begin;
-  int par = 0;
-  stage_offsets(r0, 0);
-  stage_offsets(r0 + BK, 1);
-  if constexpr (GROUPED) __syncthreads();
-  load_tile(r0, 0);
-  while (r0 < r_end) {
-    __syncthreads();  // previous multiply finished reading LDS (and the offsets staged during it are visible)
-    store_tile();
-    __syncthreads();
-    r0 += BK;
-    par ^= 1;
-    if (r0 < r_end) load_tile(r0, par);
-    // offsets of the step after that one go into the other buffer (last read one step ago, two barriers back)
-    if (r0 + BK < r_end) stage_offsets(r0 + BK, par ^ 1);
-#pragma unroll
-    for (int sl = 0; sl < 2; ++sl) {
-      bf16x8 a[2][3], b[2][3];
-#pragma unroll
-      for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-        for (int p = 0; p < 3; ++p)
-          a[mi][p] = *reinterpret_cast<const bf16x8*>(A3 + p * G3_PIECE + (wm * 64 + mi * 32 + li) * G3_LDB + 32 * sl + 16 * lh);
-#pragma unroll
-      for (int ni = 0; ni < 2; ++ni)
-#pragma unroll
-        for (int p = 0; p < 3; ++p)
-          b[ni][p] = *reinterpret_cast<const bf16x8*>(B3 + p * G3_PIECE + (wn * 64 + ni * 32 + li) * G3_LDB + 32 * sl + 16 * lh);
-#pragma unroll
-      for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-        for (int ni = 0; ni < 2; ++ni) {
-          acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[mi][0], b[ni][2], acc[mi][ni], 0, 0, 0);
-          acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[mi][2], b[ni][0], acc[mi][ni], 0, 0, 0);
-          acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[mi][1], b[ni][1], acc[mi][ni], 0, 0, 0);
-          acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[mi][0], b[ni][1], acc[mi][ni], 0, 0, 0);
-          acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[mi][1], b[ni][0], acc[mi][ni], 0, 0, 0);
-          acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[mi][0], b[ni][0], acc[mi][ni], 0, 0, 0);
-        }
-    }
-  }
-
-#pragma unroll
-  for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-    for (int ni = 0; ni < 2; ++ni) {
-      int gc = c0 + wn * 64 + ni * 32 + li;
-      if (gc >= g.K) continue;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        int gr = n0 + wm * 64 + mi * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-        if (gr >= g.N) continue;
-        atomicAdd(dW + (int64_t)gr * g.lddw + gc, acc[mi][ni][r]);
-      }
-    }
-  if (g.dbias != nullptr && bz == 0 && x_ok) atomicAdd(g.dbias + n0 + col, bsum);
-}
-
-template <bool GROUPED>
-__global__ void __launch_bounds__(256, 2) k_gemm_wgrad3(wgrad_args g) {
-  __shared__ __attribute__((aligned(16))) unsigned char A3[G3_OP];
-  __shared__ __attribute__((aligned(16))) unsigned char B3[G3_OP];
-  __shared__ __attribute__((aligned(16))) unsigned offs[128];
-  wgrad3_body<GROUPED>(g, blockIdx.x, blockIdx.y, blockIdx.z, A3, B3, offs);
-}
-
-// ---------------------------------------------------------------------------------------------------------------
-// Wave-specialised split-operand weight gradient (same contract and arithmetic as wgrad3_body for 16-byte aligned
-// operands with N, K multiples of 4), ONE 512-thread workgroup per CU -- the weight-gradient launches are sized to one
-// workgroup per CU anyway, and in the two-barrier body above such a lone workgroup runs its phases back to back: 32
-// four-byte loads per thread, wait, split, LDS stores, barrier, fragment reads, 48 MFMAs, barrier = 2.5-2.8 us per
-// 32-row step against 0.65-0.87 us of MFMA time (SQ_VALU_MFMA_BUSY_CYCLES: 0.20-0.26 of the matrix pipe; ablations:
-// split + LDS stores alone 1.0 us, fragment reads + MFMAs alone 1.27 us, and the compiler keeps the two apart even
-// inside one basic block).  Here the phases belong to different waves of the same SIMD, which the hardware overlaps:
-//   * waves 0..3 multiply: fragment reads + 48 MFMAs per step out of the LDS stage of step j (2 x 2 tiles of 64 x 64);
-//   * waves 4..7 stage: threads 256..383 dC, 384..511 A -- eight 16-byte loads each (8 rows x 4 columns) issued five
-//     steps ahead into four register stages (128 KB in flight per CU), always unconditional (invalid rows / columns read a zero line instead of
-//     being masked), split column by column and written as 16-byte LDS words into the [column][32 m] bf16 images of
-//     step j + 1 (two-stage ring, 120 KB); they also accumulate the bias gradient;
-//   * ONE barrier per step joins the two groups.
-// Rows gathered by degree class stay on wgrad3_body: the same structure with LDS-staged row offsets was built, correct, and
-// SLOWER there (145 vs 123 us per launch: the per-class chunks are 1024 rows = 32 steps, too short for its prologue).
-// Measured (tools/wgrad_ab.py, a layer's eight 81 920 x 128 x 128 problems in one launch = 671 MB): 235 -> 205 us (3.4 -> 3.9
-// TB/s); K = 512: 111 -> 94 us.  Ablations of this kernel: the loads alone 124 us (the HBM floor), + the multiply waves
-// 132 us, + the staging waves' split and stores instead 138 us, both 195-205 us: the two groups slow each other down.
-// tools/ubench/wave_specialised_overlap.hip isolates that: per step, multiply waves alone 0.91 us, staging waves alone
-// 0.60 us (split) / 0.84 us (+ the twelve ds_write_b128), both 1.04 us without and 1.41-1.46 us with the LDS stores --
-// the 16-byte LDS stores, not the split, are what the MFMA waves feel; 1.45 us is this structure's floor, the kernel
-// runs at 2.2 us (loads, masks, address arithmetic, bias sums on top).
-// ---------------------------------------------------------------------------------------------------------------
-#define WG3P_LDS (4 * G3_OP)
-#define WG3P_NST 4  // register stages of the staging waves (must be 4: the prologue and the unrolled loop assume it)
-
-__device__ __forceinline__ void wgrad3p_body(const wgrad_args& g, const int bx, const int by, const int bz,
-                                             unsigned char* lds) {
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = tid >> 6;
-  const int n0 = by * BN;  // dW row tile (output features)
-  const int c0 = bz * BN;  // dW col tile (input features)
-  if (n0 >= g.N || c0 >= g.K) return;
-  int64_t r_begin = (int64_t)bx * g.rows_per_block;
-  int64_t r_end = r_begin + g.rows_per_block;
-  if (r_end > g.M) r_end = g.M;
-  float* const dW = g.dW;
-  if (r_begin >= r_end) return;
-  const int64_t nsteps = (r_end - r_begin + BK - 1) / BK;
-
-  if (wave < 4) {
-    // ================================================================ multiply waves
-    const int wm = wave >> 1, wn = wave & 1;
-    const int li = lane & 31, lh = lane >> 5;
-    f32x16 acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int j = 0; j < 2; ++j)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-    __syncthreads();  // the staging waves' prologue
-    for (int64_t j = 0; j < nsteps; ++j) {
-      const unsigned char* const A3 = lds + (j & 1) * 2 * G3_OP;
-      const unsigned char* const B3 = A3 + G3_OP;
-#pragma unroll
-      for (int sl = 0; sl < 2; ++sl) {
-        bf16x8 a[2][3], b[2][3];
-#pragma unroll
-        for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-          for (int p = 0; p < 3; ++p)
-            a[mi][p] = *reinterpret_cast<const bf16x8*>(A3 + p * G3_PIECE + (wm * 64 + mi * 32 + li) * G3_LDB + 32 * sl + 16 * lh);
-#pragma unroll
-        for (int ni = 0; ni < 2; ++ni)
-#pragma unroll
-          for (int p = 0; p < 3; ++p)
-            b[ni][p] = *reinterpret_cast<const bf16x8*>(B3 + p * G3_PIECE + (wn * 64 + ni * 32 + li) * G3_LDB + 32 * sl + 16 * lh);
-#pragma unroll
-        for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-          for (int ni = 0; ni < 2; ++ni) {
-            acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[mi][0], b[ni][2], acc[mi][ni], 0, 0, 0);
-            acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[mi][2], b[ni][0], acc[mi][ni], 0, 0, 0);
-            acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[mi][1], b[ni][1], acc[mi][ni], 0, 0, 0);
-            acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[mi][0], b[ni][1], acc[mi][ni], 0, 0, 0);
-            acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[mi][1], b[ni][0], acc[mi][ni], 0, 0, 0);
-            acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[mi][0], b[ni][0], acc[mi][ni], 0, 0, 0);
-          }
-      }
-      __syncthreads();
-    }
-#pragma unroll
-    for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-      for (int ni = 0; ni < 2; ++ni) {
-        int gc = c0 + wn * 64 + ni * 32 + li;
-        if (gc >= g.K) continue;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          int gr = n0 + wm * 64 + mi * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-          if (gr >= g.N) continue;
-          atomicAdd(dW + (int64_t)gr * g.lddw + gc, acc[mi][ni][r]);
-        }
-      }
-    return;
-  }
-
-  // ================================================================== staging waves
-  const int lt = tid - 256;
-  const int role = lt >> 7;  // 0: dC (dW rows n0..), 1: A (dW columns c0..)
-  const int c4 = (lt & 31) * 4, rg = (lt >> 5) & 3;
-  const bool col_ok = role ? (c0 + c4 < g.K) : (n0 + c4 < g.N);  // N, K multiples of 4: the quad is valid as a whole
-  const float* const base = (role ? g.Y + (col_ok ? c0 + c4 : 0) : g.X + (col_ok ? n0 + c4 : 0));
-  const float* const zero = g.zero;  // 16 zero bytes: what an invalid row or column quad reads
-  const int64_t ld = role ? g.ldy : g.ldx;
-  const int img = role * G3_OP;
-  float bsum[4] = {0.f, 0.f, 0.f, 0.f};  // role 0: column sums of dC (bias gradient)
-
-  f32x4 v[WG3P_NST][8];  // register stages: the loads of WG3P_NST steps in flight (32 KB per stage and workgroup)
-
-  auto load_step = [&](auto PC, int64_t r0) {
-    constexpr int P = decltype(PC)::value;
-    const int64_t left = r_end - (r0 + rg * 8);
-    const int nval = (left >= 8 && col_ok) ? 8 : ((left > 0 && col_ok) ? (int)left : 0);
-    const float* p = base + (r0 + rg * 8) * ld;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) v[P][j] = *reinterpret_cast<const f32x4*>(j < nval ? p + j * ld : zero);
-  };
-  auto store_step = [&](auto PC, unsigned char* stage) {
-    constexpr int P = decltype(PC)::value;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      float xa[8];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) xa[j] = v[P][j][q];
-      if (role == 0) {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) bsum[q] += xa[j];
-      }
-      bf16x8 p1, p2, p3;
-      split3(xa, p1, p2, p3);
-      unsigned char* dst = stage + img + (c4 + q) * G3_LDB + rg * 16;
-      *reinterpret_cast<bf16x8*>(dst) = p1;
-      *reinterpret_cast<bf16x8*>(dst + G3_PIECE) = p2;
-      *reinterpret_cast<bf16x8*>(dst + 2 * G3_PIECE) = p3;
-    }
-  };
-  auto row_of = [&](int64_t step) { return r_begin + step * BK; };
-
-  // ---- prologue: steps 0 .. 3 loaded, step 0 split into LDS stage 0, step 4 loaded into its register stage
-  load_step(std::integral_constant<int, 0>{}, row_of(0));
-  load_step(std::integral_constant<int, 1>{}, row_of(1));
-  load_step(std::integral_constant<int, 2>{}, row_of(2));
-  load_step(std::integral_constant<int, 3>{}, row_of(3));
-  store_step(std::integral_constant<int, 0>{}, lds);
-  load_step(std::integral_constant<int, 0>{}, row_of(4));
-  __syncthreads();
-
-  // iteration j (K = j % NST): split register stage (K + 1) % NST = step j + 1 into LDS stage (j + 1) & 1, then refill
-  // that register stage with step j + 1 + NST
-  auto iteration = [&](auto KC, int64_t j) {
-    constexpr int K = decltype(KC)::value;
-    constexpr int P = (K + 1) % WG3P_NST;
-    store_step(std::integral_constant<int, P>{}, lds + ((K + 1) & 1) * 2 * G3_OP);
-    load_step(std::integral_constant<int, P>{}, row_of(j + 1 + WG3P_NST));
-    __syncthreads();
-  };
-  for (int64_t j = 0; j < nsteps; j += 4) {
-    iteration(std::integral_constant<int, 0>{}, j);
-    if (j + 1 >= nsteps) break;
-    iteration(std::integral_constant<int, 1>{}, j + 1);
-    if (j + 2 >= nsteps) break;
-    iteration(std::integral_constant<int, 2>{}, j + 2);
-    if (j + 3 >= nsteps) break;
-    iteration(std::integral_constant<int, 3>{}, j + 3);
-  }
-  if (g.dbias != nullptr && bz == 0 && role == 0 && col_ok) {
-#pragma unroll
-    for (int q = 0; q < 4; ++q) atomicAdd(g.dbias + n0 + c4 + q, bsum[q]);
-  }
-}
-
-__global__ void __launch_bounds__(512, 1) k_gemm_wgrad3p(wgrad_args g) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char lds_w[];
-  wgrad3p_body(g, blockIdx.x, blockIdx.y, blockIdx.z, lds_w);
-}
-
-// Several independent weight gradients in ONE launch (a layer's same-shaped dW = g^T a products): blockIdx.x =
-// problem * chunks + chunk.  With P problems sharing the grid every workgroup owns a P x longer row range, so the
-// per-problem atomic flush shrinks P x at equal parallelism (a lone 128x128 dW over 82k rows flushes 33 MB of fp32
-// atomics for 17 us of MFMA work).
-#define WGRAD_MAX_BATCH 8
-struct wgrad_batch_args {
-  wgrad_args p[WGRAD_MAX_BATCH];
-  int nprob;
-  // 1-D work list: problem i owns workgroups [wg_off[i], wg_off[i+1]) = its row chunks x its 128x128 output tiles.
-  // Chunk counts are per problem (proportional to its share of the work): one uniform count starved the small
-  // problems of a batch that also held a 512x512 one (cfg-5: 32 workgroups busy on 256 CUs, 26 TF).
-  int wg_off[WGRAD_MAX_BATCH + 1];
-  int tiles_k[WGRAD_MAX_BATCH];  // column tiles of dW
-  int tiles[WGRAD_MAX_BATCH];    // row tiles x column tiles of dW
-};
-
-// (problem, chunk, dW row tile, dW column tile) of a workgroup of the 1-D batched grid
-__device__ __forceinline__ void wgrad_batch_locate(const wgrad_batch_args& b, int w, int& prob, int& chunk, int& by,
-                                                   int& bz) {
-  prob = 0;
-#pragma unroll
-  for (int i = 1; i < WGRAD_MAX_BATCH; ++i) prob += (i < b.nprob && w >= b.wg_off[i]) ? 1 : 0;
-  int off = b.wg_off[0], tiles = b.tiles[0], tk = b.tiles_k[0];
-#pragma unroll
-  for (int i = 1; i < WGRAD_MAX_BATCH; ++i)
-    if (i == prob) {
-      off = b.wg_off[i];
-      tiles = b.tiles[i];
-      tk = b.tiles_k[i];
-    }
-  const int local = w - off;
-  chunk = local / tiles;
-  const int t = local - chunk * tiles;
-  by = t / tk;
-  bz = t - by * tk;
-}
-
-__global__ void __launch_bounds__(256, 2) k_gemm_wgrad_batched(wgrad_batch_args b) {
-  __shared__ __attribute__((aligned(16))) float Xs[BK * LDN];
-  __shared__ __attribute__((aligned(16))) float Ys[BK * LDN];
-  int prob, chunk, by, bz;
-  wgrad_batch_locate(b, blockIdx.x, prob, chunk, by, bz);
-  // copy the selected descriptor (wave-uniform index) so the body sees scalars
-  wgrad_args g = b.p[0];
-#pragma unroll
-  for (int i = 1; i < WGRAD_MAX_BATCH; ++i)
-    if (i == prob) g = b.p[i];
-  wgrad_body<true, false>(g, chunk, by, bz, Xs, Ys);
-}
-
-__global__ void __launch_bounds__(256, 2) k_gemm_wgrad3_batched(wgrad_batch_args b) {
-  __shared__ __attribute__((aligned(16))) unsigned char A3[G3_OP];
-  __shared__ __attribute__((aligned(16))) unsigned char B3[G3_OP];
-  int prob, chunk, by, bz;
-  wgrad_batch_locate(b, blockIdx.x, prob, chunk, by, bz);
-  wgrad_args g = b.p[0];
-#pragma unroll
-  for (int i = 1; i < WGRAD_MAX_BATCH; ++i)
-    if (i == prob) g = b.p[i];
-  wgrad3_body<false>(g, chunk, by, bz, A3, B3, nullptr);
-}
-
-__global__ void __launch_bounds__(512, 1) k_gemm_wgrad3p_batched(wgrad_batch_args b) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char lds_wb[];
-  int prob, chunk, by, bz;
-  wgrad_batch_locate(b, blockIdx.x, prob, chunk, by, bz);
-  wgrad_args g = b.p[0];
-#pragma unroll
-  for (int i = 1; i < WGRAD_MAX_BATCH; ++i)
-    if (i == prob) g = b.p[i];
-  wgrad3p_body(g, chunk, by, bz, lds_wb);
-}
-
-template <typename KERNEL>
-static hipError_t wgrad3p_attr(KERNEL kern) {
-  return hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)WG3P_LDS);
-}
-
-// the split-operand weight-gradient kernels take over for large row counts (GNX_GEMM_SPLIT=0: fp32 MFMA everywhere)
-static bool wgrad_split_enabled(const gnx_handle* h, int64_t M, bool any_rowscale) {
-  if (any_rowscale || M < 4096) return false;
-  return h->opt[GNX_OPT_GEMM_SPLIT] != 0;
-}
-
-static int32_t wgrad_launch(gnx_handle* h, const float* dC, int64_t lddc, const float* A, int64_t lda,
-                            const float* rowscale, int64_t M, int32_t N, int32_t K, float* dW, int64_t lddw,
-                            float* dbias, const int32_t* row_index, const int32_t* chunk_info, const int32_t* nchunks,
-                            int64_t max_chunks, int64_t dw_cls_stride) {
-  GNX_CHECK_ARG(h && dC && A && dW, "gnx_gemm_wgrad: NULL argument");
-  GNX_CHECK_ARG(M >= 0 && N > 0 && K > 0 && lddc >= N && lda >= K && lddw >= K, "gnx_gemm_wgrad: bad shape");
-  if (M == 0) return GNX_OK;
-  wgrad_args g;
-  g.X = dC;
-  g.ldx = lddc;
-  g.Y = A;
-  g.ldy = lda;
-  g.rs = rowscale;
-  g.M = M;
-  g.N = N;
-  g.K = K;
-  g.dW = dW;
-  g.lddw = lddw;
-  g.dbias = dbias;
-  g.vec_x = aligned16(dC) && (lddc % 4 == 0);
-  g.vec_y = aligned16(A) && (lda % 4 == 0);
-  int64_t tiles = gnx_cdiv(N, BN) * gnx_cdiv(K, BN);
-  // aim for ~512 workgroups; at least 128 rows each (4 K-steps) so the atomic flush stays amortised
-  // default: one workgroup per CU.  Measured on cfg-2 (tools/ab_bench.py, same box): 512 / 1024 workgroups cost 0.4 ms
-  // per step more -- every workgroup flushes its 128 x 128 partial sum with fp32 atomics, and a weight-gradient launch
-  // that fills every CU slot starves the input-gradient chain it overlaps with on the main stream.
-  const int64_t target_wgs = h->opt[GNX_OPT_WGRAD_WGS] > 0 ? h->opt[GNX_OPT_WGRAD_WGS] : (h->num_cus > 0 ? h->num_cus : 256);
-  int64_t chunks = gnx_cdiv(target_wgs, tiles);
-  int64_t rows = gnx_cdiv(gnx_cdiv(M, chunks), BK) * BK;
-  if (rows < 128) rows = 128;
-  g.rows_per_block = rows;
-  g.row_index = row_index;
-  g.chunk_info = chunk_info;
-  g.nchunks = nchunks;
-  g.dw_cls_stride = dw_cls_stride;
-  g.zero = h->d_zero;
-  dim3 grid((unsigned)(chunk_info ? max_chunks : gnx_cdiv(M, rows)), (unsigned)gnx_cdiv(N, BN), (unsigned)gnx_cdiv(K, BN));
-  bool vec = g.vec_x && g.vec_y && (N % 4 == 0) && (K % 4 == 0);
-  if (h->opt[GNX_OPT_WGRAD_VEC] == 0) vec = false;
-  const bool offs32 = (uint64_t)M * (uint64_t)lddc < (1ull << 32) && (uint64_t)M * (uint64_t)lda < (1ull << 32);
-  const bool wsplit = wgrad_split_enabled(h, M, rowscale != nullptr) && (!chunk_info || offs32);
-  const double wfl = 2.0 * (double)M * N * K;
-  gnx_prof_scope prof(h, GNX_K_GEMM_WGRAD, 4.0 * M * ((double)N + K) + 4.0 * N * K, wfl, wsplit ? 6.0 * wfl : 0.0);
-  // (short row ranges -- the readout's 4096-row problems -- keep the two-barrier kernel: 14.7 vs 24 us)
-  if (wsplit && vec && !chunk_info && rows >= 512 && h->opt[GNX_OPT_WGRAD_PIPE] != 0) {
-    static bool attr_set = false;
-    if (!attr_set) {
-      GNX_HIP(wgrad3p_attr(&k_gemm_wgrad3p));
-      attr_set = true;
-    }
-    hipLaunchKernelGGL(k_gemm_wgrad3p, grid, dim3(512), WG3P_LDS, h->stream, g);
-  } else if (wsplit) {
-    if (chunk_info)
-      hipLaunchKernelGGL((k_gemm_wgrad3<true>), grid, dim3(256), 0, h->stream, g);
-    else
-      hipLaunchKernelGGL((k_gemm_wgrad3<false>), grid, dim3(256), 0, h->stream, g);
-  } else if (chunk_info) {
-    if (vec)
-      hipLaunchKernelGGL((k_gemm_wgrad<true, true>), grid, dim3(256), 0, h->stream, g);
-    else
-      hipLaunchKernelGGL((k_gemm_wgrad<false, true>), grid, dim3(256), 0, h->stream, g);
-  } else {
-    if (vec)
-      hipLaunchKernelGGL((k_gemm_wgrad<true, false>), grid, dim3(256), 0, h->stream, g);
-    else
-      hipLaunchKernelGGL((k_gemm_wgrad<false, false>), grid, dim3(256), 0, h->stream, g);
-  }
-  GNX_LAUNCH_CHECK();
-  return GNX_OK;
-}
-
-extern "C" int32_t gnx_gemm_wgrad(gnx_handle* h, const float* dC, int64_t lddc, const float* A, int64_t lda,
-                                  const float* rowscale, int64_t M, int32_t N, int32_t K, float* dW, int64_t lddw,
-                                  float* dbias) {
-  return wgrad_launch(h, dC, lddc, A, lda, rowscale, M, N, K, dW, lddw, dbias, nullptr, nullptr, nullptr, 0, 0);
-}
-
-extern "C" int32_t gnx_gemm_wgrad_grouped(gnx_handle* h, const float* dC, int64_t lddc, const float* A, int64_t lda,
-                                          int64_t M, int32_t N, int32_t K, float* dW_cls, int64_t lddw,
-                                          int64_t dw_cls_stride, const int32_t* row_index, const int32_t* chunk_info,
-                                          const int32_t* nchunks, int64_t max_chunks) {
-  GNX_CHECK_ARG(row_index && chunk_info && nchunks && max_chunks > 0, "gnx_gemm_wgrad_grouped: NULL argument");
-  return wgrad_launch(h, dC, lddc, A, lda, nullptr, M, N, K, dW_cls, lddw, nullptr, row_index, chunk_info, nchunks,
-                      max_chunks, dw_cls_stride);
-}
-
-// ---------------------------------------------------------------------------------------------------------------
-// PNA post-layer 0 effective weights per in-degree class d (amp/att depend on d only):
-//   Weff[d][o][j] = W[o][F + j] + amp(d) W[o][5F + j] + att(d) W[o][9F + j],   o < F, j < 4F
-// and the matching weight gradient:  dW[:, F:5F] += sum_d dWeff[d], [:, 5F:9F] += sum_d amp(d) dWeff[d], ...
-// ---------------------------------------------------------------------------------------------------------------
-__global__ void k_pna_weff(const float* __restrict__ W, int64_t ldw, int F, int D, float avg_log,
-                           float* __restrict__ Weff) {
-  int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  int64_t per = (int64_t)F * 4 * F;
-  if (i >= per * D) return;
-  int d = (int)(i / per);
-  int o = (int)((i % per) / (4 * F)), j = (int)(i % (4 * F));
-  float dd = (float)d;
-  float amp = logf(dd + 1.0f) / avg_log;
-  float att = avg_log / logf(fmaxf(dd, 1.0f) + 1.0f);
-  const float* w = W + (int64_t)o * ldw;
-  Weff[i] = w[F + j] + amp * w[5 * F + j] + att * w[9 * F + j];
-}
-
-__global__ void k_pna_weff_bwd(const float* __restrict__ dWeff, int F, int D, float avg_log, float* __restrict__ dW,
-                               int64_t lddw) {
-  int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  int64_t per = (int64_t)F * 4 * F;
-  if (i >= per) return;
-  int o = (int)(i / (4 * F)), j = (int)(i % (4 * F));
-  float s1 = 0.f, s2 = 0.f, s3 = 0.f;
-  for (int d = 0; d < D; ++d) {
-    float dd = (float)d;
-    float amp = logf(dd + 1.0f) / avg_log;
-    float att = avg_log / logf(fmaxf(dd, 1.0f) + 1.0f);
-    float v = dWeff[(int64_t)d * per + i];
-    s1 += v;
-    s2 += amp * v;
-    s3 += att * v;
-  }
-  float* w = dW + (int64_t)o * lddw;
-  w[F + j] += s1;
-  w[5 * F + j] += s2;
-  w[9 * F + j] += s3;
-}
-
-// the same for up to GNX_SMALL_BATCH (layer, tower) pairs in one launch (blockIdx.y = pair)
-struct weff_batch_args {
-  const float* W[GNX_SMALL_BATCH];
-  float* out[GNX_SMALL_BATCH];
-  float avg_log[GNX_SMALL_BATCH];
-  int64_t ldw;
-  int F, D;
-};
-
-__global__ void k_pna_weff_batched(weff_batch_args a) {
-  const int b = blockIdx.y;
-  const int F = a.F;
-  int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  int64_t per = (int64_t)F * 4 * F;
-  if (i >= per * a.D) return;
-  int d = (int)(i / per);
-  int o = (int)((i % per) / (4 * F)), j = (int)(i % (4 * F));
-  float dd = (float)d;
-  float amp = logf(dd + 1.0f) / a.avg_log[b];
-  float att = a.avg_log[b] / logf(fmaxf(dd, 1.0f) + 1.0f);
-  const float* w = a.W[b] + (int64_t)o * a.ldw;
-  a.out[b][i] = w[F + j] + amp * w[5 * F + j] + att * w[9 * F + j];
-}
-
-struct weff_bwd_batch_args {
-  const float* dWeff[GNX_SMALL_BATCH];
-  float* dW[GNX_SMALL_BATCH];
-  float avg_log[GNX_SMALL_BATCH];
-  int64_t lddw;
-  int F, D;
-};
-
-__global__ void k_pna_weff_bwd_batched(weff_bwd_batch_args a) {
-  const int b = blockIdx.y;
-  const int F = a.F;
-  int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  int64_t per = (int64_t)F * 4 * F;
-  if (i >= per) return;
-  int o = (int)(i / (4 * F)), j = (int)(i % (4 * F));
-  float s1 = 0.f, s2 = 0.f, s3 = 0.f;
-  const float avg_log = a.avg_log[b];
-  const float* dWeff = a.dWeff[b];
-  for (int d = 0; d < a.D; ++d) {  // same order and expressions as k_pna_weff_bwd
-    float dd = (float)d;
-    float amp = logf(dd + 1.0f) / avg_log;
-    float att = avg_log / logf(fmaxf(dd, 1.0f) + 1.0f);
-    float v = dWeff[(int64_t)d * per + i];
-    s1 += v;
-    s2 += amp * v;
-    s3 += att * v;
-  }
-  float* w = a.dW[b] + (int64_t)o * a.lddw;
-  w[F + j] += s1;
-  w[5 * F + j] += s2;
-  w[9 * F + j] += s3;
-}
-
-extern "C" int32_t gnx_pna_weff_bwd_batched(gnx_handle* h, int32_t n, const float* const* dWeff, int32_t F, int32_t D,
-                                            const float* avg_deg_log, float* const* dW, int64_t lddw) {
-  GNX_CHECK_ARG(h && dWeff && dW && avg_deg_log && n >= 0 && F > 0 && D > 0 && lddw >= 13 * F,
-                "gnx_pna_weff_bwd_batched: bad argument");
-  const int64_t cnt = (int64_t)F * 4 * F;
-  for (int32_t i0 = 0; i0 < n; i0 += GNX_SMALL_BATCH) {
-    weff_bwd_batch_args a;
-    const int m = n - i0 < GNX_SMALL_BATCH ? n - i0 : GNX_SMALL_BATCH;
-    for (int i = 0; i < GNX_SMALL_BATCH; ++i) {
-      const int k = i < m ? i0 + i : i0;
-      a.dWeff[i] = dWeff[k];
-      a.dW[i] = dW[k];
-      a.avg_log[i] = avg_deg_log[k];
-      GNX_CHECK_ARG(a.dWeff[i] && a.dW[i], "gnx_pna_weff_bwd_batched: NULL pointer at %d", k);
-    }
-    a.lddw = lddw;
-    a.F = F;
-    a.D = D;
-    hipLaunchKernelGGL(k_pna_weff_bwd_batched, dim3((unsigned)gnx_cdiv(cnt, 256), (unsigned)m), dim3(256), 0, h->stream, a);
-    GNX_LAUNCH_CHECK();
-  }
-  return GNX_OK;
-}
-
-// W[i] / out[i]: HOST arrays of n device pointers (post_nns[t][0].weight [F,13F] -> Weff [D,F,4F]); avg_log: HOST [n]
-extern "C" int32_t gnx_pna_weff_batched(gnx_handle* h, int32_t n, const float* const* W, int64_t ldw, int32_t F, int32_t D,
-                                        const float* avg_deg_log, float* const* Weff) {
-  GNX_CHECK_ARG(h && W && Weff && avg_deg_log && n >= 0 && F > 0 && D > 0 && ldw >= 13 * F, "gnx_pna_weff_batched: bad argument");
-  const int64_t cnt = (int64_t)F * 4 * F * D;
-  for (int32_t i0 = 0; i0 < n; i0 += GNX_SMALL_BATCH) {
-    weff_batch_args a;
-    const int m = n - i0 < GNX_SMALL_BATCH ? n - i0 : GNX_SMALL_BATCH;
-    for (int i = 0; i < GNX_SMALL_BATCH; ++i) {
-      const int k = i < m ? i0 + i : i0;
-      a.W[i] = W[k];
-      a.out[i] = Weff[k];
-      a.avg_log[i] = avg_deg_log[k];
-      GNX_CHECK_ARG(a.W[i] && a.out[i], "gnx_pna_weff_batched: NULL pointer at %d", k);
-    }
-    a.ldw = ldw;
-    a.F = F;
-    a.D = D;
-    hipLaunchKernelGGL(k_pna_weff_batched, dim3((unsigned)gnx_cdiv(cnt, 256), (unsigned)m), dim3(256), 0, h->stream, a);
-    GNX_LAUNCH_CHECK();
-  }
-  return GNX_OK;
-}
-
-extern "C" int32_t gnx_pna_weff(gnx_handle* h, const float* W, int64_t ldw, int32_t F, int32_t D, float avg_deg_log,
-                                float* Weff) {
-  GNX_CHECK_ARG(h && W && Weff && F > 0 && D > 0 && ldw >= 13 * F, "gnx_pna_weff: bad argument");
-  int64_t n = (int64_t)F * 4 * F * D;
-  hipLaunchKernelGGL(k_pna_weff, dim3((unsigned)gnx_cdiv(n, 256)), dim3(256), 0, h->stream, W, ldw, (int)F, (int)D,
-                     avg_deg_log, Weff);
-  GNX_LAUNCH_CHECK();
-  return GNX_OK;
-}
-
-extern "C" int32_t gnx_pna_weff_bwd(gnx_handle* h, const float* dWeff, int32_t F, int32_t D, float avg_deg_log,
-                                    float* dW, int64_t lddw) {
-  GNX_CHECK_ARG(h && dWeff && dW && F > 0 && D > 0 && lddw >= 13 * F, "gnx_pna_weff_bwd: bad argument");
-  int64_t n = (int64_t)F * 4 * F;
-  hipLaunchKernelGGL(k_pna_weff_bwd, dim3((unsigned)gnx_cdiv(n, 256)), dim3(256), 0, h->stream, dWeff, (int)F, (int)D,
-                     avg_deg_log, dW, lddw);
-  GNX_LAUNCH_CHECK();
-  return GNX_OK;
-}
-
-extern "C" int32_t gnx_gemm_wgrad_batched(gnx_handle* h, int32_t nprob, const gnx_wgrad_prob* probs) {
-  GNX_CHECK_ARG(h && probs && nprob >= 1 && nprob <= WGRAD_MAX_BATCH, "gnx_gemm_wgrad_batched: nprob must be in [1,%d]",
-                WGRAD_MAX_BATCH);
-  wgrad_batch_args b;
-  int64_t maxM = 0;
-  int maxN = 0, maxK = 0;
-  for (int i = 0; i < nprob; ++i) {
-    const gnx_wgrad_prob& q = probs[i];
-    GNX_CHECK_ARG(q.dC && q.A && q.dW && q.M >= 0 && q.N > 0 && q.K > 0 && q.lddc >= q.N && q.lda >= q.K && q.lddw >= q.K,
-                  "gnx_gemm_wgrad_batched: problem %d: bad argument", i);
-    const bool vec = aligned16(q.dC) && (q.lddc % 4 == 0) && aligned16(q.A) && (q.lda % 4 == 0) && (q.N % 4 == 0) &&
-                     (q.K % 4 == 0);
-    GNX_CHECK_ARG(vec, "gnx_gemm_wgrad_batched: problem %d is not 16-byte aligned / multiple-of-4 shaped", i);
-    wgrad_args g;
-    g.X = q.dC;
-    g.ldx = q.lddc;
-    g.Y = q.A;
-    g.ldy = q.lda;
-    g.rs = q.rowscale;
-    g.M = q.M;
-    g.N = q.N;
-    g.K = q.K;
-    g.dW = q.dW;
-    g.lddw = q.lddw;
-    g.dbias = q.dbias;
-    g.vec_x = g.vec_y = 1;
-    g.row_index = nullptr;
-    g.chunk_info = nullptr;
-    g.nchunks = nullptr;
-    g.dw_cls_stride = 0;
-    g.rows_per_block = 0;
-    g.zero = h->d_zero;
-    b.p[i] = g;
-    if (q.M > maxM) maxM = q.M;
-    if (q.N > maxN) maxN = q.N;
-    if (q.K > maxK) maxK = q.K;
-  }
-  for (int i = nprob; i < WGRAD_MAX_BATCH; ++i) b.p[i] = b.p[0];
-  if (maxM == 0) return GNX_OK;
-  // ~1024 workgroups in total, shared out by work (rows x output tiles); every chunk is a multiple of 32 rows
-  double total_cost = 0.0;
-  for (int i = 0; i < nprob; ++i)
-    total_cost += (double)b.p[i].M * (double)(gnx_cdiv(b.p[i].N, BN) * gnx_cdiv(b.p[i].K, BN));
-  int off = 0;
-  for (int i = 0; i < WGRAD_MAX_BATCH; ++i) {
-    b.wg_off[i] = off;
-    b.tiles[i] = 1;
-    b.tiles_k[i] = 1;
-    if (i >= nprob) continue;
-    const int tn = (int)gnx_cdiv(b.p[i].N, BN), tk = (int)gnx_cdiv(b.p[i].K, BN);
-    const int64_t M = b.p[i].M > 0 ? b.p[i].M : 1;
-    // workgroups of the launch: at most one per CU, and at least ~5120 rows of a 128 x 128 output tile each (every
-    // workgroup ends with a 64 KB fp32 atomic flush and, on its CU, displaces the main stream's workgroups: at cfg-2's
-    // 650 k row-tiles per layer 160 workgroups beat 256 by 1.7 % of the step in round 2; with round 3's shorter main
-    // stream 128 beat 160 / 96 / 192 / 256: 6.765 vs 6.836 / 6.932 / 6.880 / 6.880 ms; at cfg-3/4/5's sizes 256 are best)
-    const double cus_d = (double)(h->num_cus > 0 ? h->num_cus : 256);
-    double auto_budget = total_cost / 5120.0;
-    auto_budget = auto_budget < cus_d / 4 ? cus_d / 4 : (auto_budget > cus_d ? cus_d : auto_budget);
-    const double budget = h->opt[GNX_OPT_WGRAD_WGS] > 0 ? (double)h->opt[GNX_OPT_WGRAD_WGS] : auto_budget;
-    int64_t chunks = (int64_t)(budget * ((double)M * tn * tk / total_cost) / (tn * tk) + 0.5);
-    const int64_t max_chunks = gnx_cdiv(M, 128);
-    if (chunks > max_chunks) chunks = max_chunks;
-    if (chunks < 1) chunks = 1;
-    const int64_t rows = gnx_cdiv(gnx_cdiv(M, chunks), BK) * BK;
-    chunks = gnx_cdiv(M, rows);  // no empty chunks
-    b.p[i].rows_per_block = rows;
-    b.tiles[i] = tn * tk;
-    b.tiles_k[i] = tk;
-    off += (int)chunks * tn * tk;
-  }
-  b.wg_off[WGRAD_MAX_BATCH] = off;
-  for (int i = nprob; i < WGRAD_MAX_BATCH; ++i) b.wg_off[i] = off;
-  b.nprob = nprob;
-  dim3 grid((unsigned)off);
-  bool any_rs = false;
-  for (int i = 0; i < nprob; ++i) any_rs = any_rs || probs[i].rowscale != nullptr;
-  double wby = 0.0, wfl = 0.0;
-  for (int i = 0; i < nprob; ++i) {
-    wby += 4.0 * probs[i].M * ((double)probs[i].N + probs[i].K) + 4.0 * probs[i].N * probs[i].K;
-    wfl += 2.0 * (double)probs[i].M * probs[i].N * probs[i].K;
-  }
-  gnx_prof_scope prof(h, GNX_K_GEMM_WGRAD_BATCHED, wby, wfl, wgrad_split_enabled(h, maxM, any_rs) ? 6.0 * wfl : 0.0);
-  if (wgrad_split_enabled(h, maxM, any_rs) && h->opt[GNX_OPT_WGRAD_PIPE] != 0) {
-    static bool attr_set = false;
-    if (!attr_set) {
-      GNX_HIP(wgrad3p_attr(&k_gemm_wgrad3p_batched));
-      attr_set = true;
-    }
-    hipLaunchKernelGGL(k_gemm_wgrad3p_batched, grid, dim3(512), WG3P_LDS, h->stream, b);
-  } else if (wgrad_split_enabled(h, maxM, any_rs))
-    hipLaunchKernelGGL(k_gemm_wgrad3_batched, grid, dim3(256), 0, h->stream, b);
-  else
-    hipLaunchKernelGGL(k_gemm_wgrad_batched, grid, dim3(256), 0, h->stream, b);
-  GNX_LAUNCH_CHECK();
-  return GNX_OK;
-}
-
-// ---------------------------------------------------------------------------------------------------------------
-// Embedding backward on the matrix cores: dTable[r, :] += sum_n onehot[n, r] * dOut[n, :], where onehot[n, r] counts the
-// features k with offs[k] + idx[n,k] == r ([3P] embedding_dense_backward summed over the K tables of an ogb encoder).
-// It is the weight-gradient contraction over rows with a left operand GENERATED from the integer features (exact: the
-// products are by 0/1), so the 10^8 LDS atomic lane-ops of the table-scatter kernel (~2 clk each) become ~5 GFLOP of MFMA.
-// grid = (row chunks, R tiles of 128, H tiles of 128).
-// ---------------------------------------------------------------------------------------------------------------
-#define EMB_MAX_K 12
-struct embed_bwd_args {
-  const int64_t* idx;  // [N, K]
-  int offs[EMB_MAX_K + 1];
-  int K;
-  const float* Y;  // dOut [N, H]
-  int64_t ldy;
-  int64_t N;
-  int R, H;
-  float* dT;  // [R, H]
-  int64_t rows_per_block;
-};
-
-__global__ void __launch_bounds__(256, 2) k_embed_bwd_mfma(embed_bwd_args g) {
-  __shared__ __attribute__((aligned(16))) float Xs[BK * LDN];
-  __shared__ __attribute__((aligned(16))) float Ys[BK * LDN];
-  const int tid = threadIdx.x;
-  const int lane = tid & 63, wave = tid >> 6;
-  const int wm = wave >> 1, wn = wave & 1;
-  const int li = lane & 31, lh = lane >> 5;
-  const int n0 = blockIdx.y * BN;  // table-row tile
-  const int c0 = blockIdx.z * BN;  // channel tile
-  const int64_t r_begin = (int64_t)blockIdx.x * g.rows_per_block;
-  int64_t r_end = r_begin + g.rows_per_block;
-  if (r_end > g.N) r_end = g.N;
-  if (r_begin >= r_end) return;
-
-  f32x16 acc[2][2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-
-  const int br = tid >> 5;
-  const int bc = (tid & 31) * 4;
-  const int yk = c0 + bc;
-  const bool y_ok = yk < g.H;
-  const int yc = y_ok ? yk : 0;
-  f32x4 ry[4];
-  int fr[4][EMB_MAX_K];  // table rows hit by the 4 batch rows this thread stages (raw loads, used at LDS-store time)
-  int okmask = 0;
-
-  auto load_tile = [&](int64_t r0) {
-    okmask = 0;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int64_t pos = r0 + br + 8 * i;
-      const bool rv = pos < r_end;
-      const int64_t row = rv ? pos : r_begin;
-      ry[i] = *reinterpret_cast<const f32x4*>(g.Y + row * g.ldy + yc);
-#pragma unroll
-      for (int k = 0; k < EMB_MAX_K; ++k) fr[i][k] = (int)g.idx[row * g.K + (k < g.K ? k : 0)];  // unconditional
-      okmask |= rv ? (1 << i) : 0;
-    }
-  };
-
-  int64_t r0 = r_begin;
-  load_tile(r0);
-  while (r0 < r_end) {
-    __syncthreads();
-    {
-      const f32x4 z = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const bool rv = (okmask >> i) & 1;
-        f32x4 x = z;
-#pragma unroll
-        for (int k = 0; k < EMB_MAX_K; ++k) {
-          const int span = g.offs[k + 1 <= g.K ? k + 1 : g.K] - g.offs[k < g.K ? k : g.K];
-          const int f = fr[i][k];
-          const int r = g.offs[k < g.K ? k : 0] + f - (n0 + bc);  // position relative to this thread's 4 table rows
-          const bool hit = rv && k < g.K && f >= 0 && f < span;
-          x.x += (hit && r == 0) ? 1.f : 0.f;
-          x.y += (hit && r == 1) ? 1.f : 0.f;
-          x.z += (hit && r == 2) ? 1.f : 0.f;
-          x.w += (hit && r == 3) ? 1.f : 0.f;
-        }
-        const int kr = br + 8 * i;
-        *reinterpret_cast<f32x4*>(&Xs[kr * LDN + bc]) = x;
-        *reinterpret_cast<f32x4*>(&Ys[kr * LDN + bc]) = (rv && y_ok) ? ry[i] : z;
-      }
-    }
-    __syncthreads();
-    r0 += BK;
-    if (r0 < r_end) load_tile(r0);
-#pragma unroll
-    for (int kk = 0; kk < 4; ++kk) {
-      f32x4 a[2], b[2];
-#pragma unroll
-      for (int mi = 0; mi < 2; ++mi) {
-        const float* p = &Xs[(kk * 8 + 4 * lh) * LDN + wm * 64 + mi * 32 + li];
-        a[mi].x = p[0];
-        a[mi].y = p[LDN];
-        a[mi].z = p[2 * LDN];
-        a[mi].w = p[3 * LDN];
-      }
-#pragma unroll
-      for (int ni = 0; ni < 2; ++ni) {
-        const float* p = &Ys[(kk * 8 + 4 * lh) * LDN + wn * 64 + ni * 32 + li];
-        b[ni].x = p[0];
-        b[ni].y = p[LDN];
-        b[ni].z = p[2 * LDN];
-        b[ni].w = p[3 * LDN];
-      }
-#pragma unroll
-      for (int t = 0; t < 4; ++t)
-#pragma unroll
-        for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-          for (int ni = 0; ni < 2; ++ni)
-            acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[mi][t], b[ni][t], acc[mi][ni], 0, 0, 0);
-    }
-  }
-#pragma unroll
-  for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-    for (int ni = 0; ni < 2; ++ni) {
-      const int gc = c0 + wn * 64 + ni * 32 + li;
-      if (gc >= g.H) continue;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int gr = n0 + wm * 64 + mi * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-        if (gr >= g.R) continue;
-        const float v = acc[mi][ni][r];
-        if (v != 0.f) atomicAdd(g.dT + (int64_t)gr * g.H + gc, v);
-      }
-    }
-}
-
-// ---------------------------------------------------------------------------------------------------------------
-// The same gradient on the bf16 matrix pipe (R <= 192 table rows, e.g. the 174 rows of the nine atom-feature tables):
-// the one-hot operand is EXACT in bf16 and is not computed but SCATTERED -- its [table row][batch row] LDS image stays
-// zero except for the K ones per batch row, which the thread that set them clears again after the multiply --, the
-// gradient goes through the three-piece split like every other product (three bf16 MFMAs per slab instead of eight
-// fp32 ones at a sixteenth of the rate: the fp32 kernel above spends 34 of its 107 us in the matrix pipe and most of the
-// rest building the one-hot operand with K x 4 compares per element).  A workgroup owns ALL table rows (six 32-row
-// blocks) x 128 channels (wave w: channels 32 w ..) of a row chunk; 32 batch rows per step; fp32 atomics at the end.
-// ---------------------------------------------------------------------------------------------------------------
-#define EB_R 192
-#define EB_LDX 80   // bytes per image row: 32 batch rows of bf16 + 16 (odd number of 16-byte slots)
-#define EB_X_BYTES (EB_R * EB_LDX)
-#define EB_Y_BYTES (128 * EB_LDX)
-__global__ void __launch_bounds__(256, 2) k_embed_bwd_bf16(embed_bwd_args g) {
-  __shared__ __attribute__((aligned(16))) unsigned char Xs[EB_X_BYTES];       // one-hot  [table row][32 batch rows]
-  __shared__ __attribute__((aligned(16))) unsigned char Ys[3 * EB_Y_BYTES];   // gradient [piece][channel][32 batch rows]
-  const int tid = threadIdx.x;
-  const int lane = tid & 63, wave = tid >> 6;
-  const int li = lane & 31, lh = lane >> 5;
-  const int c0 = blockIdx.y * 128;
-  const int64_t r_begin = (int64_t)blockIdx.x * g.rows_per_block;
-  int64_t r_end = r_begin + g.rows_per_block;
-  if (r_end > g.N) r_end = g.N;
-  if (r_begin >= r_end) return;
-
-  for (int i = tid; i < EB_X_BYTES / 16; i += 256) reinterpret_cast<f32x4*>(Xs)[i] = f32x4{0.f, 0.f, 0.f, 0.f};
-  __syncthreads();  // (the first step's ones are set by other threads than the ones that zeroed their words)
-
-  f32x16 acc[6];
-#pragma unroll
-  for (int i = 0; i < 6; ++i)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[i][r] = 0.f;
-
-  // gradient loader: thread = (channel, 16 batch rows): 4-byte loads, 256 contiguous bytes per wave instruction
-  const int yc = tid & 127, yh = tid >> 7;
-  const bool y_ok = c0 + yc < g.H;
-  // one-hot setter: work item = (batch row, feature): K <= 12 -> at most 384 items, two per thread at most
-  const int nitems = 32 * g.K;
-  int xpos[2] = {-1, -1};
-
-  for (int64_t r0 = r_begin; r0 < r_end; r0 += 32) {
-    float yv[16];
-#pragma unroll
-    for (int j = 0; j < 16; ++j) {
-      const int64_t row = r0 + 16 * yh + j;
-      yv[j] = (y_ok && row < r_end) ? g.Y[row * g.ldy + c0 + yc] : 0.f;
-    }
-    int fi[2];
-#pragma unroll
-    for (int q = 0; q < 2; ++q) {
-      const int it = tid + 256 * q;
-      const int m = it / g.K, k = it - m * g.K;
-      const int64_t row = r0 + m;
-      fi[q] = -1;
-      if (it < nitems && row < r_end) {
-        const int f = (int)g.idx[row * g.K + k];
-        const int span = g.offs[k + 1] - g.offs[k];
-        if (f >= 0 && f < span) fi[q] = (g.offs[k] + f) * EB_LDX + m * 2;  // byte offset of X[table row][m]
-      }
-    }
-    {
-      bf16x8 pc[2][3];
-      float x8[8];
-#pragma unroll
-      for (int hf = 0; hf < 2; ++hf) {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) x8[j] = yv[8 * hf + j];
-        split3(x8, pc[hf][0], pc[hf][1], pc[hf][2]);
-      }
-#pragma unroll
-      for (int p = 0; p < 3; ++p) {
-        unsigned char* q = Ys + p * EB_Y_BYTES + yc * EB_LDX + 32 * yh;
-        *reinterpret_cast<bf16x8*>(q) = pc[0][p];
-        *reinterpret_cast<bf16x8*>(q + 16) = pc[1][p];
-      }
-    }
-#pragma unroll
-    for (int q = 0; q < 2; ++q) {
-      xpos[q] = fi[q];
-      if (fi[q] >= 0) *reinterpret_cast<unsigned short*>(Xs + fi[q]) = 0x3F80;  // bf16 1.0
-    }
-    __syncthreads();
-#pragma unroll
-    for (int sl = 0; sl < 2; ++sl) {
-      bf16x8 b[3];
-#pragma unroll
-      for (int p = 0; p < 3; ++p)
-        b[p] = *reinterpret_cast<const bf16x8*>(Ys + p * EB_Y_BYTES + (wave * 32 + li) * EB_LDX + 32 * sl + 16 * lh);
-#pragma unroll
-      for (int i = 0; i < 6; ++i) {
-        const bf16x8 a = *reinterpret_cast<const bf16x8*>(Xs + (i * 32 + li) * EB_LDX + 32 * sl + 16 * lh);
-        acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b[2], acc[i], 0, 0, 0);
-        acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b[1], acc[i], 0, 0, 0);
-        acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b[0], acc[i], 0, 0, 0);
-      }
-    }
-    __syncthreads();
-#pragma unroll
-    for (int q = 0; q < 2; ++q)
-      if (xpos[q] >= 0) *reinterpret_cast<unsigned short*>(Xs + xpos[q]) = 0;  // (same thread that set it)
-  }
-  const int gc = c0 + wave * 32 + li;
-  if (gc < g.H) {
-#pragma unroll
-    for (int i = 0; i < 6; ++i)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int gr = i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-        const float v = acc[i][r];
-        if (gr < g.R && v != 0.f) atomicAdd(g.dT + (int64_t)gr * g.H + gc, v);
-      }
-  }
-}
-
-// returns GNX_OK after launching, or 1 if the shape is not eligible (caller falls back to the LDS-atomic kernel)
-int32_t gnx_embed_bwd_mfma(gnx_handle* h, const int64_t* idx, int64_t N, int K, const int32_t* offsets, int R,
-                           const float* dout, int H, float* dtable) {
-  if (K > EMB_MAX_K || (H % 4) != 0 || !aligned16(dout) || N < 256) return 1;  // (below 4096 rows the LDS-atomic kernel
-  // is contention-bound: 76 us for a 32-graph batch's 640 atoms, whose feature values repeat in every row)
-  if (h->opt[GNX_OPT_EMBED_BWD_MFMA] == 0) return 1;
-  embed_bwd_args g;
-  g.idx = idx;
-  for (int k = 0; k <= EMB_MAX_K; ++k) g.offs[k] = offsets[k <= K ? k : K];
-  g.K = K;
-  g.Y = dout;
-  g.ldy = H;
-  g.N = N;
-  g.R = R;
-  g.H = H;
-  g.dT = dtable;
-  if (h->opt[GNX_OPT_EMBED_BWD_MFMA] == 1 && R <= EB_R) {  // (2 = the fp32-MFMA kernel below)
-    // ~256 workgroups; at least 128 rows each; small batches: ONE chunk per channel tile (one adder per element: deterministic)
-    int64_t rows = gnx_cdiv(gnx_cdiv(N, (int64_t)(N < 4096 ? 1 : 256)), 32) * 32;
-    if (rows < 128) rows = 128;
-    g.rows_per_block = rows;
-    dim3 grid((unsigned)gnx_cdiv(N, rows), (unsigned)gnx_cdiv(H, 128));
-    hipLaunchKernelGGL(k_embed_bwd_bf16, grid, dim3(256), 0, h->stream, g);
-    GNX_LAUNCH_CHECK();
-    return GNX_OK;
-  }
-  const int64_t tiles = gnx_cdiv(R, BN) * gnx_cdiv(H, BN);
-  int64_t chunks = gnx_cdiv(512, tiles);
-  int64_t rows = gnx_cdiv(gnx_cdiv(N, chunks), BK) * BK;
-  if (rows < 128) rows = 128;
-  if (N < 4096) rows = gnx_cdiv(N, (int64_t)BK) * BK;  // small batches: ONE row chunk per output tile, i.e. one adder per
-                                                       // table element -> a deterministic sum (and 20 K-steps at most)
-  g.rows_per_block = rows;
-  dim3 grid((unsigned)gnx_cdiv(N, rows), (unsigned)gnx_cdiv(R, BN), (unsigned)gnx_cdiv(H, BN));
-  hipLaunchKernelGGL(k_embed_bwd_mfma, grid, dim3(256), 0, h->stream, g);
-  GNX_LAUNCH_CHECK();
-  return GNX_OK;
-}

@@ -297,6 +297,128 @@ extern "C" int32_t gnx_degree_scalers(gnx_handle* h, const int32_t* rowptr, int6
 }
 
 // ---------------------------------------------------------------------------------------------------------------
+// PNA post-layer 0 effective weights per in-degree class d (amp/att depend on d only):
+//   Weff[d][o][j] = W[o][F + j] + amp(d) W[o][5F + j] + att(d) W[o][9F + j],   o < F, j < 4F
+// and the matching weight gradient:  dW[:, F:5F] += sum_d dWeff[d], [:, 5F:9F] += sum_d amp(d) dWeff[d], ...
+// Up to GNX_SMALL_BATCH (layer, tower) pairs per launch (blockIdx.y = pair); gnx_pna_weff(_bwd) is a batch of one.
+// ---------------------------------------------------------------------------------------------------------------
+struct weff_batch_args {
+  const float* W[GNX_SMALL_BATCH];
+  float* out[GNX_SMALL_BATCH];
+  float avg_log[GNX_SMALL_BATCH];
+  int64_t ldw;
+  int F, D;
+};
+
+__global__ void k_pna_weff_batched(weff_batch_args a) {
+  const int b = blockIdx.y;
+  const int F = a.F;
+  int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  int64_t per = (int64_t)F * 4 * F;
+  if (i >= per * a.D) return;
+  int d = (int)(i / per);
+  int o = (int)((i % per) / (4 * F)), j = (int)(i % (4 * F));
+  float dd = (float)d;
+  float amp = logf(dd + 1.0f) / a.avg_log[b];
+  float att = a.avg_log[b] / logf(fmaxf(dd, 1.0f) + 1.0f);
+  const float* w = a.W[b] + (int64_t)o * a.ldw;
+  a.out[b][i] = w[F + j] + amp * w[5 * F + j] + att * w[9 * F + j];
+}
+
+struct weff_bwd_batch_args {
+  const float* dWeff[GNX_SMALL_BATCH];
+  float* dW[GNX_SMALL_BATCH];
+  float avg_log[GNX_SMALL_BATCH];
+  int64_t lddw;
+  int F, D;
+};
+
+__global__ void k_pna_weff_bwd_batched(weff_bwd_batch_args a) {
+  const int b = blockIdx.y;
+  const int F = a.F;
+  int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  int64_t per = (int64_t)F * 4 * F;
+  if (i >= per) return;
+  int o = (int)(i / (4 * F)), j = (int)(i % (4 * F));
+  float s1 = 0.f, s2 = 0.f, s3 = 0.f;
+  const float avg_log = a.avg_log[b];
+  const float* dWeff = a.dWeff[b];
+  for (int d = 0; d < a.D; ++d) {
+    float dd = (float)d;
+    float amp = logf(dd + 1.0f) / avg_log;
+    float att = avg_log / logf(fmaxf(dd, 1.0f) + 1.0f);
+    float v = dWeff[(int64_t)d * per + i];
+    s1 += v;
+    s2 += amp * v;
+    s3 += att * v;
+  }
+  float* w = a.dW[b] + (int64_t)o * a.lddw;
+  w[F + j] += s1;
+  w[5 * F + j] += s2;
+  w[9 * F + j] += s3;
+}
+
+extern "C" int32_t gnx_pna_weff_bwd_batched(gnx_handle* h, int32_t n, const float* const* dWeff, int32_t F, int32_t D,
+                                            const float* avg_deg_log, float* const* dW, int64_t lddw) {
+  GNX_CHECK_ARG(h && dWeff && dW && avg_deg_log && n >= 0 && F > 0 && D > 0 && lddw >= 13 * F,
+                "gnx_pna_weff_bwd_batched: bad argument");
+  const int64_t cnt = (int64_t)F * 4 * F;
+  for (int32_t i0 = 0; i0 < n; i0 += GNX_SMALL_BATCH) {
+    weff_bwd_batch_args a;
+    const int m = n - i0 < GNX_SMALL_BATCH ? n - i0 : GNX_SMALL_BATCH;
+    for (int i = 0; i < GNX_SMALL_BATCH; ++i) {
+      const int k = i < m ? i0 + i : i0;
+      a.dWeff[i] = dWeff[k];
+      a.dW[i] = dW[k];
+      a.avg_log[i] = avg_deg_log[k];
+      GNX_CHECK_ARG(a.dWeff[i] && a.dW[i], "gnx_pna_weff_bwd_batched: NULL pointer at %d", k);
+    }
+    a.lddw = lddw;
+    a.F = F;
+    a.D = D;
+    hipLaunchKernelGGL(k_pna_weff_bwd_batched, dim3((unsigned)gnx_cdiv(cnt, 256), (unsigned)m), dim3(256), 0, h->stream, a);
+    GNX_LAUNCH_CHECK();
+  }
+  return GNX_OK;
+}
+
+// W[i] / out[i]: HOST arrays of n device pointers (post_nns[t][0].weight [F,13F] -> Weff [D,F,4F]); avg_log: HOST [n]
+extern "C" int32_t gnx_pna_weff_batched(gnx_handle* h, int32_t n, const float* const* W, int64_t ldw, int32_t F, int32_t D,
+                                        const float* avg_deg_log, float* const* Weff) {
+  GNX_CHECK_ARG(h && W && Weff && avg_deg_log && n >= 0 && F > 0 && D > 0 && ldw >= 13 * F, "gnx_pna_weff_batched: bad argument");
+  const int64_t cnt = (int64_t)F * 4 * F * D;
+  for (int32_t i0 = 0; i0 < n; i0 += GNX_SMALL_BATCH) {
+    weff_batch_args a;
+    const int m = n - i0 < GNX_SMALL_BATCH ? n - i0 : GNX_SMALL_BATCH;
+    for (int i = 0; i < GNX_SMALL_BATCH; ++i) {
+      const int k = i < m ? i0 + i : i0;
+      a.W[i] = W[k];
+      a.out[i] = Weff[k];
+      a.avg_log[i] = avg_deg_log[k];
+      GNX_CHECK_ARG(a.W[i] && a.out[i], "gnx_pna_weff_batched: NULL pointer at %d", k);
+    }
+    a.ldw = ldw;
+    a.F = F;
+    a.D = D;
+    hipLaunchKernelGGL(k_pna_weff_batched, dim3((unsigned)gnx_cdiv(cnt, 256), (unsigned)m), dim3(256), 0, h->stream, a);
+    GNX_LAUNCH_CHECK();
+  }
+  return GNX_OK;
+}
+
+extern "C" int32_t gnx_pna_weff(gnx_handle* h, const float* W, int64_t ldw, int32_t F, int32_t D, float avg_deg_log,
+                                float* Weff) {
+  GNX_CHECK_ARG(h && W && Weff && F > 0 && D > 0 && ldw >= 13 * F, "gnx_pna_weff: bad argument");
+  return gnx_pna_weff_batched(h, 1, &W, ldw, F, D, &avg_deg_log, &Weff);
+}
+
+extern "C" int32_t gnx_pna_weff_bwd(gnx_handle* h, const float* dWeff, int32_t F, int32_t D, float avg_deg_log,
+                                    float* dW, int64_t lddw) {
+  GNX_CHECK_ARG(h && dWeff && dW && F > 0 && D > 0 && lddw >= 13 * F, "gnx_pna_weff_bwd: bad argument");
+  return gnx_pna_weff_bwd_batched(h, 1, &dWeff, F, D, &avg_deg_log, &dW, lddw);
+}
+
+// ---------------------------------------------------------------------------------------------------------------
 // In-degree classes: nodes stably sorted by in-degree (a deterministic counting sort: per-block histograms -> scan ->
 // stable ranks), and tile tables that never straddle two classes.  Lets PNA's post-layer 0 use one effective weight
 // W_eff(d) = W1 + amp(d) W2 + att(d) W3 per class instead of the 12F-wide scaled operand (amp/att depend on d only).

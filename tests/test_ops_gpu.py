@@ -211,7 +211,8 @@ def test_gemm_segments_rowscale_strided(gpu_device):
 def test_gemm_mid_size_kernel_against_the_tiled_kernel(gpu_device):
     """k_gemm_mid (M < 4096 and <= 48 tiles of 128 x 128: 16 x 16 patches on many workgroups) against the tiled fp32-MFMA
     kernel (GNX_OPT_GEMM_MID = 0) and fp64: a 32-graph batch's shapes (640 atoms, 1 280 bonds), multi-segment, row scale,
-    mask / accumulate, both weight layouts, unaligned views, and the degree-class grouped post-layer-0 pair."""
+    mask / accumulate, both weight layouts, unaligned views, and the degree-class grouped post-layer-0 pair.  At M <= 256
+    the unmasked products with GNX_OPT_GEMM_MID = 0 take the small-product kernel (a batch of one)."""
     from gnnepcsaft_amd import _lib, ops
     dev = torch.device("cuda:0")
 
@@ -226,7 +227,8 @@ def test_gemm_mid_size_kernel_against_the_tiled_kernel(gpu_device):
         return outs
 
     torch.manual_seed(19)
-    for M, N, K in [(640, 128, 128), (1280, 128, 128), (640, 128, 384), (3000, 256, 100), (515, 130, 36)]:
+    for M, N, K in [(640, 128, 128), (1280, 128, 128), (640, 128, 384), (3000, 256, 100), (515, 130, 36), (60, 128, 128),
+                    (200, 36, 300)]:
         a, w, wt = torch.randn(M, K, device=gpu_device), torch.randn(K, N, device=gpu_device), torch.randn(N, K, device=gpu_device)
         b, mask, c0 = torch.randn(N, device=gpu_device), torch.randn(M, N, device=gpu_device), torch.randn(M, N, device=gpu_device)
 
