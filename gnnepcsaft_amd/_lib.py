@@ -10,11 +10,11 @@ import torch
 
 _LIB_PATH = Path(__file__).resolve().parent / "libgnnepcsaft_hip.so"
 
-ABI_VERSION = 5
+ABI_VERSION = 6
 GNX_OK, GNX_E_INVALID, GNX_E_HIP, GNX_E_RANGE, GNX_E_WORKSPACE = 0, -1, -2, -3, -4
 # gnx_set_option ids (include/gnx.h)
-OPT_GEMM_SPLIT, OPT_GEMM_WS, OPT_GEMM_VEC, OPT_WGRAD_VEC, OPT_WGRAD_WGS, OPT_AGG_BWD_RECOMPUTE, OPT_EMBED_BWD_MFMA, \
-    OPT_STD_BWD_CENTERED, OPT_GEMM_PIPE, OPT_WGRAD_PIPE, OPT_EDGE_FUSED, OPT_SIDE_CUS, OPT_GEMM_AS, OPT_GEMM_WS_FAST, OPT_GEMM_TILE_ROWS, OPT_GEMM_MID, OPT_SPLIT_AHEAD = range(17)
+OPT_GEMM_SPLIT, OPT_WGRAD_WGS, OPT_EMBED_BWD_MFMA, OPT_STD_BWD_CENTERED, OPT_GEMM_PIPE, OPT_WGRAD_PIPE, OPT_GEMM_AS, \
+    OPT_GEMM_WS_FAST, OPT_GEMM_TILE_ROWS, OPT_GEMM_MID = range(10)
 GEMM_RELU, GEMM_ACCUMULATE, GEMM_B_TRANS, GEMM_SPLIT_ONLY, GEMM_PRESPLIT = 1, 2, 4, 8, 16
 POOL_ADD, POOL_MEAN, POOL_MAX = 0, 1, 2
 K_NONE, K_PNA_AGG_FWD, K_PNA_AGG_BWD, K_GEMM_WS, K_GEMM_WGRAD, K_GINE_AGG_FWD, K_GINE_AGG_BWD, K_EDGE_COMBINE_FWD, \
@@ -51,6 +51,8 @@ class WgradProb(C.Structure):
 _vp, _i32, _i64, _f32, _sz = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_size_t
 
 PNA_MAX_LAYERS, PNA_MAX_TOWERS = 8, 8
+# gnx_pna_bwd_args.flags (GNX_PNA_BWD_* of include/gnx.h)
+PNA_BWD_DEFER_SMALL, PNA_BWD_LAST_OF_PASS = 1, 2
 
 
 class PnaFwdArgs(C.Structure):
@@ -77,7 +79,7 @@ class PnaBwdArgs(C.Structure):
                 ("params", C.POINTER(_vp)), ("grads", C.POINTER(_vp)), ("dout", _vp),
                 ("gbuf", _vp * PNA_MAX_LAYERS), ("dA", _vp), ("gebuf", _vp * PNA_MAX_LAYERS), ("dP", _vp), ("dQ", _vp),
                 ("dTe", _vp), ("dEE", _vp), ("dWm", _vp), ("dbm", _vp), ("dWeff", _vp), ("ws", _vp), ("ws_bytes", _sz),
-                ("acc_buf", _vp), ("dx", _vp), ("defer_small", _i32), ("etile_w", _i32), ("etile_info", _vp)]
+                ("acc_buf", _vp), ("dx", _vp), ("flags", _i32), ("etile_w", _i32), ("etile_info", _vp)]
 
 
 class PnaFinishArgs(C.Structure):

@@ -144,87 +144,13 @@ extern "C" int32_t gnx_pna_aggregate_fwd(gnx_handle* h, const float* m, const in
 // ---------------------------------------------------------------------------------------------------------------
 // backward: dm[p,c] = dmean/cnt + [m==min] dmin/#ties + [m==max] dmax/#ties + [std>0] dstd (m-mean)/(cnt std)
 // ---------------------------------------------------------------------------------------------------------------
-template <int VEC>
-__global__ void __launch_bounds__(256) k_pna_agg_bwd(const float* __restrict__ dA, const float* __restrict__ m,
-                                                     const float* __restrict__ A, const int* __restrict__ rowptr,
-                                                     int64_t N, int T, int F, float* __restrict__ dm, int centered) {
-  const int H = T * F;
-  const int G = H / VEC;
-  int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= N * G) return;
-  int64_t n = t / G;
-  int c = (int)(t % G) * VEC;
-  int p0 = rowptr[n], p1 = rowptr[n + 1];
-  if (p1 <= p0) return;
-  int tw = c / F, f = c % F;
-  int64_t ao = (n * T + tw) * (int64_t)(4 * F) + f;
-  float mean[VEC], mn[VEC], mx[VEC], sd[VEC], gmean[VEC], gmn[VEC], gmx[VEC], gsd[VEC];
-  vload<VEC>(mean, A + ao);
-  vload<VEC>(mn, A + ao + F);
-  vload<VEC>(mx, A + ao + 2 * F);
-  vload<VEC>(sd, A + ao + 3 * F);
-  vload<VEC>(gmean, dA + ao);
-  vload<VEC>(gmn, dA + ao + F);
-  vload<VEC>(gmx, dA + ao + 2 * F);
-  vload<VEC>(gsd, dA + ao + 3 * F);
-  // torch's scatter_reduce(amin/amax) backward divides by (#src ties + [self == result]) with self = the zero-filled
-  // output buffer, also under include_self=False: an extremum that is exactly 0 counts one extra tie.  The reference's
-  // CPU path behaves that way (verified on torch 2.10: src [0,-1,0] -> grads [1/3,0,1/3]); reproduced here.
-  float nmn[VEC], nmx[VEC], c2[VEC];
-#pragma unroll
-  for (int v = 0; v < VEC; ++v) {
-    nmn[v] = (mn[v] == 0.f) ? 1.f : 0.f;
-    nmx[v] = (mx[v] == 0.f) ? 1.f : 0.f;
-    c2[v] = 0.f;
-  }
-  const float* mp = m + (int64_t)p0 * H + c;
-  for (int p = p0; p < p1; ++p, mp += H) {
-    float a[VEC];
-    vload<VEC>(a, mp);
-#pragma unroll
-    for (int v = 0; v < VEC; ++v) {
-      nmn[v] += (a[v] == mn[v]) ? 1.f : 0.f;
-      nmx[v] += (a[v] == mx[v]) ? 1.f : 0.f;
-      const float dv = a[v] - mean[v];
-      c2[v] = fmaf(dv, dv, c2[v]);
-    }
-  }
-  const float cnt = (float)(p1 - p0);
-  float k_mean[VEC], k_mn[VEC], k_mx[VEC], k_sd[VEC];
-#pragma unroll
-  for (int v = 0; v < VEC; ++v) {
-    k_mean[v] = gmean[v] / cnt;
-    k_mn[v] = gmn[v] / nmn[v];
-    k_mx[v] = gmx[v] / nmx[v];
-    // masked or not is the forward's decision (sd, bit for bit); the divisor is the centred two-pass std, free of the
-    // cancellation error of mean(x^2) - mean(x)^2 (centered = 0: the forward's value, like the CPU path's backward)
-    const float sdiv = (centered && c2[v] > 0.f) ? sqrtf(c2[v] / cnt) : sd[v];
-    k_sd[v] = (sd[v] > 0.f) ? gsd[v] / (cnt * sdiv) : 0.f;
-  }
-  mp = m + (int64_t)p0 * H + c;
-  float* dp = dm + (int64_t)p0 * H + c;
-  for (int p = p0; p < p1; ++p, mp += H, dp += H) {
-    float a[VEC], o[VEC];
-    vload<VEC>(a, mp);
-#pragma unroll
-    for (int v = 0; v < VEC; ++v) {
-      float r = k_mean[v] + k_sd[v] * (a[v] - mean[v]);
-      r += (a[v] == mn[v]) ? k_mn[v] : 0.f;
-      r += (a[v] == mx[v]) ? k_mx[v] : 0.f;
-      o[v] = r;
-    }
-    vstore<VEC>(dp, o);
-  }
-}
-
-
-// Variant that does not read the saved aggregate A: mean / min / max / std are recomputed from the message rows with the
-// forward's exact arithmetic (same bits, so the std mask decision is identical), which drops 16NH bytes of reads — the
-// rows of one destination (<= a few KB) are re-read from L1/L2 by the tie-count and write passes.
+// The saved aggregate A is not read: mean / min / max / std are recomputed from the message rows with the forward's exact
+// arithmetic (same bits, so the std mask decision is identical), which drops 16NH bytes of reads against a two-pass kernel
+// that takes them from A -- the rows of one destination (<= a few KB) are re-read from L1/L2 by the tie-count and write passes.
 template <int VEC>
 __global__ void __launch_bounds__(256) k_pna_agg_bwd_rc(const float* __restrict__ dA, const float* __restrict__ m,
                                                         const int* __restrict__ rowptr, int64_t N, int T, int F,
-                                                        float* __restrict__ dm, int centered, int small_deg) {
+                                                        float* __restrict__ dm, int centered) {
   const int H = T * F;
   const int G = H / VEC;
   int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -253,7 +179,7 @@ __global__ void __launch_bounds__(256) k_pna_agg_bwd_rc(const float* __restrict_
   // (the same treatment of k_edge_combine_bwd's dQ gather and of k_gine_fwd / k_gine_bwd_dx -- indices, then rows, four at a time
   // -- was measured and rejected: cfg-3 20.15-20.23 vs 19.99-20.00 ms, cfg-2 neutral; those kernels sit at 0.76 of HBM with
   // one row in flight per thread and lose more occupancy to the 32 extra VGPRs than the loads gain)
-  if (small_deg && p1 - p0 <= 4) {
+  if (p1 - p0 <= 4) {
     // in-degree <= 4 (every atom of an organic molecule): the row's messages are loaded ONCE, all four loads in flight
     // together (clamped addresses past the row's end), and the three passes run on registers -- same operations in the
     // same order per element as the loops below
@@ -343,7 +269,10 @@ __global__ void __launch_bounds__(256) k_pna_agg_bwd_rc(const float* __restrict_
     float var = __fsub_rn(mean2, __fmul_rn(mean[v], mean[v]));
     float o = __fsqrt_rn(fmaxf(var, STD_VAR_MIN));
     sd[v] = (o <= STD_MASK_AT) ? 0.f : o;
-    nmn[v] = (mn[v] == 0.f) ? 1.f : 0.f;  // torch's zero-filled self counts as a tie (see k_pna_agg_bwd)
+    // torch's scatter_reduce(amin/amax) backward divides by (#src ties + [self == result]) with self = the zero-filled
+    // output buffer, also under include_self=False: an extremum that is exactly 0 counts one extra tie.  The reference's
+    // CPU path behaves that way (verified on torch 2.10: src [0,-1,0] -> grads [1/3,0,1/3]); reproduced here.
+    nmn[v] = (mn[v] == 0.f) ? 1.f : 0.f;
     nmx[v] = (mx[v] == 0.f) ? 1.f : 0.f;
   }
   mp = m + (int64_t)p0 * H + c;
@@ -392,29 +321,12 @@ extern "C" int32_t gnx_pna_aggregate_bwd(gnx_handle* h, const float* dA, const f
   if (N == 0) return GNX_OK;
   // read the aggregate gradient 16NH, re-read the messages 4EH + index 4E, write the message gradient 4EH
   gnx_prof_scope prof(h, GNX_K_PNA_AGG_BWD, 16.0 * N * T * F + 8.0 * E * T * F + 4.0 * E, 0.0, 0.0, true);
-  {
-    if (h->opt[GNX_OPT_AGG_BWD_RECOMPUTE] != 0) {
-      if (F % 4 == 0)
-        GNX_LAUNCH_TIMED(prof, k_pna_agg_bwd_rc<4>, dim3((unsigned)gnx_cdiv(N * (T * F / 4), 256)), dim3(256), 0,
-                         h->stream, dA, m, rowptr, N, (int)T, (int)F, dm, h->opt[GNX_OPT_STD_BWD_CENTERED],
-                         h->opt[GNX_OPT_AGG_BWD_RECOMPUTE] == 1 ? 1 : 0);
-      else
-        GNX_LAUNCH_TIMED(prof, k_pna_agg_bwd_rc<1>, dim3((unsigned)gnx_cdiv(N * (int64_t)(T * F), 256)), dim3(256), 0,
-                         h->stream, dA, m, rowptr, N, (int)T, (int)F, dm, h->opt[GNX_OPT_STD_BWD_CENTERED],
-                         h->opt[GNX_OPT_AGG_BWD_RECOMPUTE] == 1 ? 1 : 0);
-      GNX_LAUNCH_CHECK();
-      return GNX_OK;
-    }
-  }
-  if (F % 4 == 0) {
-    int64_t th = N * (T * F / 4);
-    GNX_LAUNCH_TIMED(prof, k_pna_agg_bwd<4>, dim3((unsigned)gnx_cdiv(th, 256)), dim3(256), 0, h->stream, dA, m, A, rowptr,
-                     N, (int)T, (int)F, dm, h->opt[GNX_OPT_STD_BWD_CENTERED]);
-  } else {
-    int64_t th = N * (T * F);
-    GNX_LAUNCH_TIMED(prof, k_pna_agg_bwd<1>, dim3((unsigned)gnx_cdiv(th, 256)), dim3(256), 0, h->stream, dA, m, A, rowptr,
-                     N, (int)T, (int)F, dm, h->opt[GNX_OPT_STD_BWD_CENTERED]);
-  }
+  if (F % 4 == 0)
+    GNX_LAUNCH_TIMED(prof, k_pna_agg_bwd_rc<4>, dim3((unsigned)gnx_cdiv(N * (T * F / 4), 256)), dim3(256), 0, h->stream, dA, m,
+                     rowptr, N, (int)T, (int)F, dm, h->opt[GNX_OPT_STD_BWD_CENTERED]);
+  else
+    GNX_LAUNCH_TIMED(prof, k_pna_agg_bwd_rc<1>, dim3((unsigned)gnx_cdiv(N * (int64_t)(T * F), 256)), dim3(256), 0, h->stream, dA,
+                     m, rowptr, N, (int)T, (int)F, dm, h->opt[GNX_OPT_STD_BWD_CENTERED]);
   GNX_LAUNCH_CHECK();
   return GNX_OK;
 }

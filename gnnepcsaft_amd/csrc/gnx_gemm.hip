@@ -1768,15 +1768,13 @@ static int32_t gemm_ws_launch(gnx_handle* h, const gnx_gemm_seg& s, int64_t M, i
 }
 
 // eligibility of the weights-stationary path (everything else goes to the tiled kernel)
-static bool gemm_ws_eligible(const gnx_handle* h, int32_t nseg, const gnx_gemm_seg* segs, int64_t M, int32_t N,
-                             const float* mask, int32_t flags) {
+static bool gemm_ws_eligible(int32_t nseg, const gnx_gemm_seg* segs, int64_t M, int32_t N, const float* mask, int32_t flags) {
   if (nseg != 1 || M < 8192) return false;
   const gnx_gemm_seg& s = segs[0];
   if (s.rowscale != nullptr || s.k > 128 || s.k < 32 || N > 128 || N < 32) return false;
   if ((s.k % 4) != 0 || (N % 4) != 0) return false;
   if (!aligned16(s.a) || (s.lda % 4) != 0 || !aligned16(s.b) || (s.ldb % 4) != 0) return false;
-  if (mask != nullptr && (flags & GNX_GEMM_ACCUMULATE)) return false;
-  return h->opt[GNX_OPT_GEMM_WS] != 0;
+  return !(mask != nullptr && (flags & GNX_GEMM_ACCUMULATE));
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -2038,8 +2036,8 @@ static size_t gemm_split_bytes(const gnx_handle* h, int32_t nseg, const gnx_gemm
                                int32_t num_classes, int64_t M, int32_t N, const float* mask, int32_t flags,
                                bool grouped) {
   if (h == nullptr || segs == nullptr || nseg < 1 || nseg > MAX_SEGS || M < 4096 || N <= 0) return 0;
-  if (h->opt[GNX_OPT_GEMM_SPLIT] == 0 || h->opt[GNX_OPT_GEMM_VEC] == 0) return 0;
-  if (!grouped && gemm_ws_eligible(h, nseg, segs, M, N, mask, flags)) return 0;  // weights live in registers there
+  if (h->opt[GNX_OPT_GEMM_SPLIT] == 0) return 0;
+  if (!grouped && gemm_ws_eligible(nseg, segs, M, N, mask, flags)) return 0;  // weights live in registers there
   const bool bt = (flags & GNX_GEMM_B_TRANS) != 0;
   int64_t kpad = 0;
   int ksteps = 0;
@@ -2102,7 +2100,7 @@ static int32_t gemm_launch(gnx_handle* h, int32_t nseg, const gnx_gemm_seg* segs
     GNX_CHECK_ARG(bt ? in.ldb >= in.k : in.ldb >= N, "gnx_gemm: segment %d: ldb too small", s);
   }
   const bool split_only = (flags & GNX_GEMM_SPLIT_ONLY) != 0;  // only the weight images (if this call uses any) are written
-  if (tile_info == nullptr && gemm_ws_eligible(h, nseg, segs, M, N, mask, flags))
+  if (tile_info == nullptr && gemm_ws_eligible(nseg, segs, M, N, mask, flags))
     return split_only ? GNX_OK : gemm_ws_launch(h, segs[0], M, N, bias, mask, ldmask, C, ldc, flags);
   if (split_only && M < 4096) return GNX_OK;  // (no split path below 4096 rows)
   if (tile_info == nullptr && nseg == 1 && M <= 256 && mask == nullptr && segs[0].rowscale == nullptr &&
@@ -2170,7 +2168,7 @@ static int32_t gemm_launch(gnx_handle* h, int32_t nseg, const gnx_gemm_seg* segs
   bool pipe = h->opt[GNX_OPT_GEMM_PIPE] != 0;  // decided below: needs >= G3P_MIN_KTILES K-tiles per output tile
   bool as3 = false;                            // decided below: one segment, 4 K-tiles, >= 2 column tiles
   bool mi3 = false;                            // pipelined kernel with 96-row tiles
-  bool vec = h->opt[GNX_OPT_GEMM_VEC] != 0;
+  bool vec = true;
   for (int s = 0; s < nseg; ++s)
     vec = vec && g.seg[s].vec_a && g.seg[s].vec_b && (g.seg[s].k % 4 == 0) && (bt || (N % 4 == 0));
   // Split-operand path (M >= 4096, >= 2 K-tiles, no row scale): needs the caller's workspace for the split weight

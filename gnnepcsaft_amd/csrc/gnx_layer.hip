@@ -80,8 +80,8 @@ int32_t on_side(gnx_handle* h, int which, bool enabled, F body) {
 // upper bound of the split-weight images any product of the layer's forward or backward needs (gnx_gemm_workspace_bytes): the
 // degree-class product dA = g Weff(d) (D classes, N = 4F, K = F) and the 3-segment dx product (N = F, K = 3F)
 // Layout of the workspace: [0, scratch) is reused by every product of the layer in turn; behind it one region per tower and
-// per tiled product whose weight images are split AHEAD on side stream 2 (GNX_OPT_SPLIT_AHEAD): forward: post-layer 0;
-// backward: dA and dx.
+// per tiled product whose weight images are split AHEAD on side stream 2 (layers with two or more towers, see
+// gnx_pna_conv_fwd): forward: post-layer 0; backward: dA and dx.
 static size_t align256(size_t v) { return (v + 255) / 256 * 256; }
 static void pna_ws_sizes(int32_t T, int32_t F, int32_t D, size_t& scratch, size_t& post0, size_t& grouped, size_t& dx) {
   auto pad = [](int64_t v, int64_t m) { return (v + m - 1) / m * m; };
@@ -119,8 +119,8 @@ extern "C" int32_t gnx_pna_conv_bwd(gnx_handle* h, const gnx_pna_bwd_args* a) {
   // the weight images of the two tiled products of this backward (dA per degree class, the 3-segment dx) are split on side
   // stream 2 while the lin / hidden input-gradient products run; the products take them as they are (GNX_GEMM_PRESPLIT)
   size_t scratch = a->ws_bytes, r_post0 = 0, r_dA = 0, r_dx = 0;
-  bool ahead = (h->opt[GNX_OPT_SPLIT_AHEAD] == 2 || (h->opt[GNX_OPT_SPLIT_AHEAD] == 1 && T >= 2)) && a->use_side_streams != 0 &&
-               !h->on_side && N >= 4096 && a->ws != nullptr;
+  // (for layers with two or more towers only: the measurement is at the same choice in gnx_pna_conv_fwd)
+  bool ahead = T >= 2 && side && !h->on_side && N >= 4096 && a->ws != nullptr;
   if (ahead) {
     pna_ws_sizes(T, F, D, scratch, r_post0, r_dA, r_dx);
     ahead = scratch + (size_t)T * (r_dA + r_dx) <= a->ws_bytes;
@@ -158,11 +158,13 @@ extern "C" int32_t gnx_pna_conv_bwd(gnx_handle* h, const gnx_pna_bwd_args* a) {
   float* g = a->gbuf[gi];
   const float* z_last = a->zs[a->n_z - 1];
   int last_hidden;
-  const bool tail = (a->defer_small & 2) != 0;   // nothing follows this layer on the main stream (see the flush below)
-  const bool class_after_agg = (a->defer_small & 8) != 0 && side;  // per-class weight gradient forked behind the aggregate backward
+  const bool tail = (a->flags & GNX_PNA_BWD_LAST_OF_PASS) != 0;  // nothing follows this layer on the main stream (see the flush below)
+  const bool defer = (a->flags & GNX_PNA_BWD_DEFER_SMALL) != 0;  // small accumulators pre-zeroed by the caller, their consumers
+                                                                 // run in gnx_pna_stack_finish for all layers at once
+  // with side streams the per-class weight gradients of post-layer 0 are forked BEHIND the aggregate backward, not in front of
+  // it (a memory-bound kernel they slow down a lot: 135 us beside them, 55 alone): 6.640 -> 6.609 ms, cfg-5 55.88 -> 55.63; at
+  // the END of the layer they were worse (6.662 vs 6.579)
   std::vector<std::function<int32_t()>> class_wgrads;
-  const bool defer = (a->defer_small & 1) != 0;  // small accumulators pre-zeroed by the caller, their consumers run in
-                                           // gnx_pna_stack_finish for all layers at once
   if (a->merged) {
     if (!defer) {
       GNX_TRY(gnx_fill(h, a->dWm, (int64_t)H * H, 0.f));
@@ -203,10 +205,10 @@ extern "C" int32_t gnx_pna_conv_bwd(gnx_handle* h, const gnx_pna_bwd_args* a) {
                                      a->chunks, a->nchunks, a->max_chunks));
       return defer ? GNX_OK : gnx_pna_weff_bwd(h, dWeff, F, D, a->avg_deg_log, dWp, 13 * F);
     };
-    if (class_after_agg)
+    if (side)
       class_wgrads.push_back(class_wgrad);
     else
-      GNX_TRY(on_side(h, 0, side, class_wgrad));
+      GNX_TRY(class_wgrad());
     if (ahead) {
       if (t == 0) GNX_TRY(gnx_side_join_n(h, 2));
       GNX_TRY(dA_call(t, gt, GNX_GEMM_PRESPLIT, ahead_base + (size_t)t * (r_dA + r_dx), r_dA));
@@ -215,9 +217,8 @@ extern "C" int32_t gnx_pna_conv_bwd(gnx_handle* h, const gnx_pna_bwd_args* a) {
     }
   }
   const float* g_post0 = g;  // gradient w.r.t. post-layer 0's output: also an operand of dx below
-  // the last layer of the pass: the weight gradients queued so far (lin, hidden post layers, x part of post-layer 0) go out
-  // NOW, beside the edge backward, so that only the pre-layer ones are left for the end of the step
-  if (tail && side && (a->defer_small & 4) != 0) GNX_TRY(on_side(h, 0, side, [&]() -> int32_t { return wq.flush(h); }));
+  // (the last layer of the pass keeps the weight gradients queued so far for the end of the layer as well: launched HERE,
+  // beside the edge backward, they compete with it on the main stream: 6.612 vs 6.554 ms)
   // ---- scatter-aggregate backward, then the pre layers last..1
   int ei = 0;
   float* ge = a->gebuf[ei];
@@ -225,7 +226,7 @@ extern "C" int32_t gnx_pna_conv_bwd(gnx_handle* h, const gnx_pna_bwd_args* a) {
   for (auto& fn : class_wgrads) GNX_TRY(on_side(h, 0, side, fn));
   // With two pre layers (the reference's default) the masked input gradient of pre-layer 1, the destination sums dP and the
   // bond-table sums dTe come from ONE pass over the message gradient (gnx_pna_edge_bwd); only dQ is a pass of its own.
-  bool fused_bwd = h->opt[GNX_OPT_EDGE_FUSED] == 1 && pre == 2 && a->etile_info != nullptr && E > 0 && F % 4 == 0 && F <= 128 &&
+  bool fused_bwd = pre == 2 && a->etile_info != nullptr && E > 0 && F % 4 == 0 && F <= 128 &&
                    R <= 64 && a16(ge) && a16(a->hs[0]) && a16(a->gebuf[1]) && a16(a->dP) && a16(a->dTe);
   for (int t = 0; t < T && fused_bwd; ++t) fused_bwd = a16(P[pidx(t, true, 1)]);
   if (fused_bwd) {
@@ -259,18 +260,18 @@ extern "C" int32_t gnx_pna_conv_bwd(gnx_handle* h, const gnx_pna_bwd_args* a) {
     wq.add(a->dP + t * F, H, a->x + t * F, H, N, F, F, dW0, 3 * F, nullptr);
     wq.add(a->dQ + t * F, H, a->x + t * F, H, N, F, F, dW0 + F, 3 * F, nullptr);
   }
-  // the queue is complete: with defer_small bit 4 the batched weight gradients start HERE, beside the dx product (matrix-
-  // bound), instead of behind it, beside the next layer's BatchNorm backward (memory-bound)
+  // the queue is complete: with side streams the batched weight gradients start HERE, beside the dx product (matrix-bound),
+  // instead of behind it, beside the next layer's BatchNorm backward (memory-bound): 6.578 -> 6.541 ms, cfg-5 56.03 -> 55.90
   auto flush_batched = [&]() -> int32_t {
     // the LAST layer of a backward pass has the chip to itself: its batched weight gradients take every CU instead of the
-    // workgroup budget that leaves room for the main stream (the end of a step waits for exactly this launch)
+    // workgroup budget that leaves room for the main stream (the end of a step waits for exactly this launch): 6.760 -> 6.687 ms
     const int wgs_saved = h->opt[GNX_OPT_WGRAD_WGS];
     if (tail && wgs_saved == 0) h->opt[GNX_OPT_WGRAD_WGS] = h->num_cus > 0 ? h->num_cus : 256;
     const int32_t fst = wq.flush(h);
     h->opt[GNX_OPT_WGRAD_WGS] = wgs_saved;
     return fst;
   };
-  const bool flush_before_dx = (a->defer_small & 16) != 0 && side && !tail;
+  const bool flush_before_dx = side && !tail;
   if (flush_before_dx) GNX_TRY(on_side(h, 0, side, flush_batched));
   for (int t = 0; t < T; ++t) {
     if (ahead)
@@ -375,10 +376,9 @@ extern "C" int32_t gnx_pna_conv_fwd(gnx_handle* h, const gnx_pna_fwd_args* a) {
   const int post0_flags = GNX_GEMM_B_TRANS | (post > 1 ? GNX_GEMM_RELU : 0);
   const int post0_rows = a->tile_rows == 96 ? 96 : 128;
   size_t scratch = a->ws_bytes, r_post0 = 0, r_grouped = 0, r_dx = 0;
-  // (measured: cfg-5, four towers = twelve splits per layer: -0.44 ms per step; cfg-2, one tower: +0.02 ms -- the fork / join
-  // events cost what the three 7-us splits saved -- so: 1 = with two or more towers, 2 = always, 0 = never)
-  bool ahead = (h->opt[GNX_OPT_SPLIT_AHEAD] == 2 || (h->opt[GNX_OPT_SPLIT_AHEAD] == 1 && T >= 2)) && !h->on_side && N >= 4096 &&
-               a->ws != nullptr;
+  // (measured: cfg-5, four towers = twelve splits per layer: 56.79 -> 56.35 ms per step; cfg-2, one tower: 6.608 -> 6.630 ms --
+  // the fork / join events cost what the three 7-us splits saved -- so: ahead with two or more towers, in place with one)
+  bool ahead = T >= 2 && !h->on_side && N >= 4096 && a->ws != nullptr;
   if (ahead) {
     pna_ws_sizes(T, F, D, scratch, r_post0, r_grouped, r_dx);
     ahead = scratch + (size_t)T * r_post0 <= a->ws_bytes;
@@ -408,7 +408,7 @@ extern "C" int32_t gnx_pna_conv_fwd(gnx_handle* h, const gnx_pna_fwd_args* a) {
   }
   // edge pipeline: message assembly -> pre layers 1.. -> scatter-aggregate.  With two pre layers (the reference's default)
   // it is ONE launch (gnx_pna_edge_fwd: h1 and the messages are written once and never read back, bit-identical results)
-  bool fused = h->opt[GNX_OPT_EDGE_FUSED] != 0 && pre == 2 && a->etile_info != nullptr && E > 0 && F % 4 == 0 && F <= 128 &&
+  bool fused = pre == 2 && a->etile_info != nullptr && E > 0 && F % 4 == 0 && F <= 128 &&
                a16(a->P) && a16(a->Q) && a16(a->Te) && a16(a->hs[0]) && a16(a->hs[1]) && a16(a->A);
   const float* W1[GNX_PNA_MAX_TOWERS];
   const float* b1[GNX_PNA_MAX_TOWERS];

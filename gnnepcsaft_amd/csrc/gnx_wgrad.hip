@@ -663,8 +663,7 @@ static int32_t wgrad_launch(gnx_handle* h, const float* dC, int64_t lddc, const 
   g.nchunks = nchunks;
   g.dw_cls_stride = dw_cls_stride;
   dim3 grid((unsigned)(chunk_info ? max_chunks : gnx_cdiv(M, rows)), (unsigned)gnx_cdiv(N, BN), (unsigned)gnx_cdiv(K, BN));
-  bool vec = g.vec_x && g.vec_y && (N % 4 == 0) && (K % 4 == 0);
-  if (h->opt[GNX_OPT_WGRAD_VEC] == 0) vec = false;
+  const bool vec = g.vec_x && g.vec_y && (N % 4 == 0) && (K % 4 == 0);
   const bool offs32 = (uint64_t)M * (uint64_t)lddc < (1ull << 32) && (uint64_t)M * (uint64_t)lda < (1ull << 32);
   const bool wsplit = wgrad_split_enabled(h, M, rowscale != nullptr) && (!chunk_info || offs32);
   const double wfl = 2.0 * (double)M * N * K;

@@ -14,55 +14,50 @@ from . import ops
 from .ops import GraphPack
 
 
-_GRAD_IN_PLACE = False
-_USE_DEGREE_CLASSES = True
-_MERGE_LAST_POST = True
-_PREPARE_AHEAD = True
+# ---- module switches (plain module state; each has a setter and a read accessor) -------------------------------------
+_GRAD_IN_PLACE = False      # bench.py, train/trainer.py, dp.py: gradients accumulate straight into param.grad
+_USE_DEGREE_CLASSES = True  # bench.py, tests: off = the 4-segment post-layer 0, the reference of the degree-class form
+_NATIVE_LAYER_BWD = True    # tests: off = PNAConv launch by launch from Python, the reference of the native calls
+_FUSED_EDGE = True          # tests: off = the three-launch edge pipeline, the reference of the fused edge kernels
+_BATCH_WEIGHT_ONLY = True   # tests: off = per-layer weight-only work (WeightOnlyAhead), the reference of the batched form
 
 
-def set_merge_last_post(enabled: bool) -> None:
-    """A/B switch: PNA's last post layer and ``lin`` as ONE product with a merged H x H weight (default on)."""
-    global _MERGE_LAST_POST
-    _MERGE_LAST_POST = bool(enabled)
+def set_grad_in_place(enabled: bool) -> None:
+    """Opt-in: weight-gradient kernels accumulate (+=) straight into an existing ``param.grad`` (e.g. the views of
+    ``dp.FlatGradAllReduce``'s flat buffer) and the Functions return ``None`` for those parameters, instead of
+    materialising a zero-filled gradient per parameter per layer for autograd to add.  Same result as autograd's own
+    accumulation for the usual ``loss.backward()`` loop; leave it off when calling ``torch.autograd.grad``."""
+    global _GRAD_IN_PLACE
+    _GRAD_IN_PLACE = bool(enabled)
 
 
-def set_prepare_ahead(enabled: bool) -> None:
-    """A/B switch: the model issues a PNA layer's weight-only launches one layer ahead on the side stream (default on)."""
-    global _PREPARE_AHEAD
-    _PREPARE_AHEAD = bool(enabled)
+def grad_in_place_enabled() -> bool:
+    return _GRAD_IN_PLACE
 
 
-def prepare_ahead_enabled() -> bool:
-    return _PREPARE_AHEAD
+def set_degree_classes(enabled: bool) -> None:
+    """A/B switch for PNA's per-degree-class post-layer 0 (default on; off = the 4-segment 13F-wide product)."""
+    global _USE_DEGREE_CLASSES
+    _USE_DEGREE_CLASSES = bool(enabled)
 
 
-_BOND_CHAIN_ASIDE = True
-_NATIVE_LAYER_BWD = True
-_FUSED_EDGE = True
-_CLASS_WGRAD_AFTER_AGG = True  # the per-class weight gradient starts behind the aggregate backward, not beside it: 6.640 -> 6.609 ms,
-#                                cfg-5 55.88 -> 55.63 (tools/ab_bench.py classearly); at the END of the layer it was worse (6.662 vs 6.579)
-_WGRAD_FLUSH_BEFORE_DX = True  # the batched weight gradients of a layer start in front of its dx product: 6.578 -> 6.541 ms, cfg-5
-#                                56.03 -> 55.90 (tools/ab_bench.py flushlate)
-_TAIL_WGRAD_ALL_CUS = True  # A/B switch: layer 0's batched weight gradients on every CU (tools/ab_bench.py notail)
-_TAIL_WGRAD_EARLY = False   # ... and its post-layer ones launched before the edge backward: measured 6.612 vs 6.554 ms (they
-#                             compete with the edge backward on the main stream), off
+def degree_classes_enabled() -> bool:
+    return _USE_DEGREE_CLASSES
 
 
-def set_class_wgrad_after_agg(on: bool) -> None:
-    global _CLASS_WGRAD_AFTER_AGG
-    _CLASS_WGRAD_AFTER_AGG = bool(on)
+def set_native_layer_backward(enabled: bool) -> None:
+    """A/B switch: PNAConv's backward as ONE native call (gnx_pna_conv_bwd: the same launches issued from C++, ~0.09
+    instead of ~0.32 ms of host time per layer) whenever its preconditions hold; off = launch by launch from Python."""
+    global _NATIVE_LAYER_BWD
+    _NATIVE_LAYER_BWD = bool(enabled)
 
 
-def set_wgrad_flush_before_dx(on: bool) -> None:
-    global _WGRAD_FLUSH_BEFORE_DX
-    _WGRAD_FLUSH_BEFORE_DX = bool(on)
-
-
-def set_tail_wgrad_all_cus(on: bool, early: bool = False) -> None:
-    global _TAIL_WGRAD_ALL_CUS, _TAIL_WGRAD_EARLY
-    _TAIL_WGRAD_ALL_CUS, _TAIL_WGRAD_EARLY = bool(on), bool(early)
-
-_BATCH_WEIGHT_ONLY = True
+def set_fused_edge(enabled: bool) -> None:
+    """A/B switch: PNAConv's edge pipeline (message assembly -> pre-layer 1 -> aggregate) as one fused kernel when the
+    layer has two pre layers and the batch's in-degree bound admits edge tiles (default on; bit-identical results).  Off =
+    no edge-tile table is passed and the library takes the three-launch sequence in both directions."""
+    global _FUSED_EDGE
+    _FUSED_EDGE = bool(enabled)
 
 
 def set_batch_weight_only(enabled: bool) -> None:
@@ -75,47 +70,6 @@ def set_batch_weight_only(enabled: bool) -> None:
 
 def batch_weight_only_enabled() -> bool:
     return _BATCH_WEIGHT_ONLY
-
-
-def set_fused_edge(enabled: bool) -> None:
-    """A/B switch: PNAConv's edge pipeline (message assembly -> pre-layer 1 -> aggregate) as one fused kernel when the
-    layer has two pre layers and the batch's in-degree bound admits edge tiles (default on; bit-identical results)."""
-    global _FUSED_EDGE
-    _FUSED_EDGE = bool(enabled)
-
-
-
-def set_native_layer_backward(enabled: bool) -> None:
-    """A/B switch: PNAConv's backward as ONE native call (gnx_pna_conv_bwd: the same launches issued from C++, ~0.09
-    instead of ~0.32 ms of host time per layer) whenever its preconditions hold; off = launch by launch from Python."""
-    global _NATIVE_LAYER_BWD
-    _NATIVE_LAYER_BWD = bool(enabled)
-
-
-def set_bond_chain_aside(enabled: bool) -> None:
-    """A/B switch: PNA layers accumulate the bond-embedding gradient into one shared buffer on side stream 1 (default
-    on); off = every layer computes it on the main stream and autograd sums the layers' contributions."""
-    global _BOND_CHAIN_ASIDE
-    _BOND_CHAIN_ASIDE = bool(enabled)
-
-
-def bond_chain_aside_enabled() -> bool:
-    return _BOND_CHAIN_ASIDE
-
-
-def set_degree_classes(enabled: bool) -> None:
-    """A/B switch for PNA's per-degree-class post-layer 0 (default on; off = the 4-segment 13F-wide product)."""
-    global _USE_DEGREE_CLASSES
-    _USE_DEGREE_CLASSES = bool(enabled)
-
-
-def set_grad_in_place(enabled: bool) -> None:
-    """Opt-in: weight-gradient kernels accumulate (+=) straight into an existing ``param.grad`` (e.g. the views of
-    ``dp.FlatGradAllReduce``'s flat buffer) and the Functions return ``None`` for those parameters, instead of
-    materialising a zero-filled gradient per parameter per layer for autograd to add.  Same result as autograd's own
-    accumulation for the usual ``loss.backward()`` loop; leave it off when calling ``torch.autograd.grad``."""
-    global _GRAD_IN_PLACE
-    _GRAD_IN_PLACE = bool(enabled)
 
 
 def grad_sinks(params: Sequence[torch.Tensor]) -> tuple:
@@ -305,7 +259,7 @@ def _pna_weight_only(BE, T, F, pre_layers, post_layers, avg_deg_log, params, D):
     ungrouped): EE = BondEmb W_enc^T + b_enc [R,F];  Te = per tower EE W_e^T + b (the edge part of pre-layer 0 on the
     60-row bond table) [R,H];  Weff(d) per tower;  the merged (lin o last post layer) weight / bias."""
     R, H = BE.size(0), T * F
-    merged = post_layers > 1 and _MERGE_LAST_POST
+    merged = post_layers > 1  # the last post layer and ``lin`` as ONE product with a merged H x H weight (see forward)
     if _NATIVE_LAYER_BWD and BE.is_cuda and T <= 8:
         # one native call (gnx_pna_weight_only) instead of 5 + 3 (T - 1) launches from Python
         import ctypes as C
@@ -458,7 +412,7 @@ class WeightOnlyAll:
         from . import _lib
         self.device = BE.device
         L, R, H = len(layers), BE.size(0), T * F
-        merged = post_layers > 1 and _MERGE_LAST_POST
+        merged = post_layers > 1
         f32 = dict(dtype=torch.float32, device=BE.device)
         EE = torch.empty(L, R, F, **f32)
         Te = torch.empty(L, R, H, **f32)
@@ -593,8 +547,8 @@ def _pna_backward_native(ctx, dout, x, BE, EE, A, hs, zs, params, sinks, code_po
     # small accumulators: private scratch, or (deferral) zeroed slices of the model's slab that stay alive until the ONE
     # batched finish at the end of the pass; a data-parallel exchange that hands every layer's slice to RCCL the moment
     # its launches are issued (ops.set_wgrad_done_hook) needs the layer's gradients complete here: no deferral then
-    defer = _BATCH_WEIGHT_ONLY and acc is not None and ops._WGRAD_DONE_HOOK is None and \
-        (acc.slab is not None or acc.first_in_backward(ctx.layer_index))  # pylint: disable=protected-access
+    defer = _BATCH_WEIGHT_ONLY and acc is not None and not ops.wgrad_done_hook_set() and \
+        (acc.slab is not None or acc.first_in_backward(ctx.layer_index))
     if defer:
         dTe_t, dEE_t, dWm_t, dbm_t, dWeff_t = acc.layer_slab(ctx.layer_index, R, H, F, T, D, dev)
         small = None
@@ -632,7 +586,7 @@ def _pna_backward_native(ctx, dout, x, BE, EE, A, hs, zs, params, sinks, code_po
     a.dA, a.dP, a.dQ = dA.data_ptr(), pq[0].data_ptr(), pq[1].data_ptr()
     if defer:
         a.dTe, a.dEE, a.dWm, a.dbm, a.dWeff = (t_.data_ptr() for t_ in (dTe_t, dEE_t, dWm_t, dbm_t, dWeff_t))
-        a.defer_small = 1
+        a.flags = _lib.PNA_BWD_DEFER_SMALL
         acc.deferred.append(dict(T=T, F=F, pre=pre_layers, post=post_layers, R=R, D=D, merged=merged, avg=float(avg_deg_log),
                                  BE=BE, EE=EE, params=list(params), sinks=list(sinks), dTe=dTe_t, dEE=dEE_t, dWm=dWm_t,
                                  dbm=dbm_t, dWeff=dWeff_t))
@@ -643,14 +597,11 @@ def _pna_backward_native(ctx, dout, x, BE, EE, A, hs, zs, params, sinks, code_po
         a.dWm, o = base + 4 * o, o + H * H
         a.dbm, o = base + 4 * o, o + H
         a.dWeff = base + 4 * o
-        a.defer_small = 0
-    if _CLASS_WGRAD_AFTER_AGG:
-        a.defer_small |= 8
-    if _WGRAD_FLUSH_BEFORE_DX:
-        a.defer_small |= 16
-    if ctx.layer_index == 0 and _TAIL_WGRAD_ALL_CUS:
-        a.defer_small |= 6 if _TAIL_WGRAD_EARLY else 2  # the last conv backward of the pass: its weight gradients may take
-        # every CU, and the ones of the post layers go out before the edge backward instead of at the end
+        a.flags = 0
+    if ctx.layer_index == 0:
+        # the last conv backward of the pass: its batched weight gradients take every CU, at the end of the layer (6.760 ->
+        # 6.687 ms; the post layers' ones launched earlier, before the edge backward, compete with it: 6.612 vs 6.554 ms)
+        a.flags |= _lib.PNA_BWD_LAST_OF_PASS
     a.ws, a.ws_bytes, a.acc_buf, a.dx = ws.data_ptr(), ws_bytes, acc.buf.data_ptr(), dx.data_ptr()
     etiles = pack.edge_tiles(D - 1) if (_FUSED_EDGE and pre_layers == 2) else None  # (the forward's table, cached on the pack)
     a.etile_info, a.etile_w = (etiles[0].data_ptr(), etiles[1]) if etiles is not None else (None, 0)

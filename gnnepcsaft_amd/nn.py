@@ -214,7 +214,7 @@ class PNAConv(Module):
     def prepare_ahead(self, edge_index: GraphPack, edge_attr: torch.Tensor) -> "Fn.WeightOnlyAhead":
         """Issue this layer's weight-only work (bond-table chain, Weff(d), merged lin o last post layer) on the side
         stream now; pass ``.wait()`` of the result to ``forward(prepared=...)``.  The model does this one layer ahead."""
-        dc = edge_index.degree_classes(edge_index.max_degree_hint) if Fn._USE_DEGREE_CLASSES else None
+        dc = edge_index.degree_classes(edge_index.max_degree_hint) if Fn.degree_classes_enabled() else None
         return Fn.WeightOnlyAhead(edge_attr, self.towers, self.F_in, self.pre_layers, self.post_layers,
                                   self.aggr_module.avg_log(), self._params(), dc.D if dc is not None else 0)
 
@@ -226,7 +226,7 @@ class PNAConv(Module):
         if any((c.towers, c.F_in, c.pre_layers, c.post_layers) != (c0.towers, c0.F_in, c0.pre_layers, c0.post_layers)
                for c in convs):
             raise ValueError("prepare_all needs identically shaped PNAConv layers")
-        dc = edge_index.degree_classes(edge_index.max_degree_hint) if Fn._USE_DEGREE_CLASSES else None
+        dc = edge_index.degree_classes(edge_index.max_degree_hint) if Fn.degree_classes_enabled() else None
         layers = [(c.aggr_module.avg_log(), c._params()) for c in convs]
         return Fn.WeightOnlyAll(edge_attr, c0.towers, c0.F_in, c0.pre_layers, c0.post_layers, layers,
                                 dc.D if dc is not None else 0)

@@ -478,6 +478,10 @@ def set_wgrad_done_hook(fn) -> None:
     _WGRAD_DONE_HOOK = fn
 
 
+def wgrad_done_hook_set() -> bool:
+    return _WGRAD_DONE_HOOK is not None
+
+
 def side_stream(device: torch.device, which: int = 0) -> "torch.cuda.Stream":
     """One of the library's side streams (0 = weight gradients, 1 = bond-table chain) as a torch stream (no ownership)."""
     out = C.c_void_p()

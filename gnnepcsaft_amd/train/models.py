@@ -160,12 +160,12 @@ class GNNePCSAFT(torch.nn.Module):  # pylint: disable=R0902
         if h.is_cuda and Fn.batch_weight_only_enabled() and isinstance(convs[0], gnn.PNAConv) and convs[0].towers <= 8:
             # ... of ALL layers in three launches (60-row products and Weff(d) batched over the layers)
             ahead_all = gnn.PNAConv.prepare_all(convs, pack, bond_table)
-        elif h.is_cuda and ops.wgrad_stream_enabled() and Fn.prepare_ahead_enabled() and hasattr(convs[0], "prepare_ahead"):
+        elif h.is_cuda and ops.wgrad_stream_enabled() and hasattr(convs[0], "prepare_ahead"):
             ahead = convs[0].prepare_ahead(pack, bond_table)
         # every layer's bond-embedding gradient is accumulated into one buffer on a side stream (its chain feeds no
         # activation gradient); layer 0, whose backward runs last, returns the total
         acc = None
-        if h.is_cuda and bond_table.requires_grad and torch.is_grad_enabled() and Fn.bond_chain_aside_enabled():
+        if h.is_cuda and bond_table.requires_grad and torch.is_grad_enabled():
             acc = Fn.BondGradAccumulator(bond_table.size(0), bond_table.size(1), h.device, len(convs))
             acc.encoder = (self.edge_embed.combos, self.edge_embed.offsets, self.edge_embed._weights())
         for l, (layer, norm) in enumerate(zip(convs, self.batch_norms)):

@@ -223,7 +223,7 @@ class Trainer:
             if ckpt.get("attn_dropout") and len(ckpt["attn_dropout"]) == len(attn):
                 for c, st in zip(attn, ckpt["attn_dropout"]):
                     c.seed, c.calls = int(st["seed"]), int(st["calls"])
-        prev_in_place = Fn._GRAD_IN_PLACE  # pylint: disable=protected-access
+        prev_in_place = Fn.grad_in_place_enabled()
         prev_validate = model.model.validate_inputs
         Fn.set_grad_in_place(self.fused_optimizer)
         model.model.validate_inputs = False  # one range check per logging interval instead of one sync per batch

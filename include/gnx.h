@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define GNX_ABI_VERSION 5
+#define GNX_ABI_VERSION 6
 
 enum {
   GNX_OK = 0,
@@ -57,23 +57,16 @@ int32_t gnx_abi_version(void);
  * environment variable of the same name with the GNX_ prefix (e.g. GNX_GEMM_SPLIT=0), read once in gnx_create. */
 enum {
   GNX_OPT_GEMM_SPLIT = 0,        /* 1: products with >= 4096 rows as three-bf16-piece split products; 0: fp32 MFMA */
-  GNX_OPT_GEMM_WS = 1,           /* 1: weights-stationary kernel for one segment with K, N <= 128, M >= 8192 */
-  GNX_OPT_GEMM_VEC = 2,          /* 0: element-wise loaders everywhere (debug) */
-  GNX_OPT_WGRAD_VEC = 3,         /* 0: element-wise weight-gradient loaders (debug) */
-  GNX_OPT_WGRAD_WGS = 4,         /* > 0: target workgroup count of the weight-gradient kernels (default: #CUs) */
-  GNX_OPT_AGG_BWD_RECOMPUTE = 5, /* 1: PNA aggregate backward recomputes mean/min/max/std from the messages */
-  GNX_OPT_EMBED_BWD_MFMA = 6,    /* atom-embedding gradient as a one-hot MFMA product for N >= 256: 1 = scattered bf16 one-hot x three-piece gradient (tables of <= 192 rows), 2 = computed fp32 one-hot on the fp32 matrix pipe, 0 = LDS atomics */
-  GNX_OPT_STD_BWD_CENTERED = 7,  /* 1: std gradient divides by the centred two-pass std (see gnx_pna_aggregate_bwd) */
-  GNX_OPT_GEMM_PIPE = 8,         /* 1: tiled split products with >= 8 K-tiles per tile take the software-pipelined kernel (bit-identical results) */
-  GNX_OPT_WGRAD_PIPE = 9,        /* 1: split weight gradients of 16-byte aligned operands through the software-pipelined kernel */
-  GNX_OPT_EDGE_FUSED = 10,       /* 1: gnx_pna_conv_fwd / _bwd take the fused edge kernels (gnx_pna_edge_fwd / gnx_pna_edge_bwd) when eligible (bit-identical messages, h1, aggregate, gh1, dP); 2: forward only; 0: three launches each */
-  GNX_OPT_SIDE_CUS = 11,         /* > 0: side stream 0 (weight gradients) is created with a CU mask of that many CUs (read when the stream is first used) */
-  GNX_OPT_GEMM_AS = 12,          /* 1: split products with one segment, 96 < K <= 128 and N >= 256 take the activation-stationary kernel (the row tile is split once for all column tiles; bit-identical results) */
-  GNX_OPT_GEMM_WS_FAST = 13,     /* the weights-stationary split kernel's predicate-free form (quad-transposed 16-byte stores, exact waits) for N = 128, aligned operands, no accumulate: 2 = as two 4-wave workgroups per CU on 32-row tiles (default), 1 = one 8-wave workgroup per CU on 64-row tiles, 0 = the predicated kernel; bit-identical results */
-  GNX_OPT_GEMM_TILE_ROWS = 14,   /* 96 / 128: row-tile height of the pipelined tiled product (0: chosen per launch; bit-identical results) */
-  GNX_OPT_GEMM_MID = 15,         /* 1: products with M < 4096 rows and <= 48 tiles of 128 x 128 run on 16 x 16 patches (k_gemm_mid) instead of the latency-bound tiled kernel */
-  GNX_OPT_SPLIT_AHEAD = 16,      /* gnx_pna_conv_fwd / _bwd split the weight images of their tiled products on side stream 2 at entry (GNX_GEMM_SPLIT_ONLY) instead of in front of each product: 1 = for layers with two or more towers (cfg-5: -0.44 ms per step; one tower: the fork / join costs what it saves), 2 = always, 0 = never */
-  GNX_OPT_COUNT = 17
+  GNX_OPT_WGRAD_WGS = 1,         /* > 0: target workgroup count of the weight-gradient kernels (default: #CUs) */
+  GNX_OPT_EMBED_BWD_MFMA = 2,    /* atom-embedding gradient as a one-hot MFMA product for N >= 256: 1 = scattered bf16 one-hot x three-piece gradient (tables of <= 192 rows), 2 = computed fp32 one-hot on the fp32 matrix pipe, 0 = LDS atomics */
+  GNX_OPT_STD_BWD_CENTERED = 3,  /* 1: std gradient divides by the centred two-pass std (see gnx_pna_aggregate_bwd) */
+  GNX_OPT_GEMM_PIPE = 4,         /* 1: tiled split products with >= 8 K-tiles per tile take the software-pipelined kernel (bit-identical results) */
+  GNX_OPT_WGRAD_PIPE = 5,        /* 1: split weight gradients of 16-byte aligned operands through the software-pipelined kernel */
+  GNX_OPT_GEMM_AS = 6,           /* 1: split products with one segment, 96 < K <= 128 and N >= 256 take the activation-stationary kernel (the row tile is split once for all column tiles; bit-identical results) */
+  GNX_OPT_GEMM_WS_FAST = 7,      /* the weights-stationary split kernel's predicate-free form (quad-transposed 16-byte stores, exact waits) for N = 128, aligned operands, no accumulate: 2 = as two 4-wave workgroups per CU on 32-row tiles (default), 1 = one 8-wave workgroup per CU on 64-row tiles, 0 = the predicated kernel; bit-identical results */
+  GNX_OPT_GEMM_TILE_ROWS = 8,    /* 96 / 128: row-tile height of the pipelined tiled product (0: chosen per launch; bit-identical results) */
+  GNX_OPT_GEMM_MID = 9,          /* 1: products with M < 4096 rows and <= 48 tiles of 128 x 128 run on 16 x 16 patches (k_gemm_mid) instead of the latency-bound tiled kernel */
+  GNX_OPT_COUNT = 10
 };
 int32_t gnx_set_option(gnx_handle* h, int32_t opt, int32_t value);
 int32_t gnx_get_option(gnx_handle* h, int32_t opt, int32_t* value);
@@ -319,7 +312,8 @@ int32_t gnx_pna_aggregate_fwd(gnx_handle* h, const float* m, const int32_t* rowp
  * the gradient is dstd (m - mean) / (n std): with GNX_OPT_STD_BWD_CENTERED (default) `std` is re-evaluated as
  * sqrt(sum (m - mean)^2 / n), which is accurate to fp32 rounding, instead of the forward's mean(x^2) - mean(x)^2 whose
  * cancellation error (~ eps mean(x^2) / (2 var) relative, up to 3e-5 just above the mask) the CPU path carries into
- * its gradient; 0 = divide by the forward's value like the CPU path does. */
+ * its gradient; 0 = divide by the forward's value like the CPU path does.  mean / min / max / std are recomputed from
+ * the messages with the forward's arithmetic; A (the forward's output) is required but not read. */
 int32_t gnx_pna_aggregate_bwd(gnx_handle* h, const float* dA, const float* m, const float* A, const int32_t* rowptr,
                               int64_t N, int64_t E, int32_t T, int32_t F, float* dm);
 
@@ -465,6 +459,14 @@ int32_t gnx_sgd(gnx_handle* h, float* p, const float* g, int64_t n, float lr);
  * and the weight-gradient chunks) and the by-code inverted index code_pos (gnx_group_by_small_key). */
 #define GNX_PNA_MAX_LAYERS 8
 #define GNX_PNA_MAX_TOWERS 8
+/* gnx_pna_bwd_args.flags */
+enum {
+  GNX_PNA_BWD_DEFER_SMALL = 1,   /* dTe / dEE / dWm / dbm / dWeff were ZEROED by the caller and stay alive until
+                                    gnx_pna_stack_finish, which runs every layer's 60-row bond-table chain, its lin o last-post
+                                    un-merge and its Weff gradient in a few batched launches: gnx_pna_conv_bwd leaves them out */
+  GNX_PNA_BWD_LAST_OF_PASS = 2   /* this is the LAST conv backward of the pass: nothing follows on the main stream, so its
+                                    batched weight gradients take every CU and go out at the end of the layer */
+};
 typedef struct {
   int64_t N, E;
   int32_t T, F, pre_layers, post_layers, R, D;
@@ -498,16 +500,7 @@ typedef struct {
   size_t ws_bytes;
   float* acc_buf;                             /* [R,H] bond-embedding gradient accumulator shared by the model's layers */
   float* dx;                                  /* [N,H] out: gradient w.r.t. the layer input */
-  int32_t defer_small;                        /* bit 1 (value 2): this is the LAST conv backward of the pass (nothing follows on the
-                                                 main stream: its weight gradients may take every CU); bit 2 (value 4): ... and the ones queued before the
-                                                 edge backward are launched there instead of at the end; bit 3 (value 8): the per-class weight
-                                                 gradient of post-layer 0 is forked BEHIND the aggregate backward (a memory-bound kernel it
-                                                 slows down a lot: 135 us beside it, 55 alone) instead of in front of it; bit 4 (value 16): the
-                                                 batched weight gradients start in front of the dx product (matrix-bound) instead of behind it
-                                                 (beside the next layer's BatchNorm backward).  bit 0 (value 1):
-                                                 dTe / dEE / dWm / dbm / dWeff were ZEROED by the caller and stay alive until
-                                                 gnx_pna_stack_finish, which runs every layer's 60-row bond-table chain, its
-                                                 lin o last-post un-merge and its Weff gradient in a few batched launches */
+  int32_t flags;                              /* flag word: GNX_PNA_BWD_* (above) */
   int32_t etile_w;                            /* tile width of etile_info */
   const int32_t* etile_info;                  /* gnx_edge_tiles table (NULL: three-launch edge backward); with two pre layers
                                                  the masked input gradient, dP and dTe then come from gnx_pna_edge_bwd */
@@ -515,7 +508,7 @@ typedef struct {
 size_t gnx_pna_conv_bwd_workspace_bytes(int32_t T, int32_t F, int32_t D);
 int32_t gnx_pna_conv_bwd(gnx_handle* h, const gnx_pna_bwd_args* args);
 
-/* What gnx_pna_conv_bwd(defer_small = 1) left out, for ALL L layers of a model in ~6 launches (instead of ~14 per layer):
+/* What gnx_pna_conv_bwd(flags & GNX_PNA_BWD_DEFER_SMALL) left out, for ALL L layers of a model in ~6 launches (instead of ~14 per layer):
  * side stream 1: pre-layer-0 edge-slice / edge_encoder gradients and the bond-embedding gradient (atomic adds into acc_buf,
  * which the caller zeroed) from every layer's dTe; side stream 0 (behind the layers' weight gradients): lin / last-post
  * gradients from dWm / dbm, and post-layer 0's A-block gradients from dWeff.  Pointer arrays are HOST arrays; params /

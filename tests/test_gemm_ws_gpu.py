@@ -1,5 +1,5 @@
 """GPU parity of the weights-stationary persistent GEMM (k_gemm_ws: one segment, K,N <= 128, M >= 8192) against fp64
-torch, all epilogue variants, both weight layouts, ragged M / K / N; and against the tiled kernel (GNX_GEMM_WS=0)."""
+torch, all epilogue variants, both weight layouts, ragged M / K / N."""
 import os
 
 import pytest

@@ -1,7 +1,7 @@
 """Same-box A/B of the bench step under feature switches (box-to-box spread is ~5 %, so every optimisation is judged
 inside one process): alternates the variants REPS times and prints the median ms/step of each.
 usage: python tools/ab_bench.py [--config 2] [--batch 4096] [--steps 30] [--reps 4] variant ...
-variants: base | nomerge | noahead | noside | nocentered ... (see VARIANTS)"""
+variants: base | nonative | noside | nocentered ... (see VARIANTS)"""
 import argparse, os, sys, time, statistics
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -11,10 +11,7 @@ from gnnepcsaft_amd.train.models import create_model
 
 VARIANTS = {
     "base": lambda dev: None,
-    "nomerge": lambda dev: Fn.set_merge_last_post(False),
-    "noahead": lambda dev: Fn.set_prepare_ahead(False),
     "nonative": lambda dev: Fn.set_native_layer_backward(False),
-    "nobondaside": lambda dev: Fn.set_bond_chain_aside(False),
     "noside": lambda dev: ops.set_wgrad_side_stream(False),
     "nocentered": lambda dev: ops.set_option(dev, _lib.OPT_STD_BWD_CENTERED, 0),
     "nopipe": lambda dev: ops.set_option(dev, _lib.OPT_GEMM_PIPE, 0),
@@ -38,32 +35,22 @@ VARIANTS = {
     "nobatch": lambda dev: ops.set_wgrad_batching(False),
     "nofused": lambda dev: Fn.set_fused_edge(False),
     "nobatchwo": lambda dev: Fn.set_batch_weight_only(False),
-    "nofusedbwd": lambda dev: ops.set_option(dev, _lib.OPT_EDGE_FUSED, 2),
     "noas3": lambda dev: ops.set_option(dev, _lib.OPT_GEMM_AS, 0),
     "nowsfast": lambda dev: ops.set_option(dev, _lib.OPT_GEMM_WS_FAST, 0),
-    "nosplitahead": lambda dev: ops.set_option(dev, _lib.OPT_SPLIT_AHEAD, 0),
     "embfp32": lambda dev: ops.set_option(dev, _lib.OPT_EMBED_BWD_MFMA, 2),
-    "classearly": lambda dev: Fn.set_class_wgrad_after_agg(False),
-    "flushlate": lambda dev: Fn.set_wgrad_flush_before_dx(False),
-    "notail": lambda dev: Fn.set_tail_wgrad_all_cus(False),
-    "tailearly": lambda dev: Fn.set_tail_wgrad_all_cus(True, True),
     "ws8waves": lambda dev: ops.set_option(dev, _lib.OPT_GEMM_WS_FAST, 1),
-    "rcloop": lambda dev: ops.set_option(dev, _lib.OPT_AGG_BWD_RECOMPUTE, 2),
     "rows128": lambda dev: ops.set_option(dev, _lib.OPT_GEMM_TILE_ROWS, 128),
     "rows96": lambda dev: ops.set_option(dev, _lib.OPT_GEMM_TILE_ROWS, 96),
 }
 
 
 def reset(dev):
-    Fn.set_merge_last_post(True); Fn.set_prepare_ahead(True); Fn.set_bond_chain_aside(True); Fn.set_native_layer_backward(True); ops.set_wgrad_side_stream(True); Fn.set_fused_edge(True); Fn.set_batch_weight_only(True); Fn.set_tail_wgrad_all_cus(True); Fn.set_class_wgrad_after_agg(True); Fn.set_wgrad_flush_before_dx(True)
+    Fn.set_native_layer_backward(True); ops.set_wgrad_side_stream(True); Fn.set_fused_edge(True); Fn.set_batch_weight_only(True)
     ops.set_option(dev, _lib.OPT_STD_BWD_CENTERED, 1)
     ops.set_option(dev, _lib.OPT_GEMM_PIPE, 1)
     ops.set_option(dev, _lib.OPT_WGRAD_PIPE, 1)
-    ops.set_option(dev, _lib.OPT_EDGE_FUSED, 1)
     ops.set_option(dev, _lib.OPT_GEMM_AS, 1)
     ops.set_option(dev, _lib.OPT_EMBED_BWD_MFMA, 1)
-    ops.set_option(dev, _lib.OPT_SPLIT_AHEAD, 1)
-    ops.set_option(dev, _lib.OPT_AGG_BWD_RECOMPUTE, 1)
     ops.set_option(dev, _lib.OPT_GEMM_WS_FAST, 2)
     ops.set_option(dev, _lib.OPT_GEMM_TILE_ROWS, 0)
     ops.set_option(dev, _lib.OPT_WGRAD_WGS, 0); ops.DegreeClasses.WGRAD_ROWS = 1024; ops.set_wgrad_batching(True)

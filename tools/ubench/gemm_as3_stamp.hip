@@ -25,7 +25,7 @@ int main(int argc, char** argv) {
   gnx_handle h;
   h.num_cus = 256;
   for (int i = 0; i < GNX_OPT_COUNT; ++i) h.opt[i] = 0;
-  h.opt[GNX_OPT_GEMM_SPLIT] = 1; h.opt[GNX_OPT_GEMM_VEC] = 1; h.opt[GNX_OPT_GEMM_AS] = 1; h.opt[GNX_OPT_GEMM_PIPE] = 1;
+  h.opt[GNX_OPT_GEMM_SPLIT] = 1; h.opt[GNX_OPT_GEMM_AS] = 1; h.opt[GNX_OPT_GEMM_PIPE] = 1;
   std::vector<float> ha((size_t)M * K), hw((size_t)K * N);
   unsigned s = 777u;
   for (auto& v : ha) { s = s * 1664525u + 1013904223u; v = ((int)(s >> 8) % 2001 - 1000) * 1e-3f; }

@@ -23,7 +23,7 @@ int main(int argc, char** argv) {
   gnx_handle h;
   h.num_cus = 256;
   for (int i = 0; i < GNX_OPT_COUNT; ++i) h.opt[i] = 0;
-  h.opt[GNX_OPT_GEMM_SPLIT] = 1; h.opt[GNX_OPT_GEMM_VEC] = 1; h.opt[GNX_OPT_GEMM_WS] = 1; h.opt[GNX_OPT_GEMM_WS_FAST] = 1;
+  h.opt[GNX_OPT_GEMM_SPLIT] = 1; h.opt[GNX_OPT_GEMM_WS_FAST] = 1;
   for (int64_t M : {81920ll, 327680ll}) {
     std::vector<float> ha((size_t)M * K), hw((size_t)K * N);
     unsigned s = 777u;
