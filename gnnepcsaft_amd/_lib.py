@@ -10,7 +10,7 @@ import torch
 
 _LIB_PATH = Path(__file__).resolve().parent / "libgnnepcsaft_hip.so"
 
-ABI_VERSION = 6
+ABI_VERSION = 7
 GNX_OK, GNX_E_INVALID, GNX_E_HIP, GNX_E_RANGE, GNX_E_WORKSPACE = 0, -1, -2, -3, -4
 # gnx_set_option ids (include/gnx.h)
 OPT_GEMM_SPLIT, OPT_WGRAD_WGS, OPT_EMBED_BWD_MFMA, OPT_STD_BWD_CENTERED, OPT_GEMM_PIPE, OPT_WGRAD_PIPE, OPT_GEMM_AS, \
@@ -121,6 +121,10 @@ SIGNATURES = {
     "gnx_table_scatter_workspace_bytes": (_sz, [_i64, _i32, _i32]),
     "gnx_embed_sum_bwd": (_i32, [_vp, _vp, _i64, _i32, C.POINTER(_i32), _i32, _vp, _i32, _vp, _vp, _sz]),
     "gnx_check_range": (_i32, [_vp]),
+    "gnx_collate_ptr": (_i32, [_vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp]),
+    "gnx_collate_gather": (_i32, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _i64, _vp, _vp,
+                                  _vp, _vp]),
+    "gnx_collate_rows": (_i32, [_vp, _vp, _i64, _vp, _i64, _i32, _i32, _vp]),
     "gnx_gemm_workspace_bytes": (_sz, [_vp, _i32, C.POINTER(GemmSeg), C.POINTER(_i64), _i32, _i64, _i32, _vp, _i32,
                                        _i32]),
     "gnx_gemm": (_i32, [_vp, _i32, C.POINTER(GemmSeg), _i64, _i32, _vp, _vp, _i64, _vp, _i64, _i32, _vp, _sz]),

@@ -264,6 +264,93 @@ def pack_graph(edge_index: torch.Tensor, edge_attr: Optional[torch.Tensor], batc
 
 
 # ------------------------------------------------------------------------------------------------------------------
+# batch collation from a device-resident dataset (data/device.py)
+# ------------------------------------------------------------------------------------------------------------------
+def _i64c(t: torch.Tensor, name: str, shape: Sequence[Optional[int]]) -> torch.Tensor:
+    """``t`` if it is a contiguous int64 tensor of ``shape`` (None = any extent), else GnxError(GNX_E_INVALID)."""
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.int64 or t.dim() != len(shape) or not t.is_contiguous() or \
+            any(s is not None and int(d) != s for d, s in zip(t.shape, shape)):
+        want = ",".join("*" if s is None else str(s) for s in shape)
+        got = f"{t.dtype} {tuple(t.shape)}" if isinstance(t, torch.Tensor) else type(t).__name__
+        raise _lib.GnxError(_lib.GNX_E_INVALID, f"{name}: expected contiguous int64[{want}], got {got}")
+    return t
+
+
+def _on(dev: torch.device, *tensors: torch.Tensor) -> None:
+    for t in tensors:
+        if t.device != dev:
+            raise _lib.GnxError(_lib.GNX_E_INVALID, f"collate: every tensor must be on {dev}, got one on {t.device}")
+
+
+def collate_ptr(node_ptr: torch.Tensor, edge_ptr: torch.Tensor, idx: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(ptr, eptr) int64[B+1]: exclusive prefix sums of the node / edge counts of graphs ``idx`` int64[B] of a dataset
+    with offsets ``node_ptr`` / ``edge_ptr`` int64[G+1].  An index outside [0,G) is clamped and trips ``check_range``."""
+    _i64c(node_ptr, "node_ptr", (None,))
+    G = node_ptr.size(0) - 1
+    _i64c(edge_ptr, "edge_ptr", (G + 1,))
+    _i64c(idx, "idx", (None,))
+    B = idx.size(0)
+    if G < 1 or B < 1:
+        raise _lib.GnxError(_lib.GNX_E_INVALID, f"collate_ptr: need at least one graph and one index, got G={G} B={B}")
+    dev = node_ptr.device
+    _on(dev, edge_ptr, idx)
+    out = torch.empty(2, B + 1, dtype=torch.int64, device=dev)
+    check(_lib.load().gnx_collate_ptr(handle(dev), node_ptr.data_ptr(), edge_ptr.data_ptr(), G, idx.data_ptr(), B,
+                                      out[0].data_ptr(), out[1].data_ptr()))
+    return out[0], out[1]
+
+
+def collate_gather(node_ptr: torch.Tensor, edge_ptr: torch.Tensor, x: torch.Tensor, edge_index: torch.Tensor,
+                   edge_attr: torch.Tensor, idx: torch.Tensor, ptr: torch.Tensor, eptr: torch.Tensor, N: int, E: int
+                   ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(x [N,9], edge_index [2,E], edge_attr [E,3], batch [N]) of the batch ``idx`` from the stored concatenation
+    ``x`` [sumN,9] / ``edge_index`` [2,sumE] (graph-local ids) / ``edge_attr`` [sumE,3]; ``ptr`` / ``eptr`` come from
+    ``collate_ptr`` and ``N`` / ``E`` are the batch totals the caller computed from its host copy of the sizes."""
+    _i64c(node_ptr, "node_ptr", (None,))
+    G = node_ptr.size(0) - 1
+    _i64c(edge_ptr, "edge_ptr", (G + 1,))
+    _i64c(x, "x", (None, 9))
+    _i64c(edge_index, "edge_index", (2, None))
+    E_src = edge_index.size(1)
+    _i64c(edge_attr, "edge_attr", (E_src, 3))
+    _i64c(idx, "idx", (None,))
+    B = idx.size(0)
+    _i64c(ptr, "ptr", (B + 1,))
+    _i64c(eptr, "eptr", (B + 1,))
+    N, E = int(N), int(E)
+    if G < 1 or B < 1 or N < 0 or E < 0:
+        raise _lib.GnxError(_lib.GNX_E_INVALID, f"collate_gather: bad sizes G={G} B={B} N={N} E={E}")
+    dev = x.device
+    _on(dev, node_ptr, edge_ptr, edge_index, edge_attr, idx, ptr, eptr)
+    i64 = dict(dtype=torch.int64, device=dev)
+    x_out, ei_out, ea_out = torch.empty(N, 9, **i64), torch.empty(2, E, **i64), torch.empty(E, 3, **i64)
+    batch = torch.empty(N, **i64)
+    check(_lib.load().gnx_collate_gather(handle(dev), node_ptr.data_ptr(), edge_ptr.data_ptr(), G, x.data_ptr(),
+                                         edge_index.data_ptr(), edge_attr.data_ptr(), E_src, idx.data_ptr(), B,
+                                         ptr.data_ptr(), eptr.data_ptr(), N, E, x_out.data_ptr(), ei_out.data_ptr(),
+                                         ea_out.data_ptr(), batch.data_ptr()))
+    return x_out, ei_out, ea_out, batch
+
+
+def collate_rows(src: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
+    """``src[idx]`` for a one-row-per-graph field ``src`` [G, ...] of any 4- or 8-byte dtype (moved as raw words)."""
+    if not isinstance(src, torch.Tensor) or src.dim() < 1 or not src.is_contiguous() or src.element_size() not in (4, 8):
+        got = f"{src.dtype} {tuple(src.shape)}" if isinstance(src, torch.Tensor) else type(src).__name__
+        raise _lib.GnxError(_lib.GNX_E_INVALID, f"collate_rows: expected a contiguous [G, ...] tensor of a 4- or 8-byte "
+                                                f"dtype, got {got}")
+    _i64c(idx, "idx", (None,))
+    G, B = src.size(0), idx.size(0)
+    if G < 1 or B < 1:
+        raise _lib.GnxError(_lib.GNX_E_INVALID, f"collate_rows: need at least one row and one index, got G={G} B={B}")
+    K = src.numel() // G
+    _on(src.device, idx)
+    dst = torch.empty((B,) + tuple(src.shape[1:]), dtype=src.dtype, device=src.device)
+    check(_lib.load().gnx_collate_rows(handle(src.device), src.data_ptr(), G, idx.data_ptr(), B, src.element_size(), K,
+                                       dst.data_ptr()))
+    return dst
+
+
+# ------------------------------------------------------------------------------------------------------------------
 # embeddings
 # ------------------------------------------------------------------------------------------------------------------
 def embed_sum_fwd(idx: torch.Tensor, table: torch.Tensor, offsets: Sequence[int]) -> torch.Tensor:

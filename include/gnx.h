@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define GNX_ABI_VERSION 6
+#define GNX_ABI_VERSION 7
 
 enum {
   GNX_OK = 0,
@@ -135,6 +135,29 @@ int32_t gnx_graph_ptr(gnx_handle* h, const int64_t* batch, int64_t N, int64_t B,
 /* PNA degree scalers [3P DegreeScalerAggregation]: amp[n] = log(d+1)/avg_deg_log, att[n] = avg_deg_log/log(max(d,1)+1),
  * d = rowptr[n+1]-rowptr[n]. */
 int32_t gnx_degree_scalers(gnx_handle* h, const int32_t* rowptr, int64_t N, float avg_deg_log, float* amp, float* att);
+
+/* ---- on-device batch collation from a device-resident dataset (gnnepcsaft_amd/data/device.py) ------------------
+ * Replaces, for training batches, torch_geometric's DataLoader -> Batch.from_data_list [3P] on the host
+ * (ref: train/train.py:59-75).  The dataset is stored on the device as the concatenation of its G graphs:
+ *   node_ptr / edge_ptr int64[G+1] (offsets of every graph's nodes / edges), x int64[sumN,9],
+ *   edge_index int64[2,E_src] holding GRAPH-LOCAL node ids (E_src = sumE), edge_attr int64[E_src,3].
+ * A batch is idx int64[B]: slot b takes graph idx[b] (repeats allowed).  An idx[b] outside [0,G) is clamped and sets
+ * the sticky range flag (bit 7, gnx_check_range).  Integer copies with plain stores: bit-identical from call to call.
+ * gnx_collate_ptr: out_ptr / out_eptr int64[B+1] = exclusive prefix sums of the selected graphs' node / edge counts
+ *   (out_ptr = Batch.ptr).  No workspace; 1 launch for B <= 1024, 3 above.  1 <= B < 2^31. */
+int32_t gnx_collate_ptr(gnx_handle* h, const int64_t* node_ptr, const int64_t* edge_ptr, int64_t G, const int64_t* idx,
+                        int64_t B, int64_t* out_ptr, int64_t* out_eptr);
+/* the batch itself from the gnx_collate_ptr offsets: x_out int64[N,9], edge_index_out int64[2,E] (out_ptr[b] added),
+ * edge_attr_out int64[E,3], batch_out int64[N] (= b).  N and E are the totals the caller allocated for (it keeps the
+ * graph sizes on the host, nothing is read back); a block that would not fit them is cut and sets flag bit 7. */
+int32_t gnx_collate_gather(gnx_handle* h, const int64_t* node_ptr, const int64_t* edge_ptr, int64_t G, const int64_t* x,
+                           const int64_t* edge_index, const int64_t* edge_attr, int64_t E_src, const int64_t* idx,
+                           int64_t B, const int64_t* out_ptr, const int64_t* out_eptr, int64_t N, int64_t E,
+                           int64_t* x_out, int64_t* edge_index_out, int64_t* edge_attr_out, int64_t* batch_out);
+/* dst[b,:] = src[idx[b],:] for a one-row-per-graph field (para, assoc, ...): src [G,K], dst [B,K], elements of
+ * elem_bytes = 4 or 8 bytes moved as raw words (any dtype of that size). */
+int32_t gnx_collate_rows(gnx_handle* h, const void* src, int64_t G, const int64_t* idx, int64_t B, int32_t elem_bytes,
+                         int32_t K, void* dst);
 
 /* ---- embeddings: AtomEncoder / BondEncoder [3P ogb] (ref: train/models.py:175-176, 205-206) ----------------- */
 /* out[n,:] = sum_{k<K} table[offsets[k] + idx[n,k], :], summed left to right in fp32 (bit-exact with the CPU path).
