@@ -10,6 +10,8 @@ import torch
 
 _LIB_PATH = Path(__file__).resolve().parent / "libgnnepcsaft_hip.so"
 
+# stays 7 with gnx_pcsaft_mix_*: the version guards incompatible changes, and load() names a declared symbol that a stale
+# library lacks
 ABI_VERSION = 7
 GNX_OK, GNX_E_INVALID, GNX_E_HIP, GNX_E_RANGE, GNX_E_WORKSPACE = 0, -1, -2, -3, -4
 # gnx_set_option ids (include/gnx.h)
@@ -19,8 +21,9 @@ GEMM_RELU, GEMM_ACCUMULATE, GEMM_B_TRANS, GEMM_SPLIT_ONLY, GEMM_PRESPLIT = 1, 2,
 POOL_ADD, POOL_MEAN, POOL_MAX = 0, 1, 2
 K_NONE, K_PNA_AGG_FWD, K_PNA_AGG_BWD, K_GEMM_WS, K_GEMM_WGRAD, K_GINE_AGG_FWD, K_GINE_AGG_BWD, K_EDGE_COMBINE_FWD, \
     K_EDGE_COMBINE_BWD, K_BN_FWD, K_BN_BWD, K_GEMM_TILED, K_GEMM_SMALL, K_GEMM_WGRAD_BATCHED, K_KEY_SEGMENT_SUM, \
-    K_EMBED, K_PNA_EDGE_FWD, K_PNA_EDGE_BWD, K_ATTN_FWD, K_ATTN_BWD, K_PCSAFT_RHO, K_PCSAFT_VP = range(22)
-K_COUNT = 22
+    K_EMBED, K_PNA_EDGE_FWD, K_PNA_EDGE_BWD, K_ATTN_FWD, K_ATTN_BWD, K_PCSAFT_RHO, K_PCSAFT_VP, \
+    K_PCSAFT_MIX_STATE, K_PCSAFT_MIX_RHO = range(24)
+K_COUNT = 24
 KERNEL_GROUPS = {K_PNA_AGG_FWD: "pna_aggregate_fwd", K_PNA_AGG_BWD: "pna_aggregate_bwd", K_GEMM_WS: "gemm_weights_stationary",
                  K_GEMM_WGRAD: "weight_gradient", K_GINE_AGG_FWD: "gine_aggregate_fwd", K_GINE_AGG_BWD: "gine_aggregate_bwd",
                  K_EDGE_COMBINE_FWD: "edge_combine_fwd", K_EDGE_COMBINE_BWD: "edge_combine_bwd", K_BN_FWD: "batchnorm_fwd",
@@ -28,7 +31,8 @@ KERNEL_GROUPS = {K_PNA_AGG_FWD: "pna_aggregate_fwd", K_PNA_AGG_BWD: "pna_aggrega
                  K_GEMM_WGRAD_BATCHED: "weight_gradient_batched", K_KEY_SEGMENT_SUM: "key_segment_sum", K_EMBED: "embedding",
                  K_PNA_EDGE_FWD: "pna_edge_fused_fwd", K_PNA_EDGE_BWD: "pna_edge_fused_bwd",
                  K_ATTN_FWD: "transformer_attn_fwd", K_ATTN_BWD: "transformer_attn_bwd",
-                 K_PCSAFT_RHO: "pcsaft_density", K_PCSAFT_VP: "pcsaft_vapor_pressure"}
+                 K_PCSAFT_RHO: "pcsaft_density", K_PCSAFT_VP: "pcsaft_vapor_pressure",
+                 K_PCSAFT_MIX_STATE: "pcsaft_mix_state", K_PCSAFT_MIX_RHO: "pcsaft_mix_density"}
 
 
 class GnxError(RuntimeError):
@@ -166,6 +170,9 @@ SIGNATURES = {
     "gnx_transformer_attn_dle": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp]),
     "gnx_pcsaft_density": (_i32, [_vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp]),
     "gnx_pcsaft_vapor_pressure": (_i32, [_vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp]),
+    "gnx_pcsaft_mix_state": (_i32, [_vp, _vp, _i64, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp,
+                                    _vp]),
+    "gnx_pcsaft_mix_density": (_i32, [_vp, _vp, _i64, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _vp]),
     "gnx_segment_pool_fwd": (_i32, [_vp, _vp, _vp, _i64, _i32, _i32, _vp]),
     "gnx_segment_pool_bwd": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp]),
     "gnx_batchnorm_workspace_bytes": (_sz, [_i64, _i32]),

@@ -1029,6 +1029,62 @@ def pcsaft_vapor_pressure(params: torch.Tensor, owner: torch.Tensor, T: torch.Te
     return out[0], out[1], out[2], status
 
 
+def _pcsaft_mix_args(params, comp, kij, eab, owner, T, second, x, name):
+    params, owner, T = _pcsaft_args(params, owner, T, name)
+    dev = params.device
+    if comp.dtype != torch.int64 or comp.device != dev or comp.dim() != 2 or not 1 <= comp.size(1) <= 4:
+        raise _lib.GnxError(_lib.GNX_E_INVALID, f"{name}: comp must be an int64 [M, nc] tensor on {dev} with 1 <= nc <= 4")
+    M, nc = comp.shape
+    mats = []
+    for label, t in (("kij", kij), ("eab", eab)):
+        if t is not None:
+            t = _f64_on(t, f"{name}: {label}", dev)
+            if tuple(t.shape) != (M, nc, nc):
+                raise _lib.GnxError(_lib.GNX_E_INVALID, f"{name}: {label} must be [{M}, {nc}, {nc}], got {tuple(t.shape)}")
+        mats.append(t)
+    second = _f64_on(second, f"{name}: state", dev)
+    x = _f64_on(x, f"{name}: x", dev)
+    if second.shape != T.shape or tuple(x.shape) != (T.numel(), nc):
+        raise _lib.GnxError(_lib.GNX_E_INVALID, f"{name}: T {tuple(T.shape)}, state {tuple(second.shape)} and x "
+                                                f"{tuple(x.shape)} do not describe n points of {nc} components")
+    return params, comp.contiguous(), mats[0], mats[1], owner, T, second, x
+
+
+def pcsaft_mix_state(params: torch.Tensor, comp: torch.Tensor, kij: Optional[torch.Tensor], eab: Optional[torch.Tensor],
+                     owner: torch.Tensor, T: torch.Tensor, rho: torch.Tensor, x: torch.Tensor
+                     ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Mixture PC-SAFT state (gnx_pcsaft_mix_state): params [B, 9] fp64 pool of component rows, comp [M, nc] int64 rows
+    of each mixture (-1 = unused slot), kij / eab [M, nc, nc] fp64 or None, owner [n] int64 mixture of each point, T [n] K,
+    rho [n] mol/m^3, x [n, nc] -> (a_res [n], p [n] Pa, dpdrho [n] Pa m^3/mol, status [n] int32); all 0.0 where
+    status != 0.  One launch, no host synchronisation."""
+    params, comp, kij, eab, owner, T, rho, x = _pcsaft_mix_args(params, comp, kij, eab, owner, T, rho, x,
+                                                                "pcsaft_mix_state")
+    n, dev = T.numel(), params.device
+    out = torch.empty(3, n, dtype=torch.float64, device=dev)
+    status = torch.empty(n, dtype=torch.int32, device=dev)
+    check(_lib.load().gnx_pcsaft_mix_state(handle(dev), params.data_ptr(), params.size(0), comp.data_ptr(), _ptr(kij),
+                                           _ptr(eab), comp.size(0), comp.size(1), owner.data_ptr(), T.data_ptr(),
+                                           rho.data_ptr(), x.data_ptr(), n, out[0].data_ptr(), out[1].data_ptr(),
+                                           out[2].data_ptr(), status.data_ptr()))
+    return out[0], out[1], out[2], status
+
+
+def pcsaft_mix_density(params: torch.Tensor, comp: torch.Tensor, kij: Optional[torch.Tensor],
+                       eab: Optional[torch.Tensor], owner: torch.Tensor, T: torch.Tensor, P: torch.Tensor,
+                       x: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Mixture PC-SAFT liquid density (gnx_pcsaft_mix_density): arguments as ``pcsaft_mix_state`` with P [n] Pa in
+    place of rho -> (rho [n] mol/m^3, status [n] int32); rho is 0.0 where status != 0."""
+    params, comp, kij, eab, owner, T, P, x = _pcsaft_mix_args(params, comp, kij, eab, owner, T, P, x,
+                                                              "pcsaft_mix_density")
+    n, dev = T.numel(), params.device
+    rho = torch.empty(n, dtype=torch.float64, device=dev)
+    status = torch.empty(n, dtype=torch.int32, device=dev)
+    check(_lib.load().gnx_pcsaft_mix_density(handle(dev), params.data_ptr(), params.size(0), comp.data_ptr(), _ptr(kij),
+                                             _ptr(eab), comp.size(0), comp.size(1), owner.data_ptr(), T.data_ptr(),
+                                             P.data_ptr(), x.data_ptr(), n, rho.data_ptr(), status.data_ptr()))
+    return rho, status
+
+
 _POOL = {"add": _lib.POOL_ADD, "sum": _lib.POOL_ADD, "mean": _lib.POOL_MEAN, "max": _lib.POOL_MAX}
 
 

@@ -10,6 +10,11 @@ Enable the native evaluation on a model with::
     from gnnepcsaft_amd import pcsaft
     model.rho_batch, model.vp_batch = pcsaft.rho_batch, pcsaft.vp_batch
 
+Binary (and up to quaternary) mixture densities, the reference's second score (demo/utils_binary.py ``binary_test`` ->
+pcsaft/pcsaft_feos.py ``mix_den_feos``), come from the mixture kernels of csrc/gnx_pcsaft_mix.hip:
+``mix_den`` for one point, ``mix_rho_batch`` for every point of every system in one launch, ``mixture_density`` /
+``mixture_state`` on device tensors.
+
 Parameter rows are ``[m, sigma (Å), epsilon/k (K), kappa_ab, epsilon_ab/k (K), mu (D), na, nb, mw]``; state rows are
 ``[T (K), P (Pa), phase, tp, value]`` (only T and P are read).  Densities are in mol/m³, pressures in Pa.
 """
@@ -33,25 +38,39 @@ def _device() -> torch.device:
     return torch.device("cuda", torch.cuda.current_device())
 
 
+def _upload(dev: torch.device, arrays: Sequence[Optional[np.ndarray]]) -> List[Optional[torch.Tensor]]:
+    """Host fp64 / int64 arrays packed into one 8-byte-element buffer and copied once: a flat device view of each, in
+    order (None stays None)."""
+    given = [a for a in arrays if a is not None]
+    ends = np.cumsum([a.size for a in given])
+    buf = np.empty(int(ends[-1]), dtype=np.int64)
+    flt = buf.view(np.float64)
+    for a, end in zip(given, ends):
+        (flt if a.dtype == np.float64 else buf)[end - a.size:end] = a.reshape(-1)
+    dbuf = torch.from_numpy(buf).to(dev)
+    dflt = dbuf.view(torch.float64)
+    views = iter([(dflt if a.dtype == np.float64 else dbuf)[end - a.size:end] for a, end in zip(given, ends)])
+    return [None if a is None else next(views) for a in arrays]
+
+
+def _outputs(dev: torch.device, n: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """both outputs in one buffer: value (fp64) | status (int32, padded to 8 bytes)"""
+    out = torch.empty(n + (n + 1) // 2, dtype=torch.int64, device=dev)
+    return out, out[:n].view(torch.float64), out[n:].view(torch.int32)[:n]
+
+
+def _download(out: torch.Tensor, n: int) -> Tuple[np.ndarray, np.ndarray]:
+    host = out.cpu().numpy()
+    return host[:n].view(np.float64).copy(), host[n:].view(np.int32)[:n].copy()
+
+
 def _run(kind: str, params: np.ndarray, owner: np.ndarray, T: np.ndarray, P: Optional[np.ndarray]
          ) -> Tuple[np.ndarray, np.ndarray]:
     """One upload, one launch, one download: (value [n] fp64, status [n] int32) for host arrays."""
     B, n = params.shape[0], owner.shape[0]
-    # every input in one 8-byte-element host buffer: params | T | P | owner
-    buf = np.empty(9 * B + 3 * n, dtype=np.int64)
-    flt = buf.view(np.float64)
-    flt[:9 * B] = params.reshape(-1)
-    flt[9 * B:9 * B + n] = T
-    if P is not None:
-        flt[9 * B + n:9 * B + 2 * n] = P
-    buf[9 * B + 2 * n:] = owner
     dev = _device()
-    dbuf = torch.from_numpy(buf).to(dev)
-    dflt = dbuf.view(torch.float64)
-    d_params, d_T, d_P, d_owner = dflt[:9 * B], dflt[9 * B:9 * B + n], dflt[9 * B + n:9 * B + 2 * n], dbuf[9 * B + 2 * n:]
-    # both outputs in one buffer: value (fp64) | status (int32, padded to 8 bytes)
-    out = torch.empty(n + (n + 1) // 2, dtype=torch.int64, device=dev)
-    value, status = out[:n].view(torch.float64), out[n:].view(torch.int32)[:n]
+    d_params, d_T, d_P, d_owner = _upload(dev, [params, T, P, owner])
+    out, value, status = _outputs(dev, n)
     lib = _lib.load()
     if kind == "rho":
         _lib.check(lib.gnx_pcsaft_density(_lib.handle(dev), d_params.data_ptr(), B, d_owner.data_ptr(),
@@ -59,8 +78,7 @@ def _run(kind: str, params: np.ndarray, owner: np.ndarray, T: np.ndarray, P: Opt
     else:
         _lib.check(lib.gnx_pcsaft_vapor_pressure(_lib.handle(dev), d_params.data_ptr(), B, d_owner.data_ptr(),
                                                  d_T.data_ptr(), n, value.data_ptr(), None, None, status.data_ptr()))
-    host = out.cpu().numpy()
-    return host[:n].view(np.float64).copy(), host[n:].view(np.int32)[:n].copy()
+    return _download(out, n)
 
 
 def _rows(parameters_batch: Sequence[Sequence[float]]) -> np.ndarray:
@@ -136,3 +154,120 @@ def vapor_pressure(params: torch.Tensor, T: torch.Tensor, owner: Optional[torch.
     """Tensor form on device tensors: params [B, 9] fp64, T [n] fp64, owner [n] int64 (default: point i uses row i)
     -> (psat [n] Pa, rho_l [n], rho_v [n] mol/m³, status [n] int32).  Asynchronous, on the current stream."""
     return ops.pcsaft_vapor_pressure(params, _owner(owner, T), T)
+
+
+# ---- mixtures of 1 to 4 components (csrc/gnx_pcsaft_mix.hip, DESIGN.md §4c) ------------------------------------------
+NC_MAX = 4
+
+
+def mixture_state(params: torch.Tensor, comp: torch.Tensor, x: torch.Tensor, T: torch.Tensor, rho: torch.Tensor,
+                  owner: Optional[torch.Tensor] = None, kij: Optional[torch.Tensor] = None,
+                  eab: Optional[torch.Tensor] = None
+                  ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Tensor form on device tensors: params [B, 9] fp64 pool of component rows, comp [M, nc] int64 rows of each
+    mixture (-1 = unused slot), x [n, nc] fp64 compositions (normalised by their sum), T [n] K, rho [n] mol/m³, owner [n]
+    int64 mixture of each point (default: point i is mixture i), kij / eab [M, nc, nc] fp64 (upper triangle read; NaN
+    in eab = combining rule) -> (a_res [n], p [n] Pa, dpdrho [n] Pa·m³/mol, status [n] int32).  Asynchronous, on the
+    current stream."""
+    return ops.pcsaft_mix_state(params, comp, kij, eab, _owner(owner, T), T, rho, x)
+
+
+def mixture_density(params: torch.Tensor, comp: torch.Tensor, x: torch.Tensor, T: torch.Tensor, P: torch.Tensor,
+                    owner: Optional[torch.Tensor] = None, kij: Optional[torch.Tensor] = None,
+                    eab: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Tensor form on device tensors, arguments as ``mixture_state`` with P [n] Pa in place of rho -> (rho [n] mol/m³,
+    status [n] int32).  Asynchronous, on the current stream."""
+    return ops.pcsaft_mix_density(params, comp, kij, eab, _owner(owner, T), T, P, x)
+
+
+def _run_mix(params: np.ndarray, comp: np.ndarray, kij: Optional[np.ndarray], eab: Optional[np.ndarray],
+             owner: np.ndarray, states: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
+    """One upload, one launch, one download: (rho [n] fp64, status [n] int32) for host arrays; states [n, 2 + nc]."""
+    B, (M, nc), n = params.shape[0], comp.shape, owner.shape[0]
+    dev = _device()
+    d_params, d_T, d_P, d_x, d_kij, d_eab, d_comp, d_owner = _upload(
+        dev, [params, states[:, 0], states[:, 1], states[:, 2:], kij, eab, comp, owner])
+    out, value, status = _outputs(dev, n)
+    ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+    _lib.check(_lib.load().gnx_pcsaft_mix_density(_lib.handle(dev), d_params.data_ptr(), B, d_comp.data_ptr(), ptr(d_kij),
+                                                  ptr(d_eab), M, nc, d_owner.data_ptr(), d_T.data_ptr(), d_P.data_ptr(),
+                                                  d_x.data_ptr(), n, value.data_ptr(), status.data_ptr()))
+    return _download(out, n)
+
+
+def _square(matrix: Any, k: int, nc: int, fill: float, what: str) -> np.ndarray:
+    """a [k, k] matrix placed in the corner of an [nc, nc] one"""
+    m = np.asarray(matrix, dtype=np.float64)
+    if m.shape != (k, k):
+        raise ValueError(f"{what} must be a {k} x {k} matrix, got shape {m.shape}")
+    out = np.full((nc, nc), fill, dtype=np.float64)
+    out[:k, :k] = m
+    return out
+
+
+def _pool(mixtures: Sequence[Sequence[Sequence[float]]], kij: Optional[Sequence[Any]], eab: Optional[Sequence[Any]]):
+    """pools the component rows of all mixtures: (params [B, 9], comp [M, nc], kij, eab [M, nc, nc] or None)"""
+    sizes = [len(rows) for rows in mixtures]
+    if not sizes or min(sizes) < 1 or max(sizes) > NC_MAX:
+        raise ValueError(f"a mixture has 1 to {NC_MAX} components, got {sizes}")
+    nc, M = max(sizes), len(mixtures)
+    params = np.concatenate([_rows(rows) for rows in mixtures])
+    comp = np.full((M, nc), -1, dtype=np.int64)
+    start = 0
+    for i, k in enumerate(sizes):
+        comp[i, :k] = np.arange(start, start + k)
+        start += k
+
+    def stack(mats, fill, what):
+        if mats is None or all(m is None for m in mats):
+            return None
+        if len(mats) != M:
+            raise ValueError(f"{len(mats)} {what} matrices for {M} mixtures")
+        return np.stack([np.full((nc, nc), fill) if m is None else _square(m, k, nc, fill, what)
+                         for m, k in zip(mats, sizes)])
+
+    return params, comp, stack(kij, 0.0, "kij"), stack(eab, np.nan, "epsilon_ab")
+
+
+def _states(table: Any, k: int, nc: int) -> np.ndarray:
+    """[rows, 2 + k] state table [T, P, x1..xk] widened to nc composition columns"""
+    t = np.asarray(table, dtype=np.float64)
+    t = t.reshape(t.shape[0], -1)
+    if t.shape[1] != 2 + k:
+        raise ValueError(f"a state row of a {k}-component mixture is [T, P, x1..x{k}], got {t.shape[1]} values")
+    out = np.zeros((t.shape[0], 2 + nc), dtype=np.float64)
+    out[:, :2 + k] = t
+    return out
+
+
+def mix_rho_batch(mixtures: List[List[List[Any]]], states_batch: List[Any], kij: Optional[List[Any]] = None
+                  ) -> List[np.ndarray]:
+    """Liquid densities (mol/m³) of every state of every non-empty table in one launch: ``mixtures[i]`` is the list of
+    component rows of system i, ``states_batch[i]`` its array of rows ``[T (K), P (Pa), x1..x_nc]``, ``kij[i]`` its
+    k_ij matrix or None.  One fp64 array per non-empty table, 0.0 where a point failed (the double loop of the
+    reference's demo/utils_binary.py ``binary_test`` as one call)."""
+    if len(mixtures) != len(states_batch):
+        raise ValueError(f"{len(mixtures)} mixtures but {len(states_batch)} state tables")
+    tables = [(i, s) for i, s in enumerate(states_batch) if np.shape(s)[0] > 0]
+    if not tables:
+        return []
+    params, comp, d_kij, _ = _pool(mixtures, kij, None)
+    nc = comp.shape[1]
+    states = np.concatenate([_states(s, len(mixtures[i]), nc) for i, s in tables])
+    owner = np.concatenate([np.full(np.shape(s)[0], i, dtype=np.int64) for i, s in tables])
+    value, _ = _run_mix(params, comp, d_kij, None, owner, states)
+    cuts = np.cumsum([np.shape(s)[0] for _, s in tables])[:-1]
+    return [v.copy() for v in np.split(value, cuts)]
+
+
+def mix_den(parameters: Sequence[Sequence[float]], state: Sequence[float], kij_matrix: Optional[Any] = None,
+            epsilon_ab: Optional[Any] = None) -> float:
+    """Mixture liquid density (mol/m³) at ``state = [T (K), P (Pa), x1, x2, ...]`` of the components ``parameters``
+    (reference ``mix_den_feos``); raises ``RuntimeError`` where no liquid root is found."""
+    params, comp, kij, eab = _pool([parameters], [kij_matrix], [epsilon_ab])
+    states = _states([list(state)], len(parameters), comp.shape[1])
+    value, status = _run_mix(params, comp, kij, eab, np.zeros(1, dtype=np.int64), states)
+    if status[0] != STATUS_OK:
+        raise RuntimeError(f"PC-SAFT mixture density failed at state {list(state)}: "
+                           f"{_REASON.get(int(status[0]), int(status[0]))}")
+    return float(value[0])

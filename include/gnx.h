@@ -96,7 +96,9 @@ enum {
   GNX_K_ATTN_BWD = 19,          /* its destination- and source-side backward passes (gnx_transformer_attn_bwd) */
   GNX_K_PCSAFT_RHO = 20,        /* PC-SAFT liquid density at (T, P), fp64 (gnx_pcsaft_density) */
   GNX_K_PCSAFT_VP = 21,         /* PC-SAFT vapour pressure at T, fp64 (gnx_pcsaft_vapor_pressure) */
-  GNX_K_COUNT = 22
+  GNX_K_PCSAFT_MIX_STATE = 22,  /* mixture PC-SAFT a_res, p, dp/drho at (T, rho, x), fp64 (gnx_pcsaft_mix_state) */
+  GNX_K_PCSAFT_MIX_RHO = 23,    /* mixture PC-SAFT liquid density at (T, P, x), fp64 (gnx_pcsaft_mix_density) */
+  GNX_K_COUNT = 24
 };
 /* start recording a HIP event pair around every launch of the kernels whose id bit is set in kernel_mask
  * (bit k = GNX_K_* id k).  Events go on the handle's stream, i.e. the stream the kernels run on. */
@@ -430,6 +432,31 @@ int32_t gnx_pcsaft_density(gnx_handle* h, const double* params, int64_t B, const
  * PhaseEquilibrium.pure).  rho_l / rho_v may be NULL. */
 int32_t gnx_pcsaft_vapor_pressure(gnx_handle* h, const double* params, int64_t B, const int64_t* owner, const double* T,
                                   int64_t n, double* psat, double* rho_l, double* rho_v, int32_t* status);
+
+/* ---- mixture PC-SAFT, 1 to 4 components (fp64) ------------------------------------------------------------------ */
+/* [3P] feos 0.8 PC-SAFT mixtures (ref: demo/utils_binary.py:116-160 binary_test -> pcsaft/pcsaft_feos.py:311-346
+ * mix_den_feos).  params [B, 9] fp64: the pool of component rows (layout as above).  mix_comp [M, nc] int64: the rows of
+ * params that make up each mixture, -1 = unused slot (its x is ignored); 1 <= nc <= 4.  mix_kij [M, nc, nc] fp64 or NULL
+ * (all zero): binary interaction parameters; mix_eab [M, nc, nc] fp64 or NULL: cross association energies eps_ab,ij/k,
+ * a NaN entry (or NULL) = the combining rule (eps_ab,i + eps_ab,j)/2.  Both matrices are read from their upper triangle
+ * (entry [min(i,j)][max(i,j)]), which makes them symmetric; their diagonals are ignored.  Point i belongs to mixture
+ * owner[i] (int64) and has the composition x[i, 0..nc) (fp64, normalised by its sum; a component with x = 0 contributes
+ * exactly nothing and its row is not read).  status per point: 0 = ok, 1 = no root / not converged within the fixed
+ * iteration caps, 3 = invalid input (owner outside [0, M), a component index outside [0, B) and not -1, no used slot,
+ * negative or non-finite x, zero sum of x, invalid row of a component that is present, non-finite k_ij, non-positive
+ * or non-finite T / P / rho, rho at or beyond packing fraction 1).  Every output of a point with status != 0 is exactly
+ * 0.0.  One lane per point, one launch, no atomics (same input, same bits).  DESIGN.md §4c. */
+/* at the molar density rho[i] (mol/m^3): a_res[i] = reduced residual Helmholtz energy per molecule, p[i] (Pa),
+ * dpdrho[i] = dp/drho at constant T, x (Pa m^3/mol) */
+int32_t gnx_pcsaft_mix_state(gnx_handle* h, const double* params, int64_t B, const int64_t* mix_comp,
+                             const double* mix_kij, const double* mix_eab, int64_t M, int32_t nc, const int64_t* owner,
+                             const double* T, const double* rho, const double* x, int64_t n, double* a_res, double* p,
+                             double* dpdrho, int32_t* status);
+/* rho[i] (mol/m^3) = the highest-density root of P(rho; T[i], x[i]) = P[i] with dP/drho > 0 */
+int32_t gnx_pcsaft_mix_density(gnx_handle* h, const double* params, int64_t B, const int64_t* mix_comp,
+                               const double* mix_kij, const double* mix_eab, int64_t M, int32_t nc,
+                               const int64_t* owner, const double* T, const double* P, const double* x, int64_t n,
+                               double* rho, int32_t* status);
 
 /* ---- contiguous segment reduce: global pool (ref: train/models.py:218-225, 587-595) ------------------------ */
 enum { GNX_POOL_ADD = 0, GNX_POOL_MEAN = 1, GNX_POOL_MAX = 2 };

@@ -3,7 +3,11 @@ density and the vapour pressure, kernel time (events around the launch) and end-
 time (upload, launch, download), next to the CPU oracle (tests/pcsaft_ref.py) timed on a sample of the same points and
 scaled to the call size.  Points: the ThermoML fixture's molecules and states, repeated.
 
-Usage: python tools/pcsaft_bench.py [--sizes 1000,100000,1000000] [--oracle-sample 20] [--out FILE.json]
+With ``--mixture`` it times the mixture kernels of csrc/gnx_pcsaft_mix.hip instead, on the points of
+the binary ThermoML fixture, repeated: the density and the state kernel, ``mix_rho_batch`` end to end, and the mixture
+oracle (tests/pcsaft_mix_ref.py) on a sample.
+
+Usage: python tools/pcsaft_bench.py [--mixture] [--sizes 1000,100000,1000000] [--oracle-sample 20] [--out FILE.json]
 """
 import argparse
 import json
@@ -35,12 +39,51 @@ def _kernel_ms(fn, reps=3):
     return best
 
 
+def _mixture(args, dev):
+    from tests import pcsaft_mix_cases as C
+    from tests import pcsaft_mix_ref as MR
+    params, comp, owner, T, P, x, _ = C.fixture_points()
+    t0 = time.perf_counter()
+    step = max(1, len(owner) // args.oracle_sample)
+    sample = range(0, len(owner), step)
+    ref = [MR.density(MR.Mixture(params[comp[owner[j]]], x[j]), T[j], P[j]) for j in sample]
+    oracle = (time.perf_counter() - t0) / len(ref)
+    d_params, d_comp = torch.from_numpy(params).to(dev), torch.from_numpy(comp).to(dev)
+    res = []
+    for n in [int(s) for s in args.sizes.split(",")]:
+        idx = np.arange(n) % len(owner)
+        o, t, pp, xx = (torch.from_numpy(np.ascontiguousarray(a[idx])).to(dev) for a in (owner, T, P, x))
+        rho, _ = pcsaft.mixture_density(d_params, d_comp, xx, t, pp, o)
+        k_rho = _kernel_ms(lambda: pcsaft.mixture_density(d_params, d_comp, xx, t, pp, o))
+        k_state = _kernel_ms(lambda: pcsaft.mixture_state(d_params, d_comp, xx, t, rho, o))
+        mixtures = [s["params"] for s in C.systems()]
+        tables = [np.column_stack([T[idx][owner[idx] == i], P[idx][owner[idx] == i], x[idx][owner[idx] == i]])
+                  for i in range(len(mixtures))]
+        pcsaft.mix_rho_batch(mixtures, tables)
+        t0 = time.perf_counter()
+        pcsaft.mix_rho_batch(mixtures, tables)
+        rec = dict(points=n, mix_density_kernel_ms=k_rho, mix_state_kernel_ms=k_state,
+                   mix_rho_batch_ms=(time.perf_counter() - t0) * 1e3, oracle_density_ms_est=oracle * n * 1e3)
+        print(json.dumps(rec))
+        res.append(rec)
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sizes", default="1000,100000,1000000")
     ap.add_argument("--oracle-sample", type=int, default=20)
+    ap.add_argument("--mixture", action="store_true")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    if args.mixture:
+        dev = torch.device("cuda", torch.cuda.current_device())
+        res = _mixture(args, dev)
+        if args.out:
+            with open(args.out, "w") as fh:
+                json.dump(dict(device=torch.cuda.get_device_name(dev), oracle_sample=args.oracle_sample, results=res), fh,
+                          indent=1)
+        return
     mols = json.load(open(os.path.join(ROOT, "tests", "golden", "pcsaft_thermoml.json")))["molecules"]
     rows = np.array([m["params"] for m in mols])
     rho_pts = np.array([(i, s[0], s[1]) for i, m in enumerate(mols) for s in m["rho"]])
