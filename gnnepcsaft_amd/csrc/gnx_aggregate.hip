@@ -47,6 +47,11 @@ __device__ __forceinline__ void vstore(float* p, const float (&r)[VEC]) {
   }
 }
 
+// ReLU and running maximum that keep a NaN, as torch.relu and scatter_reduce_(amax) do: fmaxf returns its other operand,
+// so fmaxf(NaN, 0) is 0 and a NaN activation would vanish from the message sum / the pooled maximum
+__device__ __forceinline__ float relu_keep_nan(float r) { return (r < 0.f) ? 0.f : r; }
+__device__ __forceinline__ float max_keep_nan(float s, float a) { return (a > s || a != a) ? a : s; }
+
 // clamp / mask constants of [3P] StdAggregation: var.clamp(min=1e-5).sqrt(), masked to 0 where <= sqrt(1e-5)
 #define STD_VAR_MIN 1e-5f
 #define STD_MASK_AT 0.0031622776601683794f
@@ -351,7 +356,7 @@ __global__ void __launch_bounds__(256) k_edge_combine_fwd(const float* __restric
 #pragma unroll
   for (int v = 0; v < VEC; ++v) {
     float r = (a[v] + b[v]) + e[v];
-    o[v] = relu ? fmaxf(r, 0.f) : r;
+    o[v] = relu ? relu_keep_nan(r) : r;
   }
   vstore<VEC>(h1 + p * H + c, o);
 }
@@ -532,7 +537,7 @@ __global__ void __launch_bounds__(256) k_gine_fwd(const float* __restrict__ x, c
     vload<VEC>(a, x + (int64_t)src[p] * H + c);
     vload<VEC>(e, Le + (int64_t)code[p] * H + c);
 #pragma unroll
-    for (int v = 0; v < VEC; ++v) s[v] += fmaxf(a[v] + e[v], 0.f);
+    for (int v = 0; v < VEC; ++v) s[v] += relu_keep_nan(a[v] + e[v]);
   }
   vload<VEC>(xi, x + n * H + c);
   const float k = 1.0f + eps;
@@ -773,13 +778,14 @@ __global__ void __launch_bounds__(256) k_pool_fwd(const float* __restrict__ x, c
 #pragma unroll
     for (int j = 0; j < 4; ++j)
 #pragma unroll
-      for (int v = 0; v < VEC; ++v) s[v] = (mode == GNX_POOL_MAX) ? fmaxf(s[v], a[j][v]) : __fadd_rn(s[v], a[j][v]);
+      for (int v = 0; v < VEC; ++v)
+        s[v] = (mode == GNX_POOL_MAX) ? max_keep_nan(s[v], a[j][v]) : __fadd_rn(s[v], a[j][v]);
   }
   for (; p < p1; ++p) {
     float a[VEC];
     vload<VEC>(a, x + (int64_t)p * H + c);
 #pragma unroll
-    for (int v = 0; v < VEC; ++v) s[v] = (mode == GNX_POOL_MAX) ? fmaxf(s[v], a[v]) : __fadd_rn(s[v], a[v]);
+    for (int v = 0; v < VEC; ++v) s[v] = (mode == GNX_POOL_MAX) ? max_keep_nan(s[v], a[v]) : __fadd_rn(s[v], a[v]);
   }
   int d = p1 - p0;
 #pragma unroll
@@ -818,7 +824,8 @@ __global__ void __launch_bounds__(256) k_pool_bwd(const float* __restrict__ dout
       float a[VEC], o[VEC];
       vload<VEC>(a, x + (int64_t)p * H + c);
 #pragma unroll
-      for (int v = 0; v < VEC; ++v) o[v] = (a[v] == mx[v]) ? g[v] / nt[v] : 0.f;
+      for (int v = 0; v < VEC; ++v)  // a NaN maximum ties with nothing: autograd's g / 0 * 0 is NaN on the whole segment
+        o[v] = (a[v] == mx[v]) ? g[v] / nt[v] : (mx[v] != mx[v] ? mx[v] : 0.f);
       vstore<VEC>(dx + (int64_t)p * H + c, o);
     }
   } else {

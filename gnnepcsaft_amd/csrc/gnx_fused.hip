@@ -209,7 +209,7 @@ __global__ void __launch_bounds__(512, 1) k_pna_edge_fwd(edge_fwd_args g) {
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         const float r = (ga[i][0][j] + ga[i][1][j]) + ga[i][2][j];
-        hv[i][j] = ok ? fmaxf(r, 0.f) : 0.f;
+        hv[i][j] = (ok && !(r < 0.f)) ? r : 0.f;  // ReLU that keeps a NaN, as k_edge_combine_fwd's
       }
       if (ok && g.h1 != nullptr)
         *reinterpret_cast<f32x4*>(g.h1 + (int64_t)(b.e0 + ar + 16 * i) * H + coff + ak) = hv[i];

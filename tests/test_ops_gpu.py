@@ -2,7 +2,7 @@
 
 Tolerances: integer / index work bit-exact; min/max/mean of the scatter-aggregate bit-exact (same summation order as
 the CPU scatter); everything that re-associates fp32 sums within 1e-5 norm-wise relative (max|a-b|/max|ref|), the
-north-star tolerance.
+north-star tolerance.  The gather / scatter kernels are held entry by entry in tests/test_graph_sums_gpu.py.
 """
 import math
 
