@@ -22,8 +22,8 @@ POOL_ADD, POOL_MEAN, POOL_MAX = 0, 1, 2
 K_NONE, K_PNA_AGG_FWD, K_PNA_AGG_BWD, K_GEMM_WS, K_GEMM_WGRAD, K_GINE_AGG_FWD, K_GINE_AGG_BWD, K_EDGE_COMBINE_FWD, \
     K_EDGE_COMBINE_BWD, K_BN_FWD, K_BN_BWD, K_GEMM_TILED, K_GEMM_SMALL, K_GEMM_WGRAD_BATCHED, K_KEY_SEGMENT_SUM, \
     K_EMBED, K_PNA_EDGE_FWD, K_PNA_EDGE_BWD, K_ATTN_FWD, K_ATTN_BWD, K_PCSAFT_RHO, K_PCSAFT_VP, \
-    K_PCSAFT_MIX_STATE, K_PCSAFT_MIX_RHO = range(24)
-K_COUNT = 24
+    K_PCSAFT_MIX_STATE, K_PCSAFT_MIX_RHO, K_PCSAFT_MIX_LNPHI_STATE, K_PCSAFT_MIX_LNPHI = range(26)
+K_COUNT = 26
 KERNEL_GROUPS = {K_PNA_AGG_FWD: "pna_aggregate_fwd", K_PNA_AGG_BWD: "pna_aggregate_bwd", K_GEMM_WS: "gemm_weights_stationary",
                  K_GEMM_WGRAD: "weight_gradient", K_GINE_AGG_FWD: "gine_aggregate_fwd", K_GINE_AGG_BWD: "gine_aggregate_bwd",
                  K_EDGE_COMBINE_FWD: "edge_combine_fwd", K_EDGE_COMBINE_BWD: "edge_combine_bwd", K_BN_FWD: "batchnorm_fwd",
@@ -32,7 +32,8 @@ KERNEL_GROUPS = {K_PNA_AGG_FWD: "pna_aggregate_fwd", K_PNA_AGG_BWD: "pna_aggrega
                  K_PNA_EDGE_FWD: "pna_edge_fused_fwd", K_PNA_EDGE_BWD: "pna_edge_fused_bwd",
                  K_ATTN_FWD: "transformer_attn_fwd", K_ATTN_BWD: "transformer_attn_bwd",
                  K_PCSAFT_RHO: "pcsaft_density", K_PCSAFT_VP: "pcsaft_vapor_pressure",
-                 K_PCSAFT_MIX_STATE: "pcsaft_mix_state", K_PCSAFT_MIX_RHO: "pcsaft_mix_density"}
+                 K_PCSAFT_MIX_STATE: "pcsaft_mix_state", K_PCSAFT_MIX_RHO: "pcsaft_mix_density",
+                 K_PCSAFT_MIX_LNPHI_STATE: "pcsaft_mix_lnphi_state", K_PCSAFT_MIX_LNPHI: "pcsaft_mix_lnphi"}
 
 
 class GnxError(RuntimeError):
@@ -173,6 +174,10 @@ SIGNATURES = {
     "gnx_pcsaft_mix_state": (_i32, [_vp, _vp, _i64, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp,
                                     _vp]),
     "gnx_pcsaft_mix_density": (_i32, [_vp, _vp, _i64, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _vp]),
+    "gnx_pcsaft_mix_lnphi_state": (_i32, [_vp, _vp, _i64, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _vp,
+                                          _vp]),
+    "gnx_pcsaft_mix_lnphi": (_i32, [_vp, _vp, _i64, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp,
+                                    _vp]),
     "gnx_segment_pool_fwd": (_i32, [_vp, _vp, _vp, _i64, _i32, _i32, _vp]),
     "gnx_segment_pool_bwd": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp]),
     "gnx_batchnorm_workspace_bytes": (_sz, [_i64, _i32]),

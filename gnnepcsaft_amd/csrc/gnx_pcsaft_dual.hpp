@@ -1,5 +1,6 @@
-// Second-order forward dual in one variable (value, first and second derivative) and the closed-form site fraction of
-// one associating component, shared by gnx_pcsaft.hip (pure components) and gnx_pcsaft_mix.hip (mixtures).
+// Second-order forward dual in one variable (value, first and second derivative), first-order forward dual in N
+// variables (value and gradient) and the closed-form site fraction of one associating component, shared by
+// gnx_pcsaft.hip (pure components) and gnx_pcsaft_mix.hpp (mixtures).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -45,6 +46,103 @@ __device__ __forceinline__ double value_of(double a) { return a; }
 __device__ __forceinline__ double exp(double a) { return ::exp(a); }
 __device__ __forceinline__ double log(double a) { return ::log(a); }
 __device__ __forceinline__ double sqrt(double a) { return ::sqrt(a); }
+
+// ---- first-order forward "gradient" dual: a value and its partial derivatives in N independent variables -------------
+// The operator set of D2.  A double converts to a constant (all partials zero), so code written for double or D2
+// coefficients instantiates on it unchanged.
+template <int N>
+struct DG {
+  double v, g[N];
+  DG() = default;
+  __device__ __forceinline__ DG(double c) : v(c) {
+#pragma unroll
+    for (int k = 0; k < N; ++k) g[k] = 0.0;
+  }
+  // the k-th independent variable at the value c
+  __device__ __forceinline__ static DG seed(double c, int k) {
+    DG r(c);
+    r.g[k] = 1.0;
+    return r;
+  }
+};
+// f(a) with f'(a) = fp, and f(a, b) with the partials fa, fb
+template <int N>
+__device__ __forceinline__ DG<N> dg_chain(double f, double fp, const DG<N>& a) {
+  DG<N> r;
+  r.v = f;
+#pragma unroll
+  for (int k = 0; k < N; ++k) r.g[k] = fp * a.g[k];
+  return r;
+}
+template <int N>
+__device__ __forceinline__ DG<N> dg_chain(double f, double fa, const DG<N>& a, double fb, const DG<N>& b) {
+  DG<N> r;
+  r.v = f;
+#pragma unroll
+  for (int k = 0; k < N; ++k) r.g[k] = fa * a.g[k] + fb * b.g[k];
+  return r;
+}
+template <int N>
+__device__ __forceinline__ DG<N> operator+(const DG<N>& a, const DG<N>& b) { return dg_chain(a.v + b.v, 1.0, a, 1.0, b); }
+template <int N>
+__device__ __forceinline__ DG<N> operator-(const DG<N>& a, const DG<N>& b) { return dg_chain(a.v - b.v, 1.0, a, -1.0, b); }
+template <int N>
+__device__ __forceinline__ DG<N> operator-(const DG<N>& a) { return dg_chain(-a.v, -1.0, a); }
+template <int N>
+__device__ __forceinline__ DG<N> operator+(const DG<N>& a, double b) { return dg_chain(a.v + b, 1.0, a); }
+template <int N>
+__device__ __forceinline__ DG<N> operator+(double b, const DG<N>& a) { return dg_chain(a.v + b, 1.0, a); }
+template <int N>
+__device__ __forceinline__ DG<N> operator-(const DG<N>& a, double b) { return dg_chain(a.v - b, 1.0, a); }
+template <int N>
+__device__ __forceinline__ DG<N> operator-(double b, const DG<N>& a) { return dg_chain(b - a.v, -1.0, a); }
+template <int N>
+__device__ __forceinline__ DG<N> operator*(const DG<N>& a, double b) { return dg_chain(a.v * b, b, a); }
+template <int N>
+__device__ __forceinline__ DG<N> operator*(double b, const DG<N>& a) { return dg_chain(a.v * b, b, a); }
+template <int N>
+__device__ __forceinline__ DG<N> operator*(const DG<N>& a, const DG<N>& b) { return dg_chain(a.v * b.v, b.v, a, a.v, b); }
+template <int N>
+__device__ __forceinline__ DG<N>& operator+=(DG<N>& a, const DG<N>& b) { return a = a + b; }
+template <int N>
+__device__ __forceinline__ DG<N>& operator*=(DG<N>& a, const DG<N>& b) { return a = a * b; }
+template <int N>
+__device__ __forceinline__ DG<N>& operator*=(DG<N>& a, double b) { return a = a * b; }
+template <int N>
+__device__ __forceinline__ DG<N> operator/(const DG<N>& a, const DG<N>& b) {
+  const double q = a.v / b.v;
+  return dg_chain(q, 1.0 / b.v, a, -q / b.v, b);
+}
+template <int N>
+__device__ __forceinline__ DG<N> operator/(const DG<N>& a, double b) { return dg_chain(a.v / b, 1.0 / b, a); }
+template <int N>
+__device__ __forceinline__ DG<N> operator/(double a, const DG<N>& b) {
+  const double q = a / b.v;
+  return dg_chain(q, -q / b.v, b);
+}
+template <int N>
+__device__ __forceinline__ DG<N> exp(const DG<N>& a) {
+  const double e = ::exp(a.v);
+  return dg_chain(e, e, a);
+}
+template <int N>
+__device__ __forceinline__ DG<N> log(const DG<N>& a) { return dg_chain(::log(a.v), 1.0 / a.v, a); }
+template <int N>
+__device__ __forceinline__ DG<N> sqrt(const DG<N>& a) {
+  const double s = ::sqrt(a.v);
+  return dg_chain(s, 0.5 / s, a);
+}
+template <int N>
+__device__ __forceinline__ double value_of(const DG<N>& a) { return a.v; }
+// a coefficient that multiplies nothing in: its value and, on a dual, every partial is zero
+__device__ __forceinline__ bool is_zero(double a) { return a == 0.0; }
+template <int N>
+__device__ __forceinline__ bool is_zero(const DG<N>& a) {
+  bool z = a.v == 0.0;
+#pragma unroll
+  for (int k = 0; k < N; ++k) z = z && a.g[k] == 0.0;
+  return z;
+}
 
 // positive root of q X^2 + u X - 1 = 0 (q > 0), the mass-action law of one site type: X_A with u = 1 + (nb - na) x,
 // q = na x.  Written so that neither branch cancels: 2 / (u + sqrt(u^2 + 4q)) for u >= 0, (sqrt(u^2 + 4q) - u) / 2q

@@ -1085,6 +1085,44 @@ def pcsaft_mix_density(params: torch.Tensor, comp: torch.Tensor, kij: Optional[t
     return rho, status
 
 
+def pcsaft_mix_lnphi_state(params: torch.Tensor, comp: torch.Tensor, kij: Optional[torch.Tensor],
+                           eab: Optional[torch.Tensor], owner: torch.Tensor, T: torch.Tensor, rho: torch.Tensor,
+                           x: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Mixture PC-SAFT fugacity coefficients at (T, rho, x) (gnx_pcsaft_mix_lnphi_state): arguments as
+    ``pcsaft_mix_state`` -> (lnphi [n, nc], Z [n], status [n] int32); NaN in a -1 slot and in the whole row where
+    status != 0.  A used slot with x = 0 stays in the mixture (infinite dilution)."""
+    params, comp, kij, eab, owner, T, rho, x = _pcsaft_mix_args(params, comp, kij, eab, owner, T, rho, x,
+                                                                "pcsaft_mix_lnphi_state")
+    n, nc, dev = T.numel(), comp.size(1), params.device
+    lnphi = torch.empty(n, nc, dtype=torch.float64, device=dev)
+    Z = torch.empty(n, dtype=torch.float64, device=dev)
+    status = torch.empty(n, dtype=torch.int32, device=dev)
+    check(_lib.load().gnx_pcsaft_mix_lnphi_state(handle(dev), params.data_ptr(), params.size(0), comp.data_ptr(),
+                                                 _ptr(kij), _ptr(eab), comp.size(0), nc, owner.data_ptr(), T.data_ptr(),
+                                                 rho.data_ptr(), x.data_ptr(), n, lnphi.data_ptr(), Z.data_ptr(),
+                                                 status.data_ptr()))
+    return lnphi, Z, status
+
+
+def pcsaft_mix_lnphi(params: torch.Tensor, comp: torch.Tensor, kij: Optional[torch.Tensor], eab: Optional[torch.Tensor],
+                     owner: torch.Tensor, T: torch.Tensor, P: torch.Tensor, x: torch.Tensor, pure: bool = False
+                     ) -> Tuple[torch.Tensor, torch.Tensor, Optional[torch.Tensor], torch.Tensor]:
+    """Mixture PC-SAFT fugacity coefficients at the liquid root of (T, P, x) (gnx_pcsaft_mix_lnphi): arguments as
+    ``pcsaft_mix_density`` -> (rho [n] mol/m^3, the bits of ``pcsaft_mix_density``; lnphi [n, nc]; lnphi_pure [n, nc] if
+    ``pure`` else None: each component alone at its own liquid root, NaN where it has none; status [n] int32)."""
+    params, comp, kij, eab, owner, T, P, x = _pcsaft_mix_args(params, comp, kij, eab, owner, T, P, x, "pcsaft_mix_lnphi")
+    n, nc, dev = T.numel(), comp.size(1), params.device
+    rho = torch.empty(n, dtype=torch.float64, device=dev)
+    lnphi = torch.empty(n, nc, dtype=torch.float64, device=dev)
+    lnphi_pure = torch.empty(n, nc, dtype=torch.float64, device=dev) if pure else None
+    status = torch.empty(n, dtype=torch.int32, device=dev)
+    check(_lib.load().gnx_pcsaft_mix_lnphi(handle(dev), params.data_ptr(), params.size(0), comp.data_ptr(), _ptr(kij),
+                                           _ptr(eab), comp.size(0), nc, owner.data_ptr(), T.data_ptr(), P.data_ptr(),
+                                           x.data_ptr(), n, rho.data_ptr(), lnphi.data_ptr(), _ptr(lnphi_pure),
+                                           status.data_ptr()))
+    return rho, lnphi, lnphi_pure, status
+
+
 _POOL = {"add": _lib.POOL_ADD, "sum": _lib.POOL_ADD, "mean": _lib.POOL_MEAN, "max": _lib.POOL_MAX}
 
 

@@ -15,6 +15,13 @@ pcsaft/pcsaft_feos.py ``mix_den_feos``), come from the mixture kernels of csrc/g
 ``mix_den`` for one point, ``mix_rho_batch`` for every point of every system in one launch, ``mixture_density`` /
 ``mixture_state`` on device tensors.
 
+Fugacity coefficients of a liquid mixture, ln phi_i at (T, P, x), and what the reference builds on them with one feos
+state (pcsaft/pcsaft_feos.py): ``mix_ln_fugacity_coefficient``, ``mix_ln_fugacity_coefficient_pure``,
+``mix_ln_activity_coefficient``, ``mix_e_gibbs_energy``, ``mix_r_gibbs_energy`` and ``mix_gibbs_energy`` for one point,
+``mix_ln_phi_batch`` for every point of every system in one launch, ``mixture_ln_phi`` / ``mixture_ln_phi_state`` on
+device tensors (csrc/gnx_pcsaft_mix_phi.hip).  There a component with x = 0 stays in the mixture: its ln phi is the
+value at infinite dilution.  x is normalised by its sum, and 0 ln 0 counts as 0 in ``mix_gibbs_energy``.
+
 Parameter rows are ``[m, sigma (Å), epsilon/k (K), kappa_ab, epsilon_ab/k (K), mu (D), na, nb, mw]``; state rows are
 ``[T (K), P (Pa), phase, tp, value]`` (only T and P are read).  Densities are in mol/m³, pressures in Pa.
 """
@@ -180,6 +187,27 @@ def mixture_density(params: torch.Tensor, comp: torch.Tensor, x: torch.Tensor, T
     return ops.pcsaft_mix_density(params, comp, kij, eab, _owner(owner, T), T, P, x)
 
 
+def mixture_ln_phi_state(params: torch.Tensor, comp: torch.Tensor, x: torch.Tensor, T: torch.Tensor, rho: torch.Tensor,
+                         owner: Optional[torch.Tensor] = None, kij: Optional[torch.Tensor] = None,
+                         eab: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Tensor form on device tensors, arguments as ``mixture_state`` -> (lnphi [n, nc], Z [n], status [n] int32): the
+    fugacity coefficients ln phi_i and the compressibility factor at the molar density rho.  NaN in a -1 slot and in the
+    whole row where status != 0; a used slot with x = 0 reports its infinite-dilution value.  Asynchronous, on the
+    current stream."""
+    return ops.pcsaft_mix_lnphi_state(params, comp, kij, eab, _owner(owner, T), T, rho, x)
+
+
+def mixture_ln_phi(params: torch.Tensor, comp: torch.Tensor, x: torch.Tensor, T: torch.Tensor, P: torch.Tensor,
+                   owner: Optional[torch.Tensor] = None, kij: Optional[torch.Tensor] = None,
+                   eab: Optional[torch.Tensor] = None, pure: bool = False
+                   ) -> Tuple[torch.Tensor, torch.Tensor, Optional[torch.Tensor], torch.Tensor]:
+    """Tensor form on device tensors, arguments as ``mixture_density`` -> (rho [n] mol/m³, lnphi [n, nc], lnphi_pure
+    [n, nc] or None, status [n] int32): the liquid root of ``mixture_density`` (the same bits), ln phi_i there and, with
+    ``pure``, ln phi of each component alone at its own liquid root at the same T and P (NaN where it has none; the
+    status stays 0).  Asynchronous, on the current stream."""
+    return ops.pcsaft_mix_lnphi(params, comp, kij, eab, _owner(owner, T), T, P, x, pure)
+
+
 def _run_mix(params: np.ndarray, comp: np.ndarray, kij: Optional[np.ndarray], eab: Optional[np.ndarray],
              owner: np.ndarray, states: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
     """One upload, one launch, one download: (rho [n] fp64, status [n] int32) for host arrays; states [n, 2 + nc]."""
@@ -271,3 +299,115 @@ def mix_den(parameters: Sequence[Sequence[float]], state: Sequence[float], kij_m
         raise RuntimeError(f"PC-SAFT mixture density failed at state {list(state)}: "
                            f"{_REASON.get(int(status[0]), int(status[0]))}")
     return float(value[0])
+
+
+def _run_mix_phi(params: np.ndarray, comp: np.ndarray, kij: Optional[np.ndarray], eab: Optional[np.ndarray],
+                 owner: np.ndarray, states: np.ndarray, pure: bool
+                 ) -> Tuple[np.ndarray, Optional[np.ndarray], np.ndarray]:
+    """One upload, one launch, one download: (lnphi [n, nc], lnphi_pure [n, nc] or None, status [n] int32) for host
+    arrays; states [n, 2 + nc]."""
+    B, (M, nc), n = params.shape[0], comp.shape, owner.shape[0]
+    dev = _device()
+    d_params, d_T, d_P, d_x, d_kij, d_eab, d_comp, d_owner = _upload(
+        dev, [params, states[:, 0], states[:, 1], states[:, 2:], kij, eab, comp, owner])
+    # every output in one buffer: rho [n] | lnphi [n, nc] | lnphi_pure [n, nc] | status (int32, padded to 8 bytes)
+    w = n * nc
+    end = n + w * (2 if pure else 1)
+    out = torch.empty(end + (n + 1) // 2, dtype=torch.int64, device=dev)
+    flt = out.view(torch.float64)
+    status = out[end:].view(torch.int32)[:n]
+    ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+    _lib.check(_lib.load().gnx_pcsaft_mix_lnphi(_lib.handle(dev), d_params.data_ptr(), B, d_comp.data_ptr(), ptr(d_kij),
+                                                ptr(d_eab), M, nc, d_owner.data_ptr(), d_T.data_ptr(), d_P.data_ptr(),
+                                                d_x.data_ptr(), n, flt[:n].data_ptr(), flt[n:n + w].data_ptr(),
+                                                flt[n + w:end].data_ptr() if pure else None, status.data_ptr()))
+    host = out.cpu().numpy()
+    val = host[:end].view(np.float64)
+    return (val[n:n + w].reshape(n, nc).copy(), val[n + w:end].reshape(n, nc).copy() if pure else None,
+            host[end:].view(np.int32)[:n].copy())
+
+
+def _phi_point(what: str, parameters: Sequence[Sequence[float]], state: Sequence[float], kij_matrix: Optional[Any],
+               epsilon_ab: Optional[Any], pure: bool) -> Tuple[np.ndarray, Optional[np.ndarray], np.ndarray]:
+    """(lnphi [k], lnphi_pure [k] or None, x [k] normalised by its sum) of one point; RuntimeError on a status != 0"""
+    k = len(parameters)
+    params, comp, kij, eab = _pool([parameters], [kij_matrix], [epsilon_ab])
+    states = _states([list(state)], k, comp.shape[1])
+    lnphi, lnphi_pure, status = _run_mix_phi(params, comp, kij, eab, np.zeros(1, dtype=np.int64), states, pure)
+    if status[0] != STATUS_OK:
+        raise RuntimeError(f"PC-SAFT mixture {what} failed at state {list(state)}: "
+                           f"{_REASON.get(int(status[0]), int(status[0]))}")
+    x = states[0, 2:2 + k]
+    return lnphi[0, :k], None if lnphi_pure is None else lnphi_pure[0, :k], x / x.sum()
+
+
+def mix_ln_fugacity_coefficient(parameters: Sequence[Sequence[float]], state: Sequence[float],
+                                kij_matrix: Optional[Any] = None, epsilon_ab: Optional[Any] = None) -> np.ndarray:
+    """ln phi_i of every component at the liquid root of ``state = [T (K), P (Pa), x1, x2, ...]`` (reference
+    ``mix_ln_fugacity_coefficient``), the infinite-dilution value where x_i = 0; raises ``RuntimeError`` where no liquid
+    root is found."""
+    return _phi_point("fugacity coefficient", parameters, state, kij_matrix, epsilon_ab, False)[0]
+
+
+def mix_ln_fugacity_coefficient_pure(parameters: Sequence[Sequence[float]], state: Sequence[float],
+                                     kij_matrix: Optional[Any] = None, epsilon_ab: Optional[Any] = None) -> np.ndarray:
+    """ln phi of every component alone at its own liquid root at the T and P of ``state`` (reference
+    ``mix_ln_fugacity_coefficient_pure``); NaN for a component without a liquid root there."""
+    return _phi_point("fugacity coefficient", parameters, state, kij_matrix, epsilon_ab, True)[1]
+
+
+def _activity(parameters, state, kij_matrix, epsilon_ab) -> Tuple[np.ndarray, np.ndarray]:
+    lnphi, lnphi_pure, x = _phi_point("activity coefficient", parameters, state, kij_matrix, epsilon_ab, True)
+    if np.any(np.isnan(lnphi_pure)):
+        raise RuntimeError(f"PC-SAFT mixture activity coefficient failed at state {list(state)}: component(s) "
+                           f"{np.nonzero(np.isnan(lnphi_pure))[0].tolist()} have no liquid root of their own")
+    return lnphi - lnphi_pure, x
+
+
+def mix_ln_activity_coefficient(parameters: Sequence[Sequence[float]], state: Sequence[float],
+                                kij_matrix: Optional[Any] = None, epsilon_ab: Optional[Any] = None) -> np.ndarray:
+    """ln gamma_i = ln phi_i - ln phi_i^pure (symmetric convention, reference ``mix_ln_activity_coefficient``); raises
+    ``RuntimeError`` where the mixture or one of its components alone has no liquid root."""
+    return _activity(parameters, state, kij_matrix, epsilon_ab)[0]
+
+
+def mix_e_gibbs_energy(parameters: Sequence[Sequence[float]], state: Sequence[float], kij_matrix: Optional[Any] = None,
+                       epsilon_ab: Optional[Any] = None) -> float:
+    """Molar excess Gibbs energy g^E/RT = sum_i x_i ln gamma_i (reference ``mix_e_gibbs_energy``)."""
+    ln_gamma, x = _activity(parameters, state, kij_matrix, epsilon_ab)
+    return float(np.sum(ln_gamma * x))
+
+
+def mix_r_gibbs_energy(parameters: Sequence[Sequence[float]], state: Sequence[float], kij_matrix: Optional[Any] = None,
+                       epsilon_ab: Optional[Any] = None) -> float:
+    """Molar residual Gibbs energy g^res/RT = sum_i x_i ln phi_i (reference ``mix_r_gibbs_energy``)."""
+    lnphi, _, x = _phi_point("fugacity coefficient", parameters, state, kij_matrix, epsilon_ab, False)
+    return float(np.sum(lnphi * x))
+
+
+def mix_gibbs_energy(parameters: Sequence[Sequence[float]], state: Sequence[float], kij_matrix: Optional[Any] = None,
+                     epsilon_ab: Optional[Any] = None) -> float:
+    """Molar Gibbs energy of mixing g/RT = g^E/RT + sum_i x_i ln x_i (reference ``mix_gibbs_energy``), with 0 ln 0 = 0."""
+    ln_gamma, x = _activity(parameters, state, kij_matrix, epsilon_ab)
+    present = x > 0
+    return float(np.sum(ln_gamma * x) + np.sum(x[present] * np.log(x[present])))
+
+
+def mix_ln_phi_batch(mixtures: List[List[List[Any]]], states_batch: List[Any], kij: Optional[List[Any]] = None,
+                     activity: bool = False) -> List[np.ndarray]:
+    """ln phi_i of every state of every non-empty table in one launch, arguments as ``mix_rho_batch``: one fp64 array
+    [rows, nc_i] per non-empty table, a row of NaN where a point failed.  With ``activity`` the arrays hold ln gamma_i
+    = ln phi_i - ln phi_i^pure instead (NaN where a component has no liquid root of its own)."""
+    if len(mixtures) != len(states_batch):
+        raise ValueError(f"{len(mixtures)} mixtures but {len(states_batch)} state tables")
+    tables = [(i, s) for i, s in enumerate(states_batch) if np.shape(s)[0] > 0]
+    if not tables:
+        return []
+    params, comp, d_kij, _ = _pool(mixtures, kij, None)
+    nc = comp.shape[1]
+    states = np.concatenate([_states(s, len(mixtures[i]), nc) for i, s in tables])
+    owner = np.concatenate([np.full(np.shape(s)[0], i, dtype=np.int64) for i, s in tables])
+    lnphi, lnphi_pure, _ = _run_mix_phi(params, comp, d_kij, None, owner, states, activity)
+    value = lnphi - lnphi_pure if activity else lnphi
+    cuts = np.cumsum([np.shape(s)[0] for _, s in tables])[:-1]
+    return [v[:, :len(mixtures[i])].copy() for v, (i, _) in zip(np.split(value, cuts), tables)]

@@ -98,7 +98,9 @@ enum {
   GNX_K_PCSAFT_VP = 21,         /* PC-SAFT vapour pressure at T, fp64 (gnx_pcsaft_vapor_pressure) */
   GNX_K_PCSAFT_MIX_STATE = 22,  /* mixture PC-SAFT a_res, p, dp/drho at (T, rho, x), fp64 (gnx_pcsaft_mix_state) */
   GNX_K_PCSAFT_MIX_RHO = 23,    /* mixture PC-SAFT liquid density at (T, P, x), fp64 (gnx_pcsaft_mix_density) */
-  GNX_K_COUNT = 24
+  GNX_K_PCSAFT_MIX_LNPHI_STATE = 24, /* mixture PC-SAFT ln phi_i, Z at (T, rho, x), fp64 (gnx_pcsaft_mix_lnphi_state) */
+  GNX_K_PCSAFT_MIX_LNPHI = 25,  /* mixture PC-SAFT ln phi_i at the liquid root of (T, P, x), fp64 (gnx_pcsaft_mix_lnphi) */
+  GNX_K_COUNT = 26
 };
 /* start recording a HIP event pair around every launch of the kernels whose id bit is set in kernel_mask
  * (bit k = GNX_K_* id k).  Events go on the handle's stream, i.e. the stream the kernels run on. */
@@ -457,6 +459,26 @@ int32_t gnx_pcsaft_mix_density(gnx_handle* h, const double* params, int64_t B, c
                                const double* mix_kij, const double* mix_eab, int64_t M, int32_t nc,
                                const int64_t* owner, const double* T, const double* P, const double* x, int64_t n,
                                double* rho, int32_t* status);
+/* Fugacity coefficients (ref: pcsaft/pcsaft_feos.py mix_ln_fugacity_coefficient, mix_ln_fugacity_coefficient_pure and
+ * what builds on them): ln phi_i = mu_i^res/kT - ln Z with mu_i^res/kT = d(N a)/dN_i at fixed T, V, the composition
+ * derivatives of a by a first-order forward dual through every term (the site fractions by implicit differentiation).
+ * Unlike the two functions above, a used slot with x = 0 stays in the mixture: its ln phi is the value at infinite
+ * dilution, and its row is validated.  lnphi [n, nc]: NaN in a -1 slot and in every slot of a point with status != 0.
+ * Status codes as above. */
+/* at the molar density rho[i]: lnphi[i, :], Z[i] = p/(rho R T).  Z <= 0 (no ln Z): status 1, Z[i] still reported; Z[i] is
+ * 0.0 for every other status != 0 */
+int32_t gnx_pcsaft_mix_lnphi_state(gnx_handle* h, const double* params, int64_t B, const int64_t* mix_comp,
+                                   const double* mix_kij, const double* mix_eab, int64_t M, int32_t nc,
+                                   const int64_t* owner, const double* T, const double* rho, const double* x, int64_t n,
+                                   double* lnphi, double* Z, int32_t* status);
+/* at the root gnx_pcsaft_mix_density finds: rho[i] (the same bits; 0.0 with status != 0) and lnphi[i, :] there.
+ * lnphi_pure [n, nc] or NULL (skipped): ln phi of each used slot's component alone at its own liquid root at T[i], P[i]
+ * (feos ln_phi_pure_liquid); NaN where that component has no liquid root (no stretch with dp/drho <= 0 below its
+ * highest root, as above its critical temperature), which leaves status[i] at 0 */
+int32_t gnx_pcsaft_mix_lnphi(gnx_handle* h, const double* params, int64_t B, const int64_t* mix_comp,
+                             const double* mix_kij, const double* mix_eab, int64_t M, int32_t nc, const int64_t* owner,
+                             const double* T, const double* P, const double* x, int64_t n, double* rho, double* lnphi,
+                             double* lnphi_pure, int32_t* status);
 
 /* ---- contiguous segment reduce: global pool (ref: train/models.py:218-225, 587-595) ------------------------ */
 enum { GNX_POOL_ADD = 0, GNX_POOL_MEAN = 1, GNX_POOL_MAX = 2 };

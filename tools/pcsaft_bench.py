@@ -3,9 +3,10 @@ density and the vapour pressure, kernel time (events around the launch) and end-
 time (upload, launch, download), next to the CPU oracle (tests/pcsaft_ref.py) timed on a sample of the same points and
 scaled to the call size.  Points: the ThermoML fixture's molecules and states, repeated.
 
-With ``--mixture`` it times the mixture kernels of csrc/gnx_pcsaft_mix.hip instead, on the points of
-the binary ThermoML fixture, repeated: the density and the state kernel, ``mix_rho_batch`` end to end, and the mixture
-oracle (tests/pcsaft_mix_ref.py) on a sample.
+With ``--mixture`` it times the mixture kernels of csrc/gnx_pcsaft_mix.hip and csrc/gnx_pcsaft_mix_phi.hip (DESIGN.md
+§4c) instead, on the points of the binary ThermoML fixture, repeated: the density and the state kernel, the fugacity
+kernel on the same points (without and with the pure-component values, and its state form), ``mix_rho_batch`` end to
+end, and the mixture oracle (tests/pcsaft_mix_ref.py) on a sample.
 
 Usage: python tools/pcsaft_bench.py [--mixture] [--sizes 1000,100000,1000000] [--oracle-sample 20] [--out FILE.json]
 """
@@ -56,13 +57,18 @@ def _mixture(args, dev):
         rho, _ = pcsaft.mixture_density(d_params, d_comp, xx, t, pp, o)
         k_rho = _kernel_ms(lambda: pcsaft.mixture_density(d_params, d_comp, xx, t, pp, o))
         k_state = _kernel_ms(lambda: pcsaft.mixture_state(d_params, d_comp, xx, t, rho, o))
+        k_phi = _kernel_ms(lambda: pcsaft.mixture_ln_phi(d_params, d_comp, xx, t, pp, o))
+        k_phi_pure = _kernel_ms(lambda: pcsaft.mixture_ln_phi(d_params, d_comp, xx, t, pp, o, pure=True))
+        k_phi_state = _kernel_ms(lambda: pcsaft.mixture_ln_phi_state(d_params, d_comp, xx, t, rho, o))
         mixtures = [s["params"] for s in C.systems()]
         tables = [np.column_stack([T[idx][owner[idx] == i], P[idx][owner[idx] == i], x[idx][owner[idx] == i]])
                   for i in range(len(mixtures))]
         pcsaft.mix_rho_batch(mixtures, tables)
         t0 = time.perf_counter()
         pcsaft.mix_rho_batch(mixtures, tables)
-        rec = dict(points=n, mix_density_kernel_ms=k_rho, mix_state_kernel_ms=k_state,
+        rec = dict(points=n, mix_density_kernel_ms=k_rho, mix_state_kernel_ms=k_state, mix_ln_phi_kernel_ms=k_phi,
+                   mix_ln_phi_pure_kernel_ms=k_phi_pure, mix_ln_phi_state_kernel_ms=k_phi_state,
+                   mix_density_points_per_s=n / k_rho * 1e3, mix_ln_phi_points_per_s=n / k_phi * 1e3,
                    mix_rho_batch_ms=(time.perf_counter() - t0) * 1e3, oracle_density_ms_est=oracle * n * 1e3)
         print(json.dumps(rec))
         res.append(rec)
