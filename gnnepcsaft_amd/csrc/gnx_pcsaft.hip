@@ -12,34 +12,29 @@
 //
 // a is written once, as a template over its number type, and evaluated on a second-order forward dual in rho
 // (value, d/drho, d2/drho2): Z = 1 + rho a', p/kT = rho Z, d(p/kT)/drho = 1 + 2 rho a' + rho^2 a''.  Both solvers work
-// in the packing fraction eta (rho = eta / (pi/6 m d^3)) and in the reduced pressure p~ = p / kT (1/angstrom^3).
+// in the packing fraction eta (rho = eta / (pi/6 m d^3)) and in the reduced pressure p~ = p / kT (1/angstrom^3).  The
+// root of p~(eta) = p~, the status codes, the solver constants and the unit changes are gnx_pcsaft_solve.hpp's, shared
+// with the mixture kernels.
 //
 // One lane per state point; a lane loads its parameter row through owner[i].  Every loop has a fixed trip cap; a point
 // that runs into one reports a status != 0 and the value 0.0.  No atomics: same input, same bits.
 #include "gnx_common.hpp"
 #include "gnx_pcsaft_consts.hpp"
 #include "gnx_pcsaft_dual.hpp"
+#include "gnx_pcsaft_solve.hpp"
 
 #include <cmath>
 
 namespace {
 
-using namespace gnx_pcsaft;
-
-constexpr double kPi = 3.14159265358979323846;
-constexpr int kScanDensity = 512;   // downward eta scan of the density solve (step kEtaMax / 512)
 constexpr int kScanLog = 64;        // spinodal scan: 64 log-spaced points in [1e-10, 1e-2] ...
 constexpr int kScanLin = 512;       // ... then 512 linear points in (1e-2, kEtaMax]
-constexpr int kRootIters = 200;     // safeguarded Newton of one density at a given pressure
 constexpr int kBisectIters = 60;    // spinodal refinement
 constexpr int kSuccIters = 100;     // successive substitution p <- p phi_L / phi_V
 constexpr int kNewtonIters = 50;    // Newton on (eta_L, eta_V)
-constexpr double kRootTol = 1e-14;  // relative step / bracket width that ends a root solve
 // relative Newton step that ends the VLE solve: quadratic convergence leaves an error far below it after that step,
 // while a tighter bound can sit under the rounding noise of g_L for long chains (m ~ 10: |dg| ~ 1e-13)
 constexpr double kVleTol = 1e-10;
-
-enum : int32_t { ST_OK = 0, ST_NO_CONV = 1, ST_SUPERCRITICAL = 2, ST_BAD_INPUT = 3 };
 
 // ---- one component at one temperature: everything that does not depend on rho --------------------------------------
 struct Pure {
@@ -58,6 +53,7 @@ struct Pure {
     const double sigma = row[1], eps = row[2], kab = row[3], eab = row[4], mu = row[5];
     na = row[6];
     nb = row[7];
+    // valid_row's tests with T's among them, written out: behind a helper the chain compiles to other code
     if (!(T > 0.0) || !(m > 0.0) || !(sigma > 0.0) || !(eps > 0.0) || !(kab >= 0.0) || !(eab >= 0.0) ||
         !(mu >= 0.0) || !(na >= 0.0) || !(nb >= 0.0) || !isfinite(T) || !isfinite(m) || !isfinite(sigma) ||
         !isfinite(eps) || !isfinite(kab) || !isfinite(eab) || !isfinite(mu) || !isfinite(na) || !isfinite(nb))
@@ -131,6 +127,7 @@ struct Pure {
     double p;      // p / kT [1/angstrom^3]
     double dp;     // d(p/kT)/d eta
     double g;      // mu / kT up to a function of T: ln rho + a + Z - 1 (= ln phi + ln p~)
+    static constexpr bool ok = true;  // closed-form site fractions: the evaluation cannot fail
   };
   __device__ Eval eval(double eta) const {
     const double rho = eta / eta_per_rho;
@@ -141,32 +138,6 @@ struct Pure {
     e.dp = (1.0 + 2.0 * rho * a.d + rho * rho * a.dd) / eta_per_rho;
     e.g = ::log(rho) + a.v + z - 1.0;
     return e;
-  }
-
-  // root of p~(eta) = pt in [lo, hi] with p~(lo) <= pt < p~(hi), by Newton from x safeguarded by bisection
-  __device__ bool root(double pt, double lo, double hi, double x, double& out) const {
-    if (!(x > lo && x < hi)) x = 0.5 * (lo + hi);
-    for (int it = 0; it < kRootIters; ++it) {
-      const Eval e = eval(x);
-      const double f = e.p - pt;
-      if (!isfinite(f)) return false;
-      if (f > 0.0)
-        hi = x;
-      else
-        lo = x;
-      if (f == 0.0) {
-        out = x;
-        return true;
-      }
-      double xn = x - f / e.dp;
-      if (!(e.dp > 0.0) || !(xn > lo && xn < hi)) xn = 0.5 * (lo + hi);
-      if (::fabs(xn - x) <= kRootTol * x || hi - lo <= kRootTol * hi) {
-        out = xn;
-        return true;
-      }
-      x = xn;
-    }
-    return false;
   }
 };
 
@@ -193,7 +164,8 @@ __global__ void __launch_bounds__(256) k_pcsaft_density(const double* __restrict
   if (load_row(params, B, owner, i, t, c) && p > 0.0 && isfinite(p)) {
     st = ST_NO_CONV;
     const double pt = p / c.kT_pa;
-    // p~(kEtaMax) > pt, then scan down to the first eta with p~ <= pt: the bracket of the highest crossing
+    // p~(kEtaMax) > pt, then scan down to the first eta with p~ <= pt: the bracket of the highest crossing.  This is
+    // density_root written out: through it the kernel compiled to other, slower code
     double hi = kEtaMax, lo = 0.0;
     if (c.eval(hi).p - pt > 0.0) {
       for (int k = kScanDensity - 1; k >= 1; --k) {
@@ -205,9 +177,9 @@ __global__ void __launch_bounds__(256) k_pcsaft_density(const double* __restrict
         hi = eta;
       }
       double x;
-      if (c.root(pt, lo, hi, hi, x) && x > 0.0 && c.eval(x).dp > 0.0) {
+      if (pcsaft_root(c, pt, lo, hi, hi, x) && x > 0.0 && c.eval(x).dp > 0.0) {
         st = ST_OK;
-        out = x / c.eta_per_rho * 1e30 / kAvogadro;
+        out = molar_density(x, c.eta_per_rho);
       }
     }
   }
@@ -270,7 +242,8 @@ __global__ void __launch_bounds__(256) k_pcsaft_vapor_pressure(const double* __r
       double p = plo > 0.0 ? 0.5 * (plo + pvs) : 0.5 * pvs;
       double xl = kEtaMax, xv = 0.0;
       for (int it = 0; ok && it < kSuccIters; ++it) {
-        ok = c.root(p, els, kEtaMax, xl, xl) && c.root(p, 0.0, evs, xv > 0.0 ? xv : p * c.eta_per_rho, xv);
+        ok = pcsaft_root(c, p, els, kEtaMax, xl, xl) &&
+             pcsaft_root(c, p, 0.0, evs, xv > 0.0 ? xv : p * c.eta_per_rho, xv);
         if (!ok) break;
         // ln phi_L - ln phi_V at equal pressure = g_L - g_V: the form without ln Z, which is lost to rounding in a
         // liquid far below its normal boiling point (Z_L ~ 1e-19 next to terms of size 1)
@@ -288,7 +261,7 @@ __global__ void __launch_bounds__(256) k_pcsaft_vapor_pressure(const double* __r
       // Newton on (eta_L, eta_V): p~_L = p~_V and g_L = g_V
       bool conv = false;
       if (ok) {
-        ok = c.root(p, els, kEtaMax, xl, xl) && c.root(p, 0.0, evs, xv, xv);
+        ok = pcsaft_root(c, p, els, kEtaMax, xl, xl) && pcsaft_root(c, p, 0.0, evs, xv, xv);
       }
       for (int it = 0; ok && it < kNewtonIters; ++it) {
         const Pure::Eval L = c.eval(xl), V = c.eval(xv);
@@ -323,8 +296,8 @@ __global__ void __launch_bounds__(256) k_pcsaft_vapor_pressure(const double* __r
         if (pv > 0.0 && isfinite(pv)) {
           st = ST_OK;
           ps = pv * c.kT_pa;
-          el = xl / c.eta_per_rho * 1e30 / kAvogadro;
-          ev = xv / c.eta_per_rho * 1e30 / kAvogadro;
+          el = molar_density(xl, c.eta_per_rho);
+          ev = molar_density(xv, c.eta_per_rho);
         }
       }
     }

@@ -16,7 +16,7 @@ __device__ void mix_state_point(const double* __restrict__ params, int64_t B, co
   int32_t st = ST_BAD_INPUT;
   double oa = 0.0, op = 0.0, od = 0.0;
   if (load_mix(params, B, mix_comp, mix_kij, mix_eab, M, nc, owner, x, i, t, c) && r > 0.0 && isfinite(r)) {
-    const double rn = r * (kAvogadro * 1e-30);  // 1/angstrom^3
+    const double rn = number_density(r);  // 1/angstrom^3
     if (rn * c.c3 < 1.0) {
       st = ST_NO_CONV;
       const Mix::Eval e = c.eval_rho(rn);
@@ -46,8 +46,8 @@ __device__ void mix_density_point(const double* __restrict__ params, int64_t B, 
   double out = 0.0;
   if (load_mix(params, B, mix_comp, mix_kij, mix_eab, M, nc, owner, x, i, t, c) && p > 0.0 && isfinite(p)) {
     double xr;
-    st = mix_density_root(c, p / c.kT_pa, xr);
-    if (st == ST_OK) out = xr / c.c3 * 1e30 / kAvogadro;
+    st = density_root(c, p / c.kT_pa, xr);
+    if (st == ST_OK) out = molar_density(xr, c.c3);
   }
   rho[i] = st == ST_OK ? out : 0.0;
   status[i] = st;

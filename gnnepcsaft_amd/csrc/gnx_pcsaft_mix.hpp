@@ -1,5 +1,6 @@
-// Mixture PC-SAFT for 1 to 4 components in fp64: the model and the density solve, shared by gnx_pcsaft_mix.hip (state
-// at (T, rho, x), liquid density at (T, P, x)) and gnx_pcsaft_mix_phi.hip (fugacity coefficients).
+// Mixture PC-SAFT for 1 to 4 components in fp64: the model, shared by gnx_pcsaft_mix.hip (state at (T, rho, x), liquid
+// density at (T, P, x)) and gnx_pcsaft_mix_phi.hip (fugacity coefficients).  The root and density solve on it are the
+// pure code's, from gnx_pcsaft_solve.hpp.
 // (ref: demo/utils_binary.py:116-160 binary_test -> pcsaft/pcsaft_feos.py:311-346 mix_den_feos; [3P] feos 0.8
 // State(..., molefracs=x, density_initialization="liquid")).
 //
@@ -33,22 +34,15 @@
 #include "gnx_common.hpp"
 #include "gnx_pcsaft_consts.hpp"
 #include "gnx_pcsaft_dual.hpp"
+#include "gnx_pcsaft_solve.hpp"
 
 #include <cmath>
 
 namespace {
 
-using namespace gnx_pcsaft;
-
 constexpr int NC_MAX = 4;            // components per mixture: every array below has this extent
-constexpr double kPi = 3.14159265358979323846;
-constexpr int kScanDensity = 512;    // downward eta scan of the density solve (step kEtaMax / 512)
-constexpr int kRootIters = 200;      // safeguarded Newton of one density at a given pressure
 constexpr int kSiteIters = 100;      // Newton / damped substitution of the site fractions
-constexpr double kRootTol = 1e-14;   // relative step / bracket width that ends a root solve
 constexpr double kSiteTol = 1e-12;   // largest Newton step that ends the site-fraction solve (the dual steps polish it)
-
-enum : int32_t { ST_OK = 0, ST_NO_CONV = 1, ST_BAD_INPUT = 3 };
 
 // J y = r for up to NC_MAX unknowns and NR right-hand sides, by elimination with partial pivoting; r is overwritten by y
 template <int NR>
@@ -141,10 +135,7 @@ struct MixT {
       if (c == -1 || (!KEEP && !(xin[s] > 0.0))) continue;
       const double* row = params + c * 9;
       const double mm = row[0], sg = row[1], ep = row[2], ka = row[3], ea = row[4], mu = row[5], a = row[6], b = row[7];
-      if (!(mm > 0.0) || !(sg > 0.0) || !(ep > 0.0) || !(ka >= 0.0) || !(ea >= 0.0) || !(mu >= 0.0) || !(a >= 0.0) ||
-          !(b >= 0.0) || !isfinite(mm) || !isfinite(sg) || !isfinite(ep) || !isfinite(ka) || !isfinite(ea) ||
-          !isfinite(mu) || !isfinite(a) || !isfinite(b))
-        return false;
+      if (!valid_row(row)) return false;
       const int i = n++;
       slot[i] = s;
       x[i] = MixVar<X>::at(xin[s] / sum, i);
@@ -419,32 +410,6 @@ struct MixT {
     e.dp /= c3;
     return e;
   }
-
-  // root of p~(eta) = pt in [lo, hi] with p~(lo) <= pt < p~(hi), by Newton from x safeguarded by bisection
-  __device__ bool root(double pt, double lo, double hi, double x, double& out) {
-    if (!(x > lo && x < hi)) x = 0.5 * (lo + hi);
-    for (int it = 0; it < kRootIters; ++it) {
-      const Eval e = eval(x);
-      const double f = e.p - pt;
-      if (!e.ok || !isfinite(f)) return false;
-      if (f > 0.0)
-        hi = x;
-      else
-        lo = x;
-      if (f == 0.0) {
-        out = x;
-        return true;
-      }
-      double xn = x - f / e.dp;
-      if (!(e.dp > 0.0) || !(xn > lo && xn < hi)) xn = 0.5 * (lo + hi);
-      if (::fabs(xn - x) <= kRootTol * x || hi - lo <= kRootTol * hi) {
-        out = xn;
-        return true;
-      }
-      x = xn;
-    }
-    return false;
-  }
 };
 using Mix = MixT<double>;
 
@@ -457,33 +422,6 @@ __device__ __forceinline__ bool load_mix(const double* __restrict__ params, int6
   if (o < 0 || o >= M) return false;
   return c.init(params, B, mix_comp + o * nc, mix_kij ? mix_kij + o * nc * nc : nullptr,
                 mix_eab ? mix_eab + o * nc * nc : nullptr, nc, x + i * nc, T);
-}
-
-// packing fraction of the highest-density root of p~(eta) = pt with dp/deta > 0; ST_OK or ST_NO_CONV
-__device__ int32_t mix_density_root(Mix& c, double pt, double& out) {
-  // p~(kEtaMax) > pt, then scan down to the first eta with p~ <= pt: the bracket of the highest crossing
-  double hi = kEtaMax, lo = 0.0;
-  Mix::Eval e = c.eval(hi);
-  bool ok = e.ok && e.p - pt > 0.0;
-  for (int k = kScanDensity - 1; ok && k >= 1; --k) {
-    const double eta = kEtaMax * k / kScanDensity;
-    e = c.eval(eta);
-    ok = e.ok;
-    if (e.p - pt <= 0.0) {
-      lo = eta;
-      break;
-    }
-    hi = eta;
-  }
-  double xr;
-  if (ok && c.root(pt, lo, hi, hi, xr) && xr > 0.0) {
-    e = c.eval(xr);
-    if (e.ok && e.dp > 0.0) {
-      out = xr;
-      return ST_OK;
-    }
-  }
-  return ST_NO_CONV;
 }
 
 }  // namespace

@@ -95,7 +95,7 @@ __device__ double mix_lnphi_pure(const double* __restrict__ params, int64_t B, c
   const double one = 1.0;
   if (!c.init(params, B, comp, nullptr, nullptr, 1, &one, T)) return NAN;
   double xr;
-  if (mix_density_root(c, p / c.kT_pa, xr) != ST_OK) return NAN;
+  if (density_root(c, p / c.kT_pa, xr) != ST_OK) return NAN;
   bool liquid = false;
   for (int k = kScanDensity - 1; k >= 1 && !liquid; --k) {
     const double eta = kEtaMax * k / kScanDensity;
@@ -106,7 +106,7 @@ __device__ double mix_lnphi_pure(const double* __restrict__ params, int64_t B, c
   }
   if (!liquid) return NAN;
   // at the density a one-component call would report, converted as the state form converts it
-  const Mix::Eval e = c.eval_rho(xr / c.c3 * 1e30 / kAvogadro * (kAvogadro * 1e-30));
+  const Mix::Eval e = c.eval_rho(number_density(molar_density(xr, c.c3)));
   const double v = e.a + e.z - 1.0 - ::log(e.z);
   return e.ok && isfinite(v) ? v : NAN;
 }
@@ -125,7 +125,7 @@ __device__ void mix_lnphi_state_point(const double* __restrict__ params, int64_t
   double row[NC_MAX], z = 0.0;
   if (o >= 0 && o < M && r > 0.0 && isfinite(r))
     st = mix_lnphi_at(params, B, mix_comp + o * nc, mix_kij ? mix_kij + o * nc * nc : nullptr,
-                      mix_eab ? mix_eab + o * nc * nc : nullptr, nc, x + i * nc, t, r * (kAvogadro * 1e-30), c, row, z);
+                      mix_eab ? mix_eab + o * nc * nc : nullptr, nc, x + i * nc, t, number_density(r), c, row, z);
   for (int s = 0; s < nc; ++s) lnphi[i * nc + s] = st == ST_OK ? row[s] : NAN;
   Z[i] = z;
   status[i] = st;
@@ -145,14 +145,13 @@ __device__ void mix_lnphi_point(const double* __restrict__ params, int64_t B, co
   double out = 0.0, row[NC_MAX], z = 0.0;
   if (load_mix(params, B, mix_comp, mix_kij, mix_eab, M, nc, owner, x, i, t, c) && p > 0.0 && isfinite(p)) {
     double xr;
-    st = mix_density_root(c, p / c.kT_pa, xr);
+    st = density_root(c, p / c.kT_pa, xr);
     if (st == ST_OK) {
-      out = xr / c.c3 * 1e30 / kAvogadro;
+      out = molar_density(xr, c.c3);
       // at the density reported, converted as the state form converts it: the two forms then agree bit for bit
-      const double rn = out * (kAvogadro * 1e-30);
       const int64_t o = owner[i];
       st = mix_lnphi_at(params, B, mix_comp + o * nc, mix_kij ? mix_kij + o * nc * nc : nullptr,
-                        mix_eab ? mix_eab + o * nc * nc : nullptr, nc, x + i * nc, t, rn, c, row, z);
+                        mix_eab ? mix_eab + o * nc * nc : nullptr, nc, x + i * nc, t, number_density(out), c, row, z);
     }
   }
   rho[i] = st == ST_OK ? out : 0.0;

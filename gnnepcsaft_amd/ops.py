@@ -999,41 +999,78 @@ def _pcsaft_args(params: torch.Tensor, owner: torch.Tensor, T: torch.Tensor, nam
     return params, owner.contiguous(), T
 
 
-def pcsaft_density(params: torch.Tensor, owner: torch.Tensor, T: torch.Tensor, P: torch.Tensor
-                   ) -> Tuple[torch.Tensor, torch.Tensor]:
-    """PC-SAFT liquid density (gnx_pcsaft_density): params [B, 9] fp64 rows, owner [n] int64, T [n] K, P [n] Pa ->
-    (rho [n] fp64 mol/m^3, status [n] int32); rho is 0.0 where status != 0.  One launch, no host synchronisation."""
+_F64, _ST = torch.float64, torch.int32
+
+
+def _pcsaft_outs(out, specs, dev: torch.device, name: str):
+    """The output tensors of one PC-SAFT entry in its argument order: new ones of ``specs`` ((shape, dtype), or None for
+    one that is not asked for), or the caller's ``out`` checked against them.  A None in ``out`` reaches the entry as
+    NULL.  A caller that wants every output in one buffer passes views of it."""
+    if out is None:
+        return tuple(None if s is None else torch.empty(s[0], dtype=s[1], device=dev) for s in specs)
+    if len(out) != len(specs):
+        raise _lib.GnxError(_lib.GNX_E_INVALID, f"{name}: out must hold {len(specs)} tensors, got {len(out)}")
+    for t, s in zip(out, specs):
+        if t is not None and (s is None or tuple(t.shape) != s[0] or t.dtype != s[1] or t.device != dev
+                              or not t.is_contiguous()):
+            raise _lib.GnxError(_lib.GNX_E_INVALID, f"{name}: out does not match the outputs of this call")
+    return tuple(out)
+
+
+def _pcsaft_density(params, owner, T, P, out=None):
+    """``pcsaft_density`` writing into ``out`` = (rho, status) where given: the one call site of the entry."""
     params, owner, T = _pcsaft_args(params, owner, T, "pcsaft_density")
     P = _f64_on(P, "pcsaft_density: P", params.device)
     if P.shape != T.shape:
         raise _lib.GnxError(_lib.GNX_E_INVALID, f"pcsaft_density: P {tuple(P.shape)} and T {tuple(T.shape)} differ")
     n, dev = T.numel(), params.device
-    rho = torch.empty(n, dtype=torch.float64, device=dev)
-    status = torch.empty(n, dtype=torch.int32, device=dev)
+    rho, status = _pcsaft_outs(out, [((n,), _F64), ((n,), _ST)], dev, "pcsaft_density")
     check(_lib.load().gnx_pcsaft_density(handle(dev), params.data_ptr(), params.size(0), owner.data_ptr(),
                                          T.data_ptr(), P.data_ptr(), n, rho.data_ptr(), status.data_ptr()))
     return rho, status
+
+
+def pcsaft_density(params: torch.Tensor, owner: torch.Tensor, T: torch.Tensor, P: torch.Tensor
+                   ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """PC-SAFT liquid density (gnx_pcsaft_density): params [B, 9] fp64 rows, owner [n] int64, T [n] K, P [n] Pa ->
+    (rho [n] fp64 mol/m^3, status [n] int32); rho is 0.0 where status != 0.  One launch, no host synchronisation."""
+    return _pcsaft_density(params, owner, T, P)
+
+
+def _pcsaft_vapor_pressure(params, owner, T, out=None):
+    """``pcsaft_vapor_pressure`` writing into ``out`` = (psat, rho_l, rho_v, status) where given; rho_l and rho_v may
+    be None there: the one call site of the entry."""
+    params, owner, T = _pcsaft_args(params, owner, T, "pcsaft_vapor_pressure")
+    n, dev = T.numel(), params.device
+    out = _pcsaft_outs(out, [((n,), _F64)] * 3 + [((n,), _ST)], dev, "pcsaft_vapor_pressure")
+    check(_lib.load().gnx_pcsaft_vapor_pressure(handle(dev), params.data_ptr(), params.size(0), owner.data_ptr(),
+                                                T.data_ptr(), n, *map(_ptr, out)))
+    return out
 
 
 def pcsaft_vapor_pressure(params: torch.Tensor, owner: torch.Tensor, T: torch.Tensor
                           ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
     """PC-SAFT vapour pressure (gnx_pcsaft_vapor_pressure): params [B, 9] fp64, owner [n] int64, T [n] K ->
     (psat [n] Pa, rho_l [n], rho_v [n] mol/m^3, status [n] int32); all 0.0 where status != 0 (2 = supercritical)."""
-    params, owner, T = _pcsaft_args(params, owner, T, "pcsaft_vapor_pressure")
-    n, dev = T.numel(), params.device
-    out = torch.empty(3, n, dtype=torch.float64, device=dev)
-    status = torch.empty(n, dtype=torch.int32, device=dev)
-    check(_lib.load().gnx_pcsaft_vapor_pressure(handle(dev), params.data_ptr(), params.size(0), owner.data_ptr(),
-                                                T.data_ptr(), n, out[0].data_ptr(), out[1].data_ptr(),
-                                                out[2].data_ptr(), status.data_ptr()))
-    return out[0], out[1], out[2], status
+    return _pcsaft_vapor_pressure(params, owner, T)
 
 
-def _pcsaft_mix_args(params, comp, kij, eab, owner, T, second, x, name):
+# the four mixture forms: entry point and fp64 outputs in argument order (0: [n], 1: [n, nc]); the status follows them
+_PCSAFT_MIX = {"pcsaft_mix_state": ("gnx_pcsaft_mix_state", (0, 0, 0)),
+               "pcsaft_mix_density": ("gnx_pcsaft_mix_density", (0,)),
+               "pcsaft_mix_lnphi_state": ("gnx_pcsaft_mix_lnphi_state", (1, 0)),
+               "pcsaft_mix_lnphi": ("gnx_pcsaft_mix_lnphi", (0, 1, 1))}
+
+
+def _pcsaft_mix(params, comp, kij, eab, owner, T, second, x, name, out=None, last=True):
+    """The mixture form ``name`` of ``_PCSAFT_MIX``: validate, take ``out`` or make the outputs, call.  ``last`` False
+    leaves the last fp64 output (lnphi_pure) out: None in the result, NULL for the entry."""
+    entry, widths = _PCSAFT_MIX[name]
     params, owner, T = _pcsaft_args(params, owner, T, name)
     dev = params.device
     if comp.dtype != torch.int64 or comp.device != dev or comp.dim() != 2 or not 1 <= comp.size(1) <= 4:
         raise _lib.GnxError(_lib.GNX_E_INVALID, f"{name}: comp must be an int64 [M, nc] tensor on {dev} with 1 <= nc <= 4")
+    comp = comp.contiguous()
     M, nc = comp.shape
     mats = []
     for label, t in (("kij", kij), ("eab", eab)):
@@ -1044,10 +1081,18 @@ def _pcsaft_mix_args(params, comp, kij, eab, owner, T, second, x, name):
         mats.append(t)
     second = _f64_on(second, f"{name}: state", dev)
     x = _f64_on(x, f"{name}: x", dev)
-    if second.shape != T.shape or tuple(x.shape) != (T.numel(), nc):
+    n = T.numel()
+    if second.shape != T.shape or tuple(x.shape) != (n, nc):
         raise _lib.GnxError(_lib.GNX_E_INVALID, f"{name}: T {tuple(T.shape)}, state {tuple(second.shape)} and x "
                                                 f"{tuple(x.shape)} do not describe n points of {nc} components")
-    return params, comp.contiguous(), mats[0], mats[1], owner, T, second, x
+    specs = [((n, nc) if w else (n,), _F64) for w in widths] + [((n,), _ST)]
+    if not last:
+        specs[-2] = None
+    out = _pcsaft_outs(out, specs, dev, name)
+    check(getattr(_lib.load(), entry)(handle(dev), params.data_ptr(), params.size(0), comp.data_ptr(), _ptr(mats[0]),
+                                      _ptr(mats[1]), M, nc, owner.data_ptr(), T.data_ptr(), second.data_ptr(),
+                                      x.data_ptr(), n, *map(_ptr, out)))
+    return out
 
 
 def pcsaft_mix_state(params: torch.Tensor, comp: torch.Tensor, kij: Optional[torch.Tensor], eab: Optional[torch.Tensor],
@@ -1057,16 +1102,7 @@ def pcsaft_mix_state(params: torch.Tensor, comp: torch.Tensor, kij: Optional[tor
     of each mixture (-1 = unused slot), kij / eab [M, nc, nc] fp64 or None, owner [n] int64 mixture of each point, T [n] K,
     rho [n] mol/m^3, x [n, nc] -> (a_res [n], p [n] Pa, dpdrho [n] Pa m^3/mol, status [n] int32); all 0.0 where
     status != 0.  One launch, no host synchronisation."""
-    params, comp, kij, eab, owner, T, rho, x = _pcsaft_mix_args(params, comp, kij, eab, owner, T, rho, x,
-                                                                "pcsaft_mix_state")
-    n, dev = T.numel(), params.device
-    out = torch.empty(3, n, dtype=torch.float64, device=dev)
-    status = torch.empty(n, dtype=torch.int32, device=dev)
-    check(_lib.load().gnx_pcsaft_mix_state(handle(dev), params.data_ptr(), params.size(0), comp.data_ptr(), _ptr(kij),
-                                           _ptr(eab), comp.size(0), comp.size(1), owner.data_ptr(), T.data_ptr(),
-                                           rho.data_ptr(), x.data_ptr(), n, out[0].data_ptr(), out[1].data_ptr(),
-                                           out[2].data_ptr(), status.data_ptr()))
-    return out[0], out[1], out[2], status
+    return _pcsaft_mix(params, comp, kij, eab, owner, T, rho, x, "pcsaft_mix_state")
 
 
 def pcsaft_mix_density(params: torch.Tensor, comp: torch.Tensor, kij: Optional[torch.Tensor],
@@ -1074,15 +1110,7 @@ def pcsaft_mix_density(params: torch.Tensor, comp: torch.Tensor, kij: Optional[t
                        x: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
     """Mixture PC-SAFT liquid density (gnx_pcsaft_mix_density): arguments as ``pcsaft_mix_state`` with P [n] Pa in
     place of rho -> (rho [n] mol/m^3, status [n] int32); rho is 0.0 where status != 0."""
-    params, comp, kij, eab, owner, T, P, x = _pcsaft_mix_args(params, comp, kij, eab, owner, T, P, x,
-                                                              "pcsaft_mix_density")
-    n, dev = T.numel(), params.device
-    rho = torch.empty(n, dtype=torch.float64, device=dev)
-    status = torch.empty(n, dtype=torch.int32, device=dev)
-    check(_lib.load().gnx_pcsaft_mix_density(handle(dev), params.data_ptr(), params.size(0), comp.data_ptr(), _ptr(kij),
-                                             _ptr(eab), comp.size(0), comp.size(1), owner.data_ptr(), T.data_ptr(),
-                                             P.data_ptr(), x.data_ptr(), n, rho.data_ptr(), status.data_ptr()))
-    return rho, status
+    return _pcsaft_mix(params, comp, kij, eab, owner, T, P, x, "pcsaft_mix_density")
 
 
 def pcsaft_mix_lnphi_state(params: torch.Tensor, comp: torch.Tensor, kij: Optional[torch.Tensor],
@@ -1091,17 +1119,7 @@ def pcsaft_mix_lnphi_state(params: torch.Tensor, comp: torch.Tensor, kij: Option
     """Mixture PC-SAFT fugacity coefficients at (T, rho, x) (gnx_pcsaft_mix_lnphi_state): arguments as
     ``pcsaft_mix_state`` -> (lnphi [n, nc], Z [n], status [n] int32); NaN in a -1 slot and in the whole row where
     status != 0.  A used slot with x = 0 stays in the mixture (infinite dilution)."""
-    params, comp, kij, eab, owner, T, rho, x = _pcsaft_mix_args(params, comp, kij, eab, owner, T, rho, x,
-                                                                "pcsaft_mix_lnphi_state")
-    n, nc, dev = T.numel(), comp.size(1), params.device
-    lnphi = torch.empty(n, nc, dtype=torch.float64, device=dev)
-    Z = torch.empty(n, dtype=torch.float64, device=dev)
-    status = torch.empty(n, dtype=torch.int32, device=dev)
-    check(_lib.load().gnx_pcsaft_mix_lnphi_state(handle(dev), params.data_ptr(), params.size(0), comp.data_ptr(),
-                                                 _ptr(kij), _ptr(eab), comp.size(0), nc, owner.data_ptr(), T.data_ptr(),
-                                                 rho.data_ptr(), x.data_ptr(), n, lnphi.data_ptr(), Z.data_ptr(),
-                                                 status.data_ptr()))
-    return lnphi, Z, status
+    return _pcsaft_mix(params, comp, kij, eab, owner, T, rho, x, "pcsaft_mix_lnphi_state")
 
 
 def pcsaft_mix_lnphi(params: torch.Tensor, comp: torch.Tensor, kij: Optional[torch.Tensor], eab: Optional[torch.Tensor],
@@ -1110,17 +1128,7 @@ def pcsaft_mix_lnphi(params: torch.Tensor, comp: torch.Tensor, kij: Optional[tor
     """Mixture PC-SAFT fugacity coefficients at the liquid root of (T, P, x) (gnx_pcsaft_mix_lnphi): arguments as
     ``pcsaft_mix_density`` -> (rho [n] mol/m^3, the bits of ``pcsaft_mix_density``; lnphi [n, nc]; lnphi_pure [n, nc] if
     ``pure`` else None: each component alone at its own liquid root, NaN where it has none; status [n] int32)."""
-    params, comp, kij, eab, owner, T, P, x = _pcsaft_mix_args(params, comp, kij, eab, owner, T, P, x, "pcsaft_mix_lnphi")
-    n, nc, dev = T.numel(), comp.size(1), params.device
-    rho = torch.empty(n, dtype=torch.float64, device=dev)
-    lnphi = torch.empty(n, nc, dtype=torch.float64, device=dev)
-    lnphi_pure = torch.empty(n, nc, dtype=torch.float64, device=dev) if pure else None
-    status = torch.empty(n, dtype=torch.int32, device=dev)
-    check(_lib.load().gnx_pcsaft_mix_lnphi(handle(dev), params.data_ptr(), params.size(0), comp.data_ptr(), _ptr(kij),
-                                           _ptr(eab), comp.size(0), nc, owner.data_ptr(), T.data_ptr(), P.data_ptr(),
-                                           x.data_ptr(), n, rho.data_ptr(), lnphi.data_ptr(), _ptr(lnphi_pure),
-                                           status.data_ptr()))
-    return rho, lnphi, lnphi_pure, status
+    return _pcsaft_mix(params, comp, kij, eab, owner, T, P, x, "pcsaft_mix_lnphi", last=pure)
 
 
 _POOL = {"add": _lib.POOL_ADD, "sum": _lib.POOL_ADD, "mean": _lib.POOL_MEAN, "max": _lib.POOL_MAX}

@@ -46,8 +46,8 @@ def _device() -> torch.device:
 
 
 def _upload(dev: torch.device, arrays: Sequence[Optional[np.ndarray]]) -> List[Optional[torch.Tensor]]:
-    """Host fp64 / int64 arrays packed into one 8-byte-element buffer and copied once: a flat device view of each, in
-    order (None stays None)."""
+    """Host fp64 / int64 arrays packed into one 8-byte-element buffer and copied once: a device view of each, of its
+    shape and in order (None stays None)."""
     given = [a for a in arrays if a is not None]
     ends = np.cumsum([a.size for a in given])
     buf = np.empty(int(ends[-1]), dtype=np.int64)
@@ -56,36 +56,40 @@ def _upload(dev: torch.device, arrays: Sequence[Optional[np.ndarray]]) -> List[O
         (flt if a.dtype == np.float64 else buf)[end - a.size:end] = a.reshape(-1)
     dbuf = torch.from_numpy(buf).to(dev)
     dflt = dbuf.view(torch.float64)
-    views = iter([(dflt if a.dtype == np.float64 else dbuf)[end - a.size:end] for a, end in zip(given, ends)])
+    views = iter([(dflt if a.dtype == np.float64 else dbuf)[end - a.size:end].view(a.shape)
+                  for a, end in zip(given, ends)])
     return [None if a is None else next(views) for a in arrays]
 
 
-def _outputs(dev: torch.device, n: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
-    """both outputs in one buffer: value (fp64) | status (int32, padded to 8 bytes)"""
-    out = torch.empty(n + (n + 1) // 2, dtype=torch.int64, device=dev)
-    return out, out[:n].view(torch.float64), out[n:].view(torch.int32)[:n]
-
-
-def _download(out: torch.Tensor, n: int) -> Tuple[np.ndarray, np.ndarray]:
-    host = out.cpu().numpy()
-    return host[:n].view(np.float64).copy(), host[n:].view(np.int32)[:n].copy()
-
-
-def _run(kind: str, params: np.ndarray, owner: np.ndarray, T: np.ndarray, P: Optional[np.ndarray]
-         ) -> Tuple[np.ndarray, np.ndarray]:
-    """One upload, one launch, one download: (value [n] fp64, status [n] int32) for host arrays."""
-    B, n = params.shape[0], owner.shape[0]
+def _run(entry, inputs: Sequence[Optional[np.ndarray]], n: int, shapes: Sequence[Optional[Tuple[int, ...]]], **kw
+         ) -> Tuple[List[Optional[np.ndarray]], np.ndarray]:
+    """One upload, one launch, one download for host arrays.  ``entry`` is a call site of gnnepcsaft_amd.ops that takes
+    ``out``, ``inputs`` its arguments in order, ``shapes`` the shape of each of its fp64 outputs (None: not asked for).
+    Every output lives in one buffer, the fp64 ones followed by the status (int32, padded to 8 bytes) -> ([fp64
+    arrays], status [n])."""
     dev = _device()
-    d_params, d_T, d_P, d_owner = _upload(dev, [params, T, P, owner])
-    out, value, status = _outputs(dev, n)
-    lib = _lib.load()
+    sizes = [0 if s is None else int(np.prod(s)) for s in shapes]
+    ends = np.cumsum(sizes)
+    end = int(ends[-1])
+    out = torch.empty(end + (n + 1) // 2, dtype=torch.int64, device=dev)
+    flt = out.view(torch.float64)
+    views = [None if s is None else flt[e - k:e].view(s) for s, k, e in zip(shapes, sizes, ends)]
+    entry(*_upload(dev, inputs), out=(*views, out[end:].view(torch.int32)[:n]), **kw)
+    host = out.cpu().numpy()
+    val = host[:end].view(np.float64)
+    return ([None if s is None else val[e - k:e].reshape(s).copy() for s, k, e in zip(shapes, sizes, ends)],
+            host[end:].view(np.int32)[:n].copy())
+
+
+def _run_pure(kind: str, params: np.ndarray, owner: np.ndarray, T: np.ndarray, P: Optional[np.ndarray]
+              ) -> Tuple[np.ndarray, np.ndarray]:
+    """(liquid density, kind "rho", or vapour pressure, kind "vp", [n] fp64; status [n] int32)"""
+    n = owner.shape[0]
     if kind == "rho":
-        _lib.check(lib.gnx_pcsaft_density(_lib.handle(dev), d_params.data_ptr(), B, d_owner.data_ptr(),
-                                          d_T.data_ptr(), d_P.data_ptr(), n, value.data_ptr(), status.data_ptr()))
+        values, status = _run(ops._pcsaft_density, [params, owner, T, P], n, [(n,)])
     else:
-        _lib.check(lib.gnx_pcsaft_vapor_pressure(_lib.handle(dev), d_params.data_ptr(), B, d_owner.data_ptr(),
-                                                 d_T.data_ptr(), n, value.data_ptr(), None, None, status.data_ptr()))
-    return _download(out, n)
+        values, status = _run(ops._pcsaft_vapor_pressure, [params, owner, T], n, [(n,), None, None])
+    return values[0], status
 
 
 def _rows(parameters_batch: Sequence[Sequence[float]]) -> np.ndarray:
@@ -95,18 +99,32 @@ def _rows(parameters_batch: Sequence[Sequence[float]]) -> np.ndarray:
     return params
 
 
+def _nonempty(what: str, count: int, states_batch: List[Any]) -> List[Tuple[int, Any]]:
+    """(i, table) of the state tables with rows, after the length check of a batch form"""
+    if count != len(states_batch):
+        raise ValueError(f"{count} {what} but {len(states_batch)} state tables")
+    return [(i, s) for i, s in enumerate(states_batch) if np.shape(s)[0] > 0]
+
+
+def _run_tables(index: Sequence[int], states: Sequence[np.ndarray], run) -> List[np.ndarray]:
+    """states[k]: the [rows, ...] fp64 states of table index[k].  All of them stacked go through ``run(owner, states)``
+    -> [n, ...] once, owner being the table of each row; the result comes back split at the table cuts (views)."""
+    owner = np.concatenate([np.full(t.shape[0], i, dtype=np.int64) for i, t in zip(index, states)])
+    value = run(owner, np.concatenate(states))
+    return np.split(value, np.cumsum([t.shape[0] for t in states])[:-1])
+
+
 def _batch(kind: str, parameters_batch: List[List[Any]], states_batch: List[Any]) -> List[np.ndarray]:
-    if len(parameters_batch) != len(states_batch):
-        raise ValueError(f"{len(parameters_batch)} parameter rows but {len(states_batch)} state tables")
-    tables = [(i, np.asarray(s, dtype=np.float64)) for i, s in enumerate(states_batch) if s.shape[0] > 0]
+    tables = _nonempty("parameter rows", len(parameters_batch), states_batch)
     if not tables:
         return []
     params = _rows(parameters_batch)
-    owner = np.concatenate([np.full(t.shape[0], i, dtype=np.int64) for i, t in tables])
-    states = np.concatenate([t.reshape(t.shape[0], -1) for _, t in tables])
-    value, _ = _run(kind, params, owner, states[:, 0], states[:, 1] if kind == "rho" else None)
-    cuts = np.cumsum([t.shape[0] for _, t in tables])[:-1]
-    return [v.copy() for v in np.split(value, cuts)]
+    states = [np.asarray(s, dtype=np.float64).reshape(np.shape(s)[0], -1) for _, s in tables]
+
+    def run(owner, st):
+        return _run_pure(kind, params, owner, st[:, 0], st[:, 1] if kind == "rho" else None)[0]
+
+    return [v.copy() for v in _run_tables([i for i, _ in tables], states, run)]
 
 
 def rho_batch(parameters_batch: List[List[Any]], states_batch: List[Any]) -> List[np.ndarray]:
@@ -121,13 +139,16 @@ def vp_batch(parameters_batch: List[List[Any]], states_batch: List[Any]) -> List
     return _batch("vp", parameters_batch, states_batch)
 
 
+def _require_ok(status: np.ndarray, what: str, state: Sequence[float]) -> None:
+    if status[0] != STATUS_OK:
+        raise RuntimeError(f"PC-SAFT {what} failed at state {list(state)}: {_REASON.get(int(status[0]), int(status[0]))}")
+
+
 def _single(kind: str, parameters: Sequence[float], state: Sequence[float]) -> float:
     params = _rows([parameters])
     P = np.asarray([state[1]], dtype=np.float64) if kind == "rho" else None
-    value, status = _run(kind, params, np.zeros(1, dtype=np.int64), np.asarray([state[0]], dtype=np.float64), P)
-    if status[0] != STATUS_OK:
-        raise RuntimeError(f"PC-SAFT {'density' if kind == 'rho' else 'vapor pressure'} failed at state "
-                           f"{list(state)}: {_REASON.get(int(status[0]), int(status[0]))}")
+    value, status = _run_pure(kind, params, np.zeros(1, dtype=np.int64), np.asarray([state[0]], dtype=np.float64), P)
+    _require_ok(status, "density" if kind == "rho" else "vapor pressure", state)
     return float(value[0])
 
 
@@ -208,19 +229,16 @@ def mixture_ln_phi(params: torch.Tensor, comp: torch.Tensor, x: torch.Tensor, T:
     return ops.pcsaft_mix_lnphi(params, comp, kij, eab, _owner(owner, T), T, P, x, pure)
 
 
-def _run_mix(params: np.ndarray, comp: np.ndarray, kij: Optional[np.ndarray], eab: Optional[np.ndarray],
-             owner: np.ndarray, states: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
-    """One upload, one launch, one download: (rho [n] fp64, status [n] int32) for host arrays; states [n, 2 + nc]."""
-    B, (M, nc), n = params.shape[0], comp.shape, owner.shape[0]
-    dev = _device()
-    d_params, d_T, d_P, d_x, d_kij, d_eab, d_comp, d_owner = _upload(
-        dev, [params, states[:, 0], states[:, 1], states[:, 2:], kij, eab, comp, owner])
-    out, value, status = _outputs(dev, n)
-    ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
-    _lib.check(_lib.load().gnx_pcsaft_mix_density(_lib.handle(dev), d_params.data_ptr(), B, d_comp.data_ptr(), ptr(d_kij),
-                                                  ptr(d_eab), M, nc, d_owner.data_ptr(), d_T.data_ptr(), d_P.data_ptr(),
-                                                  d_x.data_ptr(), n, value.data_ptr(), status.data_ptr()))
-    return _download(out, n)
+def _run_mix(kind: str, params: np.ndarray, comp: np.ndarray, kij: Optional[np.ndarray], eab: Optional[np.ndarray],
+             owner: np.ndarray, states: np.ndarray) -> Tuple[List[Optional[np.ndarray]], np.ndarray]:
+    """states [n, 2 + nc] -> (values, status [n] int32); values is [rho [n]] for kind "density", [rho, lnphi [n, nc],
+    None] for "lnphi" and [rho, lnphi, lnphi_pure [n, nc]] for "lnphi_pure"."""
+    n, nc = owner.shape[0], comp.shape[1]
+    inputs = [params, comp, kij, eab, owner, states[:, 0], states[:, 1], states[:, 2:]]
+    if kind == "density":
+        return _run(ops._pcsaft_mix, inputs, n, [(n,)], name="pcsaft_mix_density")
+    pure = kind == "lnphi_pure"
+    return _run(ops._pcsaft_mix, inputs, n, [(n,), (n, nc), (n, nc) if pure else None], name="pcsaft_mix_lnphi", last=pure)
 
 
 def _square(matrix: Any, k: int, nc: int, fill: float, what: str) -> np.ndarray:
@@ -268,75 +286,52 @@ def _states(table: Any, k: int, nc: int) -> np.ndarray:
     return out
 
 
+def _mix_batch(kind: str, mixtures: List[List[List[Any]]], states_batch: List[Any], kij: Optional[List[Any]], pick
+               ) -> List[Tuple[int, np.ndarray]]:
+    """The mixture batch forms: (i, rows of ``pick(values of _run_mix)``) of every non-empty table i, in one launch"""
+    tables = _nonempty("mixtures", len(mixtures), states_batch)
+    if not tables:
+        return []
+    params, comp, d_kij, _ = _pool(mixtures, kij, None)
+    index = [i for i, _ in tables]
+    states = [_states(s, len(mixtures[i]), comp.shape[1]) for i, s in tables]
+    parts = _run_tables(index, states, lambda owner, st: pick(_run_mix(kind, params, comp, d_kij, None, owner, st)[0]))
+    return list(zip(index, parts))
+
+
 def mix_rho_batch(mixtures: List[List[List[Any]]], states_batch: List[Any], kij: Optional[List[Any]] = None
                   ) -> List[np.ndarray]:
     """Liquid densities (mol/m³) of every state of every non-empty table in one launch: ``mixtures[i]`` is the list of
     component rows of system i, ``states_batch[i]`` its array of rows ``[T (K), P (Pa), x1..x_nc]``, ``kij[i]`` its
     k_ij matrix or None.  One fp64 array per non-empty table, 0.0 where a point failed (the double loop of the
     reference's demo/utils_binary.py ``binary_test`` as one call)."""
-    if len(mixtures) != len(states_batch):
-        raise ValueError(f"{len(mixtures)} mixtures but {len(states_batch)} state tables")
-    tables = [(i, s) for i, s in enumerate(states_batch) if np.shape(s)[0] > 0]
-    if not tables:
-        return []
-    params, comp, d_kij, _ = _pool(mixtures, kij, None)
-    nc = comp.shape[1]
-    states = np.concatenate([_states(s, len(mixtures[i]), nc) for i, s in tables])
-    owner = np.concatenate([np.full(np.shape(s)[0], i, dtype=np.int64) for i, s in tables])
-    value, _ = _run_mix(params, comp, d_kij, None, owner, states)
-    cuts = np.cumsum([np.shape(s)[0] for _, s in tables])[:-1]
-    return [v.copy() for v in np.split(value, cuts)]
+    return [v.copy() for _, v in _mix_batch("density", mixtures, states_batch, kij, lambda values: values[0])]
+
+
+def _mix_point(what: str, kind: str, parameters: Sequence[Sequence[float]], state: Sequence[float],
+               kij_matrix: Optional[Any], epsilon_ab: Optional[Any]) -> Tuple[List[Optional[np.ndarray]], np.ndarray]:
+    """(values of ``_run_mix``, the state row [1, 2 + nc]) of one point; RuntimeError on a status != 0"""
+    params, comp, kij, eab = _pool([parameters], [kij_matrix], [epsilon_ab])
+    states = _states([list(state)], len(parameters), comp.shape[1])
+    values, status = _run_mix(kind, params, comp, kij, eab, np.zeros(1, dtype=np.int64), states)
+    _require_ok(status, f"mixture {what}", state)
+    return values, states
 
 
 def mix_den(parameters: Sequence[Sequence[float]], state: Sequence[float], kij_matrix: Optional[Any] = None,
             epsilon_ab: Optional[Any] = None) -> float:
     """Mixture liquid density (mol/m³) at ``state = [T (K), P (Pa), x1, x2, ...]`` of the components ``parameters``
     (reference ``mix_den_feos``); raises ``RuntimeError`` where no liquid root is found."""
-    params, comp, kij, eab = _pool([parameters], [kij_matrix], [epsilon_ab])
-    states = _states([list(state)], len(parameters), comp.shape[1])
-    value, status = _run_mix(params, comp, kij, eab, np.zeros(1, dtype=np.int64), states)
-    if status[0] != STATUS_OK:
-        raise RuntimeError(f"PC-SAFT mixture density failed at state {list(state)}: "
-                           f"{_REASON.get(int(status[0]), int(status[0]))}")
-    return float(value[0])
-
-
-def _run_mix_phi(params: np.ndarray, comp: np.ndarray, kij: Optional[np.ndarray], eab: Optional[np.ndarray],
-                 owner: np.ndarray, states: np.ndarray, pure: bool
-                 ) -> Tuple[np.ndarray, Optional[np.ndarray], np.ndarray]:
-    """One upload, one launch, one download: (lnphi [n, nc], lnphi_pure [n, nc] or None, status [n] int32) for host
-    arrays; states [n, 2 + nc]."""
-    B, (M, nc), n = params.shape[0], comp.shape, owner.shape[0]
-    dev = _device()
-    d_params, d_T, d_P, d_x, d_kij, d_eab, d_comp, d_owner = _upload(
-        dev, [params, states[:, 0], states[:, 1], states[:, 2:], kij, eab, comp, owner])
-    # every output in one buffer: rho [n] | lnphi [n, nc] | lnphi_pure [n, nc] | status (int32, padded to 8 bytes)
-    w = n * nc
-    end = n + w * (2 if pure else 1)
-    out = torch.empty(end + (n + 1) // 2, dtype=torch.int64, device=dev)
-    flt = out.view(torch.float64)
-    status = out[end:].view(torch.int32)[:n]
-    ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
-    _lib.check(_lib.load().gnx_pcsaft_mix_lnphi(_lib.handle(dev), d_params.data_ptr(), B, d_comp.data_ptr(), ptr(d_kij),
-                                                ptr(d_eab), M, nc, d_owner.data_ptr(), d_T.data_ptr(), d_P.data_ptr(),
-                                                d_x.data_ptr(), n, flt[:n].data_ptr(), flt[n:n + w].data_ptr(),
-                                                flt[n + w:end].data_ptr() if pure else None, status.data_ptr()))
-    host = out.cpu().numpy()
-    val = host[:end].view(np.float64)
-    return (val[n:n + w].reshape(n, nc).copy(), val[n + w:end].reshape(n, nc).copy() if pure else None,
-            host[end:].view(np.int32)[:n].copy())
+    (rho,), _ = _mix_point("density", "density", parameters, state, kij_matrix, epsilon_ab)
+    return float(rho[0])
 
 
 def _phi_point(what: str, parameters: Sequence[Sequence[float]], state: Sequence[float], kij_matrix: Optional[Any],
                epsilon_ab: Optional[Any], pure: bool) -> Tuple[np.ndarray, Optional[np.ndarray], np.ndarray]:
     """(lnphi [k], lnphi_pure [k] or None, x [k] normalised by its sum) of one point; RuntimeError on a status != 0"""
     k = len(parameters)
-    params, comp, kij, eab = _pool([parameters], [kij_matrix], [epsilon_ab])
-    states = _states([list(state)], k, comp.shape[1])
-    lnphi, lnphi_pure, status = _run_mix_phi(params, comp, kij, eab, np.zeros(1, dtype=np.int64), states, pure)
-    if status[0] != STATUS_OK:
-        raise RuntimeError(f"PC-SAFT mixture {what} failed at state {list(state)}: "
-                           f"{_REASON.get(int(status[0]), int(status[0]))}")
+    (_, lnphi, lnphi_pure), states = _mix_point(what, "lnphi_pure" if pure else "lnphi", parameters, state, kij_matrix,
+                                                 epsilon_ab)
     x = states[0, 2:2 + k]
     return lnphi[0, :k], None if lnphi_pure is None else lnphi_pure[0, :k], x / x.sum()
 
@@ -398,16 +393,8 @@ def mix_ln_phi_batch(mixtures: List[List[List[Any]]], states_batch: List[Any], k
     """ln phi_i of every state of every non-empty table in one launch, arguments as ``mix_rho_batch``: one fp64 array
     [rows, nc_i] per non-empty table, a row of NaN where a point failed.  With ``activity`` the arrays hold ln gamma_i
     = ln phi_i - ln phi_i^pure instead (NaN where a component has no liquid root of its own)."""
-    if len(mixtures) != len(states_batch):
-        raise ValueError(f"{len(mixtures)} mixtures but {len(states_batch)} state tables")
-    tables = [(i, s) for i, s in enumerate(states_batch) if np.shape(s)[0] > 0]
-    if not tables:
-        return []
-    params, comp, d_kij, _ = _pool(mixtures, kij, None)
-    nc = comp.shape[1]
-    states = np.concatenate([_states(s, len(mixtures[i]), nc) for i, s in tables])
-    owner = np.concatenate([np.full(np.shape(s)[0], i, dtype=np.int64) for i, s in tables])
-    lnphi, lnphi_pure, _ = _run_mix_phi(params, comp, d_kij, None, owner, states, activity)
-    value = lnphi - lnphi_pure if activity else lnphi
-    cuts = np.cumsum([np.shape(s)[0] for _, s in tables])[:-1]
-    return [v[:, :len(mixtures[i])].copy() for v, (i, _) in zip(np.split(value, cuts), tables)]
+    def pick(values):
+        return values[1] - values[2] if activity else values[1]
+
+    parts = _mix_batch("lnphi_pure" if activity else "lnphi", mixtures, states_batch, kij, pick)
+    return [v[:, :len(mixtures[i])].copy() for i, v in parts]

@@ -184,6 +184,23 @@ def test_reference_shaped_batch_io(gpu_device):
             assert r == pcsaft.pure_den(params[i], s[:2].tolist())
     assert vp[-1][1] == 0.0 and vp[-1][0] > 0.0  # methane-like row: 400 K is supercritical, 100 K is not
     assert pcsaft.vp_batch(params, [empty] * len(params)) == []
+    # the tensor forms give the bits of the host forms on the same points (the host forms pass NULL for rho_l / rho_v)
+    d_params = torch.tensor(params, dtype=torch.float64, device=gpu_device)
+
+    def stacked(tables):
+        live = [(i, t) for i, t in enumerate(tables) if len(t) > 0]
+        owner = torch.tensor([i for i, t in live for _ in t], dtype=torch.int64, device=gpu_device)
+        return owner, torch.tensor(np.concatenate([t for _, t in live]), dtype=torch.float64, device=gpu_device)
+
+    owner, states = stacked(rho_tables)
+    rho, status = pcsaft.density(d_params, states[:, 0], states[:, 1], owner)
+    assert torch.equal(rho.cpu(), torch.from_numpy(np.concatenate(den)))
+    assert bool((rho[status != 0] == 0.0).all())
+    owner, states = stacked(vp_tables)
+    psat, rho_l, rho_v, status = pcsaft.vapor_pressure(d_params, states[:, 0], owner)
+    assert torch.equal(psat.cpu(), torch.from_numpy(np.concatenate(vp)))
+    assert status.tolist()[-2:] == [0, 2] and bool((psat[status != 0] == 0.0).all())
+    assert bool(((rho_l > rho_v) & (rho_v > 0.0))[status == 0].all()) and bool((rho_l[status != 0] == 0.0).all())
 
 
 def _oracle_batch(kind, rows, tables):
