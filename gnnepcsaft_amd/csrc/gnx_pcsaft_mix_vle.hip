@@ -1,0 +1,221 @@
+// Mixture PC-SAFT bubble point in fp64: at (T, x) the pressure P at which the liquid x is in equilibrium with a first
+// bubble of vapour, that vapour's composition y and both densities, on the model of gnx_pcsaft_mix.hpp (ref:
+// pcsaft/pcsaft_feos.py mix_vp_feos, the bubble half, and mix_vle_pxy_diagram_feos; [3P] feos 0.8
+// PhaseEquilibrium.bubble_point / PhaseDiagram.binary_vle).  DESIGN.md §4c.
+//
+// Equilibrium in the form without ln Z: with ln f_i = mu_i^res/kT + ln(rho x_i), rho the number density of the phase,
+//   ln f_i^L(T, rho_L, x) = ln f_i^V(T, rho_V, y) for every component,  p(T, rho_L, x) = p(T, rho_V, y) = P.
+// ln phi_i = ln f_i - ln(x_i p/kT) carries -ln Z, and Z of a liquid at 0.4 Pa is 1e-11: written through ln phi the
+// equations would lose six digits there.
+//
+// Successive substitution.  Start: the liquid root at zero pressure, P = kT sum_i f_i^L, y_i = f_i^L kT / P (an ideal
+// vapour).  Step: liquid root of x and vapour root of y at P, K_i = (f_i^L/x_i)/(f_i^V/y_i), s = sum_i x_i K_i,
+// y <- x K / s, P <- P s; it ends when max(|ln s|, max_i |d ln y_i|) < 1e-10, and what is reported is the state at which
+// the fugacities were evaluated, so that the equations hold to that bound at the numbers returned.  The liquid root is
+// density_root (the highest root with dp/drho > 0), the vapour root the lowest one, from an upward scan.
+//
+// One lane per point, no shared memory, no atomics, every loop with a fixed trip cap: same input, same bits.  The
+// launch carries no kernel id (GNX_K_NONE): the profiling tables keep their 26 entries and the profiler hook of the
+// launch scope is off; time it with events around the call (tools/pcsaft_bench.py --bubble).
+#include "gnx_pcsaft_mix_grad.hpp"
+
+namespace {
+
+constexpr int kVleScanLog = 64;       // vapour scan: 64 log-spaced points in [1e-10, 1e-2) ...
+constexpr int kVleScanLin = 512;      // ... then 512 linear points in (1e-2, kEtaMax]
+constexpr int kVleMixIters = 200;     // successive substitution steps
+constexpr int kVleMixDamp = 20;       // halvings of a pressure step in a row that finds no vapour root
+// the liquid's mu^res moves by (dp/drho)/(RT) ~ 1e2 .. 1e3 per relative change of rho and a root ends at 1e-14: the
+// residual's rounding floor is about 1e-11
+constexpr double kVleMixTol = 1e-10;
+constexpr double kVleTrivial = 1e-3;  // rho_l - rho_v <= this * rho_l: both phases are the same fluid
+
+__device__ __forceinline__ double vapour_grid(int k) {
+  return k < kVleScanLog ? 1e-10 * ::pow(1e8, (double)k / kVleScanLog)
+                         : 1e-2 + (kEtaMax - 1e-2) * (double)(k - kVleScanLog + 1) / kVleScanLin;
+}
+
+enum : int { VR_OK = 0, VR_NONE = 1, VR_FAIL = 2 };
+
+// packing fraction of the lowest root of p~(eta) = pt with dp/deta > 0.  VR_NONE: p~ turns over (dp/deta <= 0) below
+// pt, the mixture has no vapour at this pressure; VR_FAIL: an evaluation failed.
+__device__ int vapour_root(Mix& c, double pt, double& out) {
+  double lo = 0.0;
+  for (int k = 0; k < kVleScanLog + kVleScanLin; ++k) {
+    const double eta = vapour_grid(k);
+    const Mix::Eval e = c.eval(eta);
+    if (!e.ok || !isfinite(e.p) || !isfinite(e.dp)) return VR_FAIL;
+    if (e.p >= pt) {
+      double xr;
+      if (!pcsaft_root(c, pt, lo, eta, pt * c.c3, xr) || !(xr > 0.0)) return VR_FAIL;
+      const Mix::Eval r = c.eval(xr);
+      if (!r.ok) return VR_FAIL;
+      if (!(r.dp > 0.0)) return VR_NONE;
+      out = xr;
+      return VR_OK;
+    }
+    if (!(e.dp > 0.0)) return VR_NONE;
+    lo = eta;
+  }
+  return VR_NONE;
+}
+
+// ln f_i = mu_i^res/kT + ln(rn x_i) of the components present, in their compact order, at (T, number density rn, x).  c
+// is the mixture in real arithmetic, initialised from the same arguments; every used slot must have x > 0.  The sibling
+// of gnx_pcsaft_mix_phi.hip's mix_lnphi_at without the ln Z:
+//   mu_i^res/kT = a + (Z - 1) + a_xi - sum_j x_j a_xj,  a_xi = da/dx_i at fixed T, rho, the x independent
+__device__ bool mix_lnf_at(const double* __restrict__ params, int64_t B, const int64_t* comp,
+                           const double* __restrict__ kij, const double* __restrict__ eab, int nc, const double* xin,
+                           double T, double rn, Mix& c, double* lnf) {
+  if (!(rn > 0.0) || !(rn * c.c3 < 1.0)) return false;
+  const Mix::Eval e = c.eval_rho(rn);  // Z from the second-order dual in rho; leaves the converged X_A in c.xa
+  if (!e.ok || !isfinite(e.a) || !isfinite(e.z)) return false;
+  MixT<GX> g;
+  if (!g.init(params, B, comp, kij, eab, nc, xin, T)) return false;
+  GX xaG[NC_MAX];
+  for (int i = 0; i < NC_MAX; ++i) xaG[i] = GX(1.0);
+  if (c.assoc && !mix_sites_grad(c, g, rn, xaG)) return false;
+  const GX a = g.a_res(GX(rn), xaG);
+  double sum = 0.0;
+  for (int s = 0; s < nc; ++s)
+    if (comp[s] != -1) sum += xin[s];
+  double xs = 0.0;
+  int k = 0;
+  for (int s = 0; s < nc; ++s)
+    if (comp[s] != -1) xs += xin[s] / sum * a.g[k++];
+  const double base = a.v + (e.z - 1.0) - xs;
+  k = 0;
+  bool fin = true;
+  for (int s = 0; s < nc; ++s)
+    if (comp[s] != -1) {
+      lnf[k] = base + a.g[k] + ::log(rn * (xin[s] / sum));
+      fin = fin && isfinite(lnf[k]);
+      ++k;
+    }
+  return fin;
+}
+
+// bubble point of point i at (T, x)
+__device__ void mix_bubble_point(const double* __restrict__ params, int64_t B, const int64_t* __restrict__ mix_comp,
+                                 const double* __restrict__ mix_kij, const double* __restrict__ mix_eab, int64_t M, int nc,
+                                 const int64_t* __restrict__ owner, const double* __restrict__ T,
+                                 const double* __restrict__ x, int64_t i, double* __restrict__ P, double* __restrict__ y,
+                                 double* __restrict__ rho_l, double* __restrict__ rho_v, int32_t* __restrict__ status) {
+  Mix cl, cv;
+  const double t = T[i];
+  int32_t st = ST_BAD_INPUT;
+  double pt = 0.0, rl = 0.0, rv = 0.0, yv[NC_MAX];
+  int64_t cm[NC_MAX];  // the mixture's slots with those that are absent (x = 0) marked unused
+  for (int s = 0; s < NC_MAX; ++s) {
+    yv[s] = 0.0;
+    cm[s] = -1;
+  }
+  if (load_mix(params, B, mix_comp, mix_kij, mix_eab, M, nc, owner, x, i, t, cl)) {
+    st = ST_NO_CONV;
+    const int64_t o = owner[i];
+    const double* kij = mix_kij ? mix_kij + o * nc * nc : nullptr;
+    const double* eab = mix_eab ? mix_eab + o * nc * nc : nullptr;
+    const double* xin = x + i * nc;
+    for (int s = 0; s < nc; ++s) {
+      const int64_t c = mix_comp[o * nc + s];
+      cm[s] = (c != -1 && xin[s] > 0.0) ? c : -1;
+    }
+    const int n = cl.n;
+    double pprev = 0.0, lnf[2][NC_MAX];
+    int damp = 0;
+    bool ok = true, conv = false;
+    // it = -1 is the start: the liquid at zero pressure under an ideal vapour
+    for (int it = -1; ok && !conv && it < kVleMixIters; ++it) {
+      const bool start = it < 0;
+      double el, ev = 0.0;
+      ok = density_root(cl, start ? 0.0 : pt, el) == ST_OK;
+      // without a liquid at zero pressure the scan runs out at its lowest step and the root is the dilute gas: the point
+      // is too close to the mixture's critical region for this method
+      if (ok && start) ok = el >= kEtaMax / kScanDensity;
+      if (!ok) break;
+      if (!start) {
+        ok = cv.init(params, B, cm, kij, eab, nc, yv, t) && cv.n == n;
+        if (!ok) break;
+        const int vr = vapour_root(cv, pt, ev);
+        if (vr == VR_NONE && ++damp <= kVleMixDamp) {
+          pt = 0.5 * (pt + pprev);  // no vapour of y at this pressure: half the step back
+          continue;
+        }
+        ok = vr == VR_OK;
+        if (!ok) break;
+        damp = 0;
+      }
+      // at the densities reported, converted as the state forms convert them
+      rl = molar_density(el, cl.c3);
+      rv = start ? 0.0 : molar_density(ev, cv.c3);
+      for (int ph = 0; ok && ph < (start ? 1 : 2); ++ph)
+        ok = mix_lnf_at(params, B, cm, kij, eab, nc, ph ? yv : xin, t, number_density(ph ? rv : rl), ph ? cv : cl,
+                        lnf[ph]);
+      if (!ok) break;
+      double xk[NC_MAX], s = 0.0;  // x_i K_i = y_i f_i^L / f_i^V; at the start f_i^L itself
+      for (int q = 0, k = 0; q < nc; ++q)
+        if (cm[q] != -1) {
+          xk[k] = start ? ::exp(lnf[0][k]) : yv[q] * ::exp(lnf[0][k] - lnf[1][k]);
+          s += xk[k++];
+        }
+      ok = s > 0.0 && isfinite(s);
+      if (!ok) break;
+      if (!start) {
+        const double ls = ::log(s);
+        double res = ::fabs(ls);
+        for (int k = 0; k < n; ++k) res = ::fmax(res, ::fabs(lnf[0][k] - lnf[1][k] - ls));
+        ok = res == res;
+        conv = res < kVleMixTol;
+        if (conv || !ok) break;
+      }
+      int k = 0;
+      for (int q = 0; q < nc; ++q)
+        if (cm[q] != -1) {
+          yv[q] = xk[k++] / s;
+          ok = ok && yv[q] > 0.0;
+        }
+      pprev = start ? 0.0 : pt;
+      pt = start ? s : pt * s;
+      ok = ok && pt > 0.0 && isfinite(pt);
+    }
+    // equal densities: the trivial solution, both phases the same fluid
+    if (ok && conv && rv > 0.0 && rl - rv > kVleTrivial * rl) st = ST_OK;
+  }
+  const bool good = st == ST_OK;
+  P[i] = good ? pt * cl.kT_pa : 0.0;
+  if (rho_l) rho_l[i] = good ? rl : 0.0;
+  if (rho_v) rho_v[i] = good ? rv : 0.0;
+  const int64_t* comp = good ? mix_comp + owner[i] * nc : nullptr;
+  for (int s = 0; s < nc; ++s) y[i * nc + s] = (comp && comp[s] != -1) ? yv[s] : NAN;
+  status[i] = st;
+}
+
+__global__ void __launch_bounds__(256) k_pcsaft_mix_bubble(const double* __restrict__ params, int64_t B,
+                                                           const int64_t* __restrict__ mix_comp,
+                                                           const double* __restrict__ mix_kij,
+                                                           const double* __restrict__ mix_eab, int64_t M, int nc,
+                                                           const int64_t* __restrict__ owner, const double* __restrict__ T,
+                                                           const double* __restrict__ x, int64_t n,
+                                                           double* __restrict__ P, double* __restrict__ y,
+                                                           double* __restrict__ rho_l, double* __restrict__ rho_v,
+                                                           int32_t* __restrict__ status) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) mix_bubble_point(params, B, mix_comp, mix_kij, mix_eab, M, nc, owner, T, x, i, P, y, rho_l, rho_v, status);
+}
+
+}  // namespace
+
+extern "C" int32_t gnx_pcsaft_mix_bubble(gnx_handle* h, const double* params, int64_t B, const int64_t* mix_comp,
+                                         const double* mix_kij, const double* mix_eab, int64_t M, int32_t nc,
+                                         const int64_t* owner, const double* T, const double* x, int64_t n, double* P,
+                                         double* y, double* rho_l, double* rho_v, int32_t* status) {
+  GNX_MIX_CHECK("gnx_pcsaft_mix_bubble")
+  GNX_CHECK_ARG(owner && T && x && P && y && status && (params || B == 0) && (mix_comp || M == 0),
+                "gnx_pcsaft_mix_bubble: NULL argument");
+  // no kernel id of its own: under GNX_K_NONE the scope stays off and the launch is a plain one
+  gnx_prof_scope prof(h, GNX_K_NONE, (44.0 + 16.0 * nc) * n, 0.0, 0.0, true);
+  GNX_LAUNCH_TIMED(prof, k_pcsaft_mix_bubble, dim3((unsigned)gnx_cdiv(n, 256)), dim3(256), 0, h->stream, params, B,
+                   mix_comp, mix_kij, mix_eab, M, (int)nc, owner, T, x, n, P, y, rho_l, rho_v, status);
+  GNX_LAUNCH_CHECK();
+  return GNX_OK;
+}

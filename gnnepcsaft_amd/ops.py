@@ -1055,16 +1055,18 @@ def pcsaft_vapor_pressure(params: torch.Tensor, owner: torch.Tensor, T: torch.Te
     return _pcsaft_vapor_pressure(params, owner, T)
 
 
-# the four mixture forms: entry point and fp64 outputs in argument order (0: [n], 1: [n, nc]); the status follows them
+# the mixture forms: entry point and fp64 outputs in argument order (0: [n], 1: [n, nc]); the status follows them
 _PCSAFT_MIX = {"pcsaft_mix_state": ("gnx_pcsaft_mix_state", (0, 0, 0)),
                "pcsaft_mix_density": ("gnx_pcsaft_mix_density", (0,)),
                "pcsaft_mix_lnphi_state": ("gnx_pcsaft_mix_lnphi_state", (1, 0)),
-               "pcsaft_mix_lnphi": ("gnx_pcsaft_mix_lnphi", (0, 1, 1))}
+               "pcsaft_mix_lnphi": ("gnx_pcsaft_mix_lnphi", (0, 1, 1)),
+               "pcsaft_mix_bubble": ("gnx_pcsaft_mix_bubble", (0, 1, 0, 0))}
 
 
 def _pcsaft_mix(params, comp, kij, eab, owner, T, second, x, name, out=None, last=True):
-    """The mixture form ``name`` of ``_PCSAFT_MIX``: validate, take ``out`` or make the outputs, call.  ``last`` False
-    leaves the last fp64 output (lnphi_pure) out: None in the result, NULL for the entry."""
+    """The mixture form ``name`` of ``_PCSAFT_MIX``: validate, take ``out`` or make the outputs, call.  ``second`` is the
+    state beside T (rho or P), None for the bubble point, which has none.  ``last`` False leaves the last fp64 output
+    (lnphi_pure) out: None in the result, NULL for the entry."""
     entry, widths = _PCSAFT_MIX[name]
     params, owner, T = _pcsaft_args(params, owner, T, name)
     dev = params.device
@@ -1079,19 +1081,19 @@ def _pcsaft_mix(params, comp, kij, eab, owner, T, second, x, name, out=None, las
             if tuple(t.shape) != (M, nc, nc):
                 raise _lib.GnxError(_lib.GNX_E_INVALID, f"{name}: {label} must be [{M}, {nc}, {nc}], got {tuple(t.shape)}")
         mats.append(t)
-    second = _f64_on(second, f"{name}: state", dev)
+    state = [] if second is None else [_f64_on(second, f"{name}: state", dev)]
     x = _f64_on(x, f"{name}: x", dev)
     n = T.numel()
-    if second.shape != T.shape or tuple(x.shape) != (n, nc):
-        raise _lib.GnxError(_lib.GNX_E_INVALID, f"{name}: T {tuple(T.shape)}, state {tuple(second.shape)} and x "
-                                                f"{tuple(x.shape)} do not describe n points of {nc} components")
+    if any(t.shape != T.shape for t in state) or tuple(x.shape) != (n, nc):
+        raise _lib.GnxError(_lib.GNX_E_INVALID, f"{name}: T {tuple(T.shape)}, state {[tuple(t.shape) for t in state]} "
+                                                f"and x {tuple(x.shape)} do not describe n points of {nc} components")
     specs = [((n, nc) if w else (n,), _F64) for w in widths] + [((n,), _ST)]
     if not last:
         specs[-2] = None
     out = _pcsaft_outs(out, specs, dev, name)
     check(getattr(_lib.load(), entry)(handle(dev), params.data_ptr(), params.size(0), comp.data_ptr(), _ptr(mats[0]),
-                                      _ptr(mats[1]), M, nc, owner.data_ptr(), T.data_ptr(), second.data_ptr(),
-                                      x.data_ptr(), n, *map(_ptr, out)))
+                                      _ptr(mats[1]), M, nc, owner.data_ptr(), T.data_ptr(),
+                                      *(t.data_ptr() for t in state), x.data_ptr(), n, *map(_ptr, out)))
     return out
 
 
@@ -1129,6 +1131,21 @@ def pcsaft_mix_lnphi(params: torch.Tensor, comp: torch.Tensor, kij: Optional[tor
     ``pcsaft_mix_density`` -> (rho [n] mol/m^3, the bits of ``pcsaft_mix_density``; lnphi [n, nc]; lnphi_pure [n, nc] if
     ``pure`` else None: each component alone at its own liquid root, NaN where it has none; status [n] int32)."""
     return _pcsaft_mix(params, comp, kij, eab, owner, T, P, x, "pcsaft_mix_lnphi", last=pure)
+
+
+def _pcsaft_mix_bubble(params, comp, kij, eab, owner, T, x, out=None):
+    """``pcsaft_mix_bubble`` writing into ``out`` = (P, y, rho_l, rho_v, status) where given; rho_l and rho_v may be None
+    there."""
+    return _pcsaft_mix(params, comp, kij, eab, owner, T, None, x, "pcsaft_mix_bubble", out=out)
+
+
+def pcsaft_mix_bubble(params: torch.Tensor, comp: torch.Tensor, kij: Optional[torch.Tensor],
+                      eab: Optional[torch.Tensor], owner: torch.Tensor, T: torch.Tensor, x: torch.Tensor
+                      ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Mixture PC-SAFT bubble point at (T, x) (gnx_pcsaft_mix_bubble): arguments as ``pcsaft_mix_state`` without rho
+    -> (P [n] Pa, y [n, nc], rho_l [n], rho_v [n] mol/m^3, status [n] int32).  A used slot with x = 0 is dropped (y = 0.0),
+    a -1 slot has y = NaN; where status != 0, P and the densities are 0.0 and the y row is NaN."""
+    return _pcsaft_mix_bubble(params, comp, kij, eab, owner, T, x)
 
 
 _POOL = {"add": _lib.POOL_ADD, "sum": _lib.POOL_ADD, "mean": _lib.POOL_MEAN, "max": _lib.POOL_MAX}

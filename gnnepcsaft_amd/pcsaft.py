@@ -22,6 +22,11 @@ state (pcsaft/pcsaft_feos.py): ``mix_ln_fugacity_coefficient``, ``mix_ln_fugacit
 device tensors (csrc/gnx_pcsaft_mix_phi.hip).  There a component with x = 0 stays in the mixture: its ln phi is the
 value at infinite dilution.  x is normalised by its sum, and 0 ln 0 counts as 0 in ``mix_gibbs_energy``.
 
+Bubble points of a mixture, the pressure at which the liquid x starts to boil at T and the vapour y that forms
+(csrc/gnx_pcsaft_mix_vle.hip): ``mix_bubble`` for one point (the bubble half of the reference's ``mix_vp_feos``),
+``mix_bubble_batch`` for every point of every system in one launch, ``mix_vle_pxy`` for the P-x-y diagram of a binary
+(``mix_vle_pxy_diagram_feos``), ``mixture_bubble_pressure`` on device tensors.  Dew pressures are not provided.
+
 Parameter rows are ``[m, sigma (Å), epsilon/k (K), kappa_ab, epsilon_ab/k (K), mu (D), na, nb, mw]``; state rows are
 ``[T (K), P (Pa), phase, tp, value]`` (only T and P are read).  Densities are in mol/m³, pressures in Pa.
 """
@@ -229,11 +234,26 @@ def mixture_ln_phi(params: torch.Tensor, comp: torch.Tensor, x: torch.Tensor, T:
     return ops.pcsaft_mix_lnphi(params, comp, kij, eab, _owner(owner, T), T, P, x, pure)
 
 
+def mixture_bubble_pressure(params: torch.Tensor, comp: torch.Tensor, x: torch.Tensor, T: torch.Tensor,
+                            owner: Optional[torch.Tensor] = None, kij: Optional[torch.Tensor] = None,
+                            eab: Optional[torch.Tensor] = None
+                            ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Tensor form on device tensors, arguments as ``mixture_state`` without rho -> (P [n] Pa, y [n, nc], rho_l [n],
+    rho_v [n] mol/m³, status [n] int32): the bubble point of the liquid x at T.  A used slot with x = 0 is dropped
+    (y = 0.0), a -1 slot has y = NaN; where status != 0 (1 also means "no bubble point at this T"), P and the densities
+    are 0.0 and the y row is NaN.  Asynchronous, on the current stream."""
+    return ops.pcsaft_mix_bubble(params, comp, kij, eab, _owner(owner, T), T, x)
+
+
 def _run_mix(kind: str, params: np.ndarray, comp: np.ndarray, kij: Optional[np.ndarray], eab: Optional[np.ndarray],
              owner: np.ndarray, states: np.ndarray) -> Tuple[List[Optional[np.ndarray]], np.ndarray]:
     """states [n, 2 + nc] -> (values, status [n] int32); values is [rho [n]] for kind "density", [rho, lnphi [n, nc],
-    None] for "lnphi" and [rho, lnphi, lnphi_pure [n, nc]] for "lnphi_pure"."""
+    None] for "lnphi", [rho, lnphi, lnphi_pure [n, nc]] for "lnphi_pure" and [P [n], y [n, nc], rho_l [n], rho_v [n]]
+    for "bubble", which does not read the P column."""
     n, nc = owner.shape[0], comp.shape[1]
+    if kind == "bubble":
+        return _run(ops._pcsaft_mix_bubble, [params, comp, kij, eab, owner, states[:, 0], states[:, 2:]], n,
+                    [(n,), (n, nc), (n,), (n,)])
     inputs = [params, comp, kij, eab, owner, states[:, 0], states[:, 1], states[:, 2:]]
     if kind == "density":
         return _run(ops._pcsaft_mix, inputs, n, [(n,)], name="pcsaft_mix_density")
@@ -398,3 +418,53 @@ def mix_ln_phi_batch(mixtures: List[List[List[Any]]], states_batch: List[Any], k
 
     parts = _mix_batch("lnphi_pure" if activity else "lnphi", mixtures, states_batch, kij, pick)
     return [v[:, :len(mixtures[i])].copy() for i, v in parts]
+
+
+def _failed_nan(values: np.ndarray, P: np.ndarray) -> np.ndarray:
+    """rows of NaN where a bubble point failed (P = 0.0)"""
+    return np.where((P > 0.0)[:, None], values, np.nan)
+
+
+def mix_bubble(parameters: Sequence[Sequence[float]], state: Sequence[float], kij_matrix: Optional[Any] = None,
+               epsilon_ab: Optional[Any] = None) -> Tuple[float, np.ndarray]:
+    """Bubble point of the liquid ``state = [T (K), P, x1, x2, ...]`` (P is ignored) of the components ``parameters``:
+    (P (Pa), y [k]), the bubble half of the reference's ``mix_vp_feos``; raises ``RuntimeError`` where there is no
+    bubble point at this T or the solve does not converge."""
+    (P, y, _, _), _ = _mix_point("bubble point", "bubble", parameters, state, kij_matrix, epsilon_ab)
+    return float(P[0]), y[0, :len(parameters)].copy()
+
+
+def mix_bubble_batch(mixtures: List[List[List[Any]]], states_batch: List[Any], kij: Optional[List[Any]] = None
+                     ) -> List[np.ndarray]:
+    """Bubble points of every state of every non-empty table in one launch, arguments as ``mix_rho_batch`` (the P column
+    is ignored): one fp64 array [rows, 1 + nc_i] of rows ``[P (Pa), y1..y_nc]`` per non-empty table, a row of NaN where a
+    point failed."""
+    def pick(values):
+        return _failed_nan(np.concatenate([values[0][:, None], values[1]], axis=1), values[0])
+
+    parts = _mix_batch("bubble", mixtures, states_batch, kij, pick)
+    return [v[:, :1 + len(mixtures[i])].copy() for i, v in parts]
+
+
+def mix_vle_pxy(parameters: Sequence[Sequence[float]], temperature: float, kij_matrix: Optional[Any] = None,
+                epsilon_ab: Optional[Any] = None, points: int = 51) -> dict:
+    """P-x-y diagram of a binary at ``temperature`` (reference ``mix_vle_pxy_diagram_feos``): the bubble points at
+    x_first = linspace(0, 1, points) in one launch, as a dict of equally long lists under the keys ``temperature``,
+    ``pressure`` (Pa), ``density liquid``, ``density vapor`` (mol/m³), ``x0``, ``x1``, ``y0``, ``y1`` (x0, y0: the first
+    component).  Points without a bubble point (beyond the critical composition) are dropped; ``ValueError`` if none is
+    left, and for anything but two components.  The dew curve is y(x) along these points."""
+    if len(parameters) != 2:
+        raise ValueError(f"a P-x-y diagram needs a binary mixture, got {len(parameters)} components")
+    if int(points) < 2:
+        raise ValueError(f"a P-x-y diagram needs at least 2 points, got {points}")
+    params, comp, kij, eab = _pool([parameters], [kij_matrix], [epsilon_ab])
+    x0 = np.linspace(0.0, 1.0, int(points))
+    states = _states(np.stack([np.full_like(x0, float(temperature)), np.zeros_like(x0), x0, 1.0 - x0], axis=1), 2, 2)
+    (P, y, rho_l, rho_v), status = _run_mix("bubble", params, comp, kij, eab, np.zeros(len(x0), dtype=np.int64), states)
+    keep = status == STATUS_OK
+    if not keep.any():
+        raise ValueError("No VLE found at the given conditions.")
+    return {"temperature": states[keep, 0].tolist(), "pressure": P[keep].tolist(),
+            "density liquid": rho_l[keep].tolist(), "density vapor": rho_v[keep].tolist(),
+            "x0": x0[keep].tolist(), "x1": (1.0 - x0)[keep].tolist(),
+            "y0": y[keep, 0].tolist(), "y1": y[keep, 1].tolist()}

@@ -479,6 +479,19 @@ int32_t gnx_pcsaft_mix_lnphi(gnx_handle* h, const double* params, int64_t B, con
                              const double* mix_kij, const double* mix_eab, int64_t M, int32_t nc, const int64_t* owner,
                              const double* T, const double* P, const double* x, int64_t n, double* rho, double* lnphi,
                              double* lnphi_pure, int32_t* status);
+/* Bubble point (ref: pcsaft/pcsaft_feos.py mix_vp_feos, the bubble half, and mix_vle_pxy_diagram_feos): at T[i] and the
+ * liquid composition x[i, :] the pressure P[i] (Pa) at which a first bubble of vapour forms, that vapour's composition
+ * y[i, :] and the molar densities rho_l[i], rho_v[i] of both phases (either may be NULL).  Equal mu_i^res/kT + ln(rho x_i)
+ * of every component and equal pressure, by successive substitution from an ideal-vapour start; the equations hold to
+ * 1e-10 at the numbers returned.  As in the density entry a used slot with x = 0 is dropped; its y is 0.0, that of a -1
+ * slot NaN.  A point with status != 0 has P = 0.0, NaN in its whole y row and densities 0.0; status 1 covers every
+ * failure that is not bad input, "no bubble point at this T" (no liquid root at zero pressure: too close to the
+ * mixture's critical region, or above it) among them.  The launch has no kernel id (GNX_K_NONE): it is not in the
+ * profiling tables. */
+int32_t gnx_pcsaft_mix_bubble(gnx_handle* h, const double* params, int64_t B, const int64_t* mix_comp,
+                              const double* mix_kij, const double* mix_eab, int64_t M, int32_t nc, const int64_t* owner,
+                              const double* T, const double* x, int64_t n, double* P, double* y, double* rho_l,
+                              double* rho_v, int32_t* status);
 
 /* ---- contiguous segment reduce: global pool (ref: train/models.py:218-225, 587-595) ------------------------ */
 enum { GNX_POOL_ADD = 0, GNX_POOL_MEAN = 1, GNX_POOL_MAX = 2 };

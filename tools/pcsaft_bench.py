@@ -8,7 +8,11 @@ With ``--mixture`` it times the mixture kernels of csrc/gnx_pcsaft_mix.hip and c
 kernel on the same points (without and with the pure-component values, and its state form), ``mix_rho_batch`` end to
 end, and the mixture oracle (tests/pcsaft_mix_ref.py) on a sample.
 
-Usage: python tools/pcsaft_bench.py [--mixture] [--sizes 1000,100000,1000000] [--oracle-sample 20] [--out FILE.json]
+With ``--bubble`` it times the bubble-point kernel of csrc/gnx_pcsaft_mix_vle.hip on the six named systems of
+tests/pcsaft_mix_vle_ref.py and the first point of each system of the binary fixture, repeated, and that module's oracle
+solve on a sample.  The launch has no kernel id, so the events around the call are the only timing there is.
+
+Usage: python tools/pcsaft_bench.py [--mixture | --bubble] [--sizes 1000,100000,1000000] [--oracle-sample 20] [--out FILE.json]
 """
 import argparse
 import json
@@ -75,16 +79,45 @@ def _mixture(args, dev):
     return res
 
 
+def _bubble(args, dev):
+    from tests import pcsaft_mix_vle_ref as V
+    cases = list(V.NAMED) + V.fixture_cases()
+    params, comp, T, x = [], np.full((len(cases), 4), -1, dtype=np.int64), [], np.zeros((len(cases), 4))
+    for i, (_, rows, t, xi) in enumerate(cases):
+        comp[i, :len(rows)] = np.arange(len(params), len(params) + len(rows))
+        params.extend(np.asarray(rows, dtype=np.float64).tolist())
+        x[i, :len(rows)] = xi
+        T.append(t)
+    T = np.array(T)
+    step = max(1, len(cases) // args.oracle_sample)
+    t0 = time.perf_counter()
+    sols = [V.bubble(rows, xi, t, max_iterations=100) for _, rows, t, xi in cases[::step]]
+    oracle = (time.perf_counter() - t0) / len(sols)
+    d_params, d_comp = torch.from_numpy(np.array(params)).to(dev), torch.from_numpy(comp).to(dev)
+    res = []
+    for n in [int(s) for s in args.sizes.split(",")]:
+        idx = np.arange(n) % len(cases)
+        o, t, xx = (torch.from_numpy(np.ascontiguousarray(a)).to(dev) for a in (idx.astype(np.int64), T[idx], x[idx]))
+        k = _kernel_ms(lambda: pcsaft.mixture_bubble_pressure(d_params, d_comp, xx, t, o))
+        st = pcsaft.mixture_bubble_pressure(d_params, d_comp, xx, t, o)[4]
+        rec = dict(points=n, mix_bubble_kernel_ms=k, mix_bubble_points_per_s=n / k * 1e3,
+                   failed_points=int((st != 0).sum().item()), oracle_bubble_ms_est=oracle * n * 1e3)
+        print(json.dumps(rec))
+        res.append(rec)
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sizes", default="1000,100000,1000000")
     ap.add_argument("--oracle-sample", type=int, default=20)
     ap.add_argument("--mixture", action="store_true")
+    ap.add_argument("--bubble", action="store_true")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
-    if args.mixture:
+    if args.mixture or args.bubble:
         dev = torch.device("cuda", torch.cuda.current_device())
-        res = _mixture(args, dev)
+        res = (_bubble if args.bubble else _mixture)(args, dev)
         if args.out:
             with open(args.out, "w") as fh:
                 json.dump(dict(device=torch.cuda.get_device_name(dev), oracle_sample=args.oracle_sample, results=res), fh,
