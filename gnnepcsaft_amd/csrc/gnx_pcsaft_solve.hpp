@@ -20,8 +20,9 @@ constexpr int kScanDensity = 512;   // downward eta scan of the density solve (s
 constexpr int kRootIters = 200;     // safeguarded Newton of one density at a given pressure
 constexpr double kRootTol = 1e-14;  // relative step / bracket width that ends a root solve
 
-// ST_SUPERCRITICAL is reported by the vapour pressure alone; no mixture entry gives it
-enum : int32_t { ST_OK = 0, ST_NO_CONV = 1, ST_SUPERCRITICAL = 2, ST_BAD_INPUT = 3 };
+// ST_SUPERCRITICAL is reported by the vapour pressure alone; no mixture entry gives it.  ST_SINGLE_PHASE is the flash's:
+// no vapour-liquid split at (T, P, z)
+enum : int32_t { ST_OK = 0, ST_NO_CONV = 1, ST_SUPERCRITICAL = 2, ST_BAD_INPUT = 3, ST_SINGLE_PHASE = 4 };
 
 // a parameter row [m, sigma, eps/k, kappa_ab, eps_ab/k, mu, na, nb, mw]: m, sigma, eps > 0, the rest >= 0, all finite
 __device__ __forceinline__ bool valid_row(const double* __restrict__ row) {

@@ -1060,7 +1060,8 @@ _PCSAFT_MIX = {"pcsaft_mix_state": ("gnx_pcsaft_mix_state", (0, 0, 0)),
                "pcsaft_mix_density": ("gnx_pcsaft_mix_density", (0,)),
                "pcsaft_mix_lnphi_state": ("gnx_pcsaft_mix_lnphi_state", (1, 0)),
                "pcsaft_mix_lnphi": ("gnx_pcsaft_mix_lnphi", (0, 1, 1)),
-               "pcsaft_mix_bubble": ("gnx_pcsaft_mix_bubble", (0, 1, 0, 0))}
+               "pcsaft_mix_bubble": ("gnx_pcsaft_mix_bubble", (0, 1, 0, 0)),
+               "pcsaft_mix_flash": ("gnx_pcsaft_mix_flash", (0, 1, 1, 0, 0))}
 
 
 def _pcsaft_mix(params, comp, kij, eab, owner, T, second, x, name, out=None, last=True):
@@ -1146,6 +1147,22 @@ def pcsaft_mix_bubble(params: torch.Tensor, comp: torch.Tensor, kij: Optional[to
     -> (P [n] Pa, y [n, nc], rho_l [n], rho_v [n] mol/m^3, status [n] int32).  A used slot with x = 0 is dropped (y = 0.0),
     a -1 slot has y = NaN; where status != 0, P and the densities are 0.0 and the y row is NaN."""
     return _pcsaft_mix_bubble(params, comp, kij, eab, owner, T, x)
+
+
+def _pcsaft_mix_flash(params, comp, kij, eab, owner, T, P, z, out=None):
+    """``pcsaft_mix_flash`` writing into ``out`` = (beta, x, y, rho_l, rho_v, status) where given; rho_l and rho_v may be
+    None there."""
+    return _pcsaft_mix(params, comp, kij, eab, owner, T, P, z, "pcsaft_mix_flash", out=out)
+
+
+def pcsaft_mix_flash(params: torch.Tensor, comp: torch.Tensor, kij: Optional[torch.Tensor],
+                     eab: Optional[torch.Tensor], owner: torch.Tensor, T: torch.Tensor, P: torch.Tensor, z: torch.Tensor
+                     ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Mixture PC-SAFT two-phase flash at (T, P, z) (gnx_pcsaft_mix_flash): arguments as ``pcsaft_mix_density`` with the
+    feed z [n, nc] in place of x -> (beta [n] vapour mole fraction, x [n, nc], y [n, nc], rho_l [n], rho_v [n] mol/m^3,
+    status [n] int32; 4 = no vapour-liquid split).  A used slot with z = 0 is dropped (x = y = 0.0), a -1 slot has NaN;
+    where status != 0, beta and the densities are 0.0 and the x and y rows are NaN."""
+    return _pcsaft_mix_flash(params, comp, kij, eab, owner, T, P, z)
 
 
 _POOL = {"add": _lib.POOL_ADD, "sum": _lib.POOL_ADD, "mean": _lib.POOL_MEAN, "max": _lib.POOL_MAX}

@@ -27,6 +27,13 @@ Bubble points of a mixture, the pressure at which the liquid x starts to boil at
 ``mix_bubble_batch`` for every point of every system in one launch, ``mix_vle_pxy`` for the P-x-y diagram of a binary
 (``mix_vle_pxy_diagram_feos``), ``mixture_bubble_pressure`` on device tensors.  Dew pressures are not provided.
 
+Isothermal two-phase flashes, the split of a feed z at (T, P) into a liquid x and a vapour y with the vapour mole fraction
+beta (csrc/gnx_pcsaft_mix_flash.hip): ``mix_tp_flash`` for one point (the reference's ``mix_tp_flash_feos``),
+``mix_tp_flash_batch`` for every point of every system in one launch, ``mix_flash_x1`` for the liquid composition of a
+binary at every measured (T, P) over a list of trial feeds in one launch (pcsaft/kij.py ``_pred_x1_worker``),
+``mixture_tp_flash`` on device tensors.  A feed without a vapour-liquid split at (T, P) reports ``STATUS_SINGLE_PHASE``;
+liquid-liquid splits are not looked for.
+
 Parameter rows are ``[m, sigma (Å), epsilon/k (K), kappa_ab, epsilon_ab/k (K), mu (D), na, nb, mw]``; state rows are
 ``[T (K), P (Pa), phase, tp, value]`` (only T and P are read).  Densities are in mol/m³, pressures in Pa.
 """
@@ -39,9 +46,10 @@ import torch
 
 from . import _lib, ops
 
-STATUS_OK, STATUS_NO_CONVERGENCE, STATUS_SUPERCRITICAL, STATUS_BAD_INPUT = 0, 1, 2, 3
+STATUS_OK, STATUS_NO_CONVERGENCE, STATUS_SUPERCRITICAL, STATUS_BAD_INPUT, STATUS_SINGLE_PHASE = 0, 1, 2, 3, 4
 _REASON = {STATUS_NO_CONVERGENCE: "no root / not converged", STATUS_SUPERCRITICAL: "temperature at or above the "
-           "critical temperature", STATUS_BAD_INPUT: "invalid parameters or state"}
+           "critical temperature", STATUS_BAD_INPUT: "invalid parameters or state",
+           STATUS_SINGLE_PHASE: "single phase: no vapour-liquid split at this temperature, pressure and feed"}
 
 
 def _device() -> torch.device:
@@ -245,12 +253,28 @@ def mixture_bubble_pressure(params: torch.Tensor, comp: torch.Tensor, x: torch.T
     return ops.pcsaft_mix_bubble(params, comp, kij, eab, _owner(owner, T), T, x)
 
 
+def mixture_tp_flash(params: torch.Tensor, comp: torch.Tensor, z: torch.Tensor, T: torch.Tensor, P: torch.Tensor,
+                     owner: Optional[torch.Tensor] = None, kij: Optional[torch.Tensor] = None,
+                     eab: Optional[torch.Tensor] = None
+                     ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Tensor form on device tensors, arguments as ``mixture_density`` with the feed z [n, nc] in place of x -> (beta [n],
+    x [n, nc], y [n, nc], rho_l [n], rho_v [n] mol/m³, status [n] int32): the split of z at (T, P) into the liquid x and the
+    vapour y, beta the vapour mole fraction, z = (1 - beta) x + beta y.  A used slot with z = 0 is dropped (x = y = 0.0), a
+    -1 slot has NaN; where status != 0 (4 = ``STATUS_SINGLE_PHASE``: no vapour-liquid split), beta and the densities are
+    0.0 and the x and y rows are NaN.  Asynchronous, on the current stream."""
+    return ops.pcsaft_mix_flash(params, comp, kij, eab, _owner(owner, T), T, P, z)
+
+
 def _run_mix(kind: str, params: np.ndarray, comp: np.ndarray, kij: Optional[np.ndarray], eab: Optional[np.ndarray],
              owner: np.ndarray, states: np.ndarray) -> Tuple[List[Optional[np.ndarray]], np.ndarray]:
     """states [n, 2 + nc] -> (values, status [n] int32); values is [rho [n]] for kind "density", [rho, lnphi [n, nc],
     None] for "lnphi", [rho, lnphi, lnphi_pure [n, nc]] for "lnphi_pure" and [P [n], y [n, nc], rho_l [n], rho_v [n]]
-    for "bubble", which does not read the P column."""
+    for "bubble", which does not read the P column, and [beta [n], x [n, nc], y [n, nc], rho_l [n], rho_v [n]] for "flash",
+    whose composition columns hold the feed."""
     n, nc = owner.shape[0], comp.shape[1]
+    if kind == "flash":
+        return _run(ops._pcsaft_mix_flash, [params, comp, kij, eab, owner, states[:, 0], states[:, 1], states[:, 2:]], n,
+                    [(n,), (n, nc), (n, nc), (n,), (n,)])
     if kind == "bubble":
         return _run(ops._pcsaft_mix_bubble, [params, comp, kij, eab, owner, states[:, 0], states[:, 2:]], n,
                     [(n,), (n, nc), (n,), (n,)])
@@ -468,3 +492,59 @@ def mix_vle_pxy(parameters: Sequence[Sequence[float]], temperature: float, kij_m
             "density liquid": rho_l[keep].tolist(), "density vapor": rho_v[keep].tolist(),
             "x0": x0[keep].tolist(), "x1": (1.0 - x0)[keep].tolist(),
             "y0": y[keep, 0].tolist(), "y1": y[keep, 1].tolist()}
+
+
+def mix_tp_flash(parameters: Sequence[Sequence[float]], state: Sequence[float], kij_matrix: Optional[Any] = None,
+                 epsilon_ab: Optional[Any] = None) -> dict:
+    """Two-phase flash of the feed ``state = [T (K), P (Pa), z1, z2, ...]`` of the components ``parameters`` (reference
+    ``mix_tp_flash_feos``): a dict with ``beta`` (the vapour mole fraction), ``x``, ``y`` ([k] arrays, liquid and vapour)
+    and ``density liquid``, ``density vapor`` (mol/m³); raises ``RuntimeError`` where the feed does not split into a
+    vapour and a liquid at (T, P) or the solve does not converge."""
+    (beta, x, y, rho_l, rho_v), _ = _mix_point("flash", "flash", parameters, state, kij_matrix, epsilon_ab)
+    k = len(parameters)
+    return {"beta": float(beta[0]), "x": x[0, :k].copy(), "y": y[0, :k].copy(), "density liquid": float(rho_l[0]),
+            "density vapor": float(rho_v[0])}
+
+
+def mix_tp_flash_batch(mixtures: List[List[List[Any]]], states_batch: List[Any], kij: Optional[List[Any]] = None
+                       ) -> List[np.ndarray]:
+    """Flashes of every state of every non-empty table in one launch, arguments as ``mix_rho_batch`` (the composition
+    columns hold the feed): one fp64 array [rows, 1 + 2 nc_i] of rows ``[beta, x1..x_nc, y1..y_nc]`` per non-empty table, a
+    row of NaN where a point has no vapour-liquid split or failed."""
+    def pick(values):
+        row = np.concatenate([values[0][:, None], values[1], values[2]], axis=1)
+        return np.where(np.isnan(values[1][:, :1]), np.nan, row)  # the first slot is always used: NaN there = failed
+
+    parts = _mix_batch("flash", mixtures, states_batch, kij, pick)
+    out = []
+    for i, v in parts:
+        k, nc = len(mixtures[i]), (v.shape[1] - 1) // 2
+        out.append(np.concatenate([v[:, :1 + k], v[:, 1 + nc:1 + nc + k]], axis=1))
+    return out
+
+
+def mix_flash_x1(parameters: Sequence[Sequence[float]], states: Any, feed_x1s: Any, kij_matrix: Optional[Any] = None,
+                 epsilon_ab: Optional[Any] = None) -> np.ndarray:
+    """x_1 of the denser phase of a binary at every row ``[T (K), P (Pa)]`` of ``states`` [n, 2]: all n x F flashes of the
+    trial feeds z_1 = ``feed_x1s`` [F] run in one launch, and each state takes the first feed, in order, that splits
+    (status 0); NaN where none does -> [n] fp64 (the loop of the reference's pcsaft/kij.py ``_pred_x1_worker``, which tries
+    the feeds one by one).  The denser phase is the liquid: rho_l > rho_v wherever the status is 0.  ``ValueError`` for
+    anything but two components."""
+    if len(parameters) != 2:
+        raise ValueError(f"mix_flash_x1 needs a binary mixture, got {len(parameters)} components")
+    st = np.asarray(states, dtype=np.float64)
+    feeds = np.asarray(feed_x1s, dtype=np.float64)
+    if st.ndim != 2 or st.shape[1] != 2:
+        raise ValueError(f"states must be [n, 2] rows of [T, P], got shape {st.shape}")
+    if feeds.ndim != 1 or feeds.size == 0:
+        raise ValueError(f"feed_x1s must be a non-empty 1-d array, got shape {feeds.shape}")
+    params, comp, kij, eab = _pool([parameters], [kij_matrix], [epsilon_ab])
+    n, F = st.shape[0], feeds.size
+    if n == 0:
+        return np.zeros(0, dtype=np.float64)
+    z1 = np.tile(feeds, n)
+    points = np.concatenate([np.repeat(st, F, axis=0), z1[:, None], 1.0 - z1[:, None]], axis=1)
+    (_, x, _, _, _), status = _run_mix("flash", params, comp, kij, eab, np.zeros(n * F, dtype=np.int64), points)
+    ok = (status == STATUS_OK).reshape(n, F)
+    first = np.argmax(ok, axis=1)
+    return np.where(ok.any(axis=1), x[:, 0].reshape(n, F)[np.arange(n), first], np.nan)

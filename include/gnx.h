@@ -492,6 +492,20 @@ int32_t gnx_pcsaft_mix_bubble(gnx_handle* h, const double* params, int64_t B, co
                               const double* mix_kij, const double* mix_eab, int64_t M, int32_t nc, const int64_t* owner,
                               const double* T, const double* x, int64_t n, double* P, double* y, double* rho_l,
                               double* rho_v, int32_t* status);
+/* Isothermal two-phase flash (ref: pcsaft/pcsaft_feos.py mix_tp_flash_feos): at T[i], P[i] (Pa) the split of the feed
+ * z[i, :] (normalised by its sum) into a liquid x[i, :] and a vapour y[i, :], the vapour mole fraction beta[i] in [0, 1]
+ * and the molar densities rho_l[i], rho_v[i] of both phases (either may be NULL).  Equal mu_i^res/kT + ln(rho x_i) of
+ * every component, both phases at P and z = (1 - beta) x + beta y, by successive substitution on ln K with a
+ * Rachford-Rice solve per step, from the bubble entry's ideal-vapour start; the equilibrium equations hold to 1e-10 at
+ * the numbers returned.  A used slot with z = 0 is dropped (x = y = 0.0), a -1 slot has NaN in x and y.  status 4 (this
+ * entry alone): no vapour-liquid split at (T, P, z): one component, every K on one side of 1, or a converged split with
+ * beta outside [0, 1] or with equal phases.  status 3 also covers a non-finite or non-positive P.  A point with
+ * status != 0 has beta = 0.0, NaN in its whole x and y rows and densities 0.0.  Liquid-liquid splits are not looked for.
+ * The launch has no kernel id (GNX_K_NONE). */
+int32_t gnx_pcsaft_mix_flash(gnx_handle* h, const double* params, int64_t B, const int64_t* mix_comp,
+                             const double* mix_kij, const double* mix_eab, int64_t M, int32_t nc, const int64_t* owner,
+                             const double* T, const double* P, const double* z, int64_t n, double* beta, double* x,
+                             double* y, double* rho_l, double* rho_v, int32_t* status);
 
 /* ---- contiguous segment reduce: global pool (ref: train/models.py:218-225, 587-595) ------------------------ */
 enum { GNX_POOL_ADD = 0, GNX_POOL_MEAN = 1, GNX_POOL_MAX = 2 };

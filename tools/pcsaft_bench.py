@@ -12,7 +12,11 @@ With ``--bubble`` it times the bubble-point kernel of csrc/gnx_pcsaft_mix_vle.hi
 tests/pcsaft_mix_vle_ref.py and the first point of each system of the binary fixture, repeated, and that module's oracle
 solve on a sample.  The launch has no kernel id, so the events around the call are the only timing there is.
 
-Usage: python tools/pcsaft_bench.py [--mixture | --bubble] [--sizes 1000,100000,1000000] [--oracle-sample 20] [--out FILE.json]
+With ``--flash`` it times the (T, P) flash kernel of csrc/gnx_pcsaft_mix_flash.hip on the tie-line feeds of
+tests/pcsaft_mix_flash_ref.py (the six named bubble points at beta = 0.3, six fixture points at beta = 0.5), repeated, the
+bubble-point kernel on the liquids of the same tie lines for the ratio, and that module's oracle flash on a sample.
+
+Usage: python tools/pcsaft_bench.py [--mixture | --bubble | --flash] [--sizes 1000,100000,1000000] [--oracle-sample 20] [--out FILE.json]
 """
 import argparse
 import json
@@ -107,17 +111,49 @@ def _bubble(args, dev):
     return res
 
 
+def _flash(args, dev):
+    from tests import pcsaft_mix_flash_ref as F
+    points = F.tie_line_points()
+    params, comp = [], np.full((len(points), 4), -1, dtype=np.int64)
+    z, x = np.zeros((len(points), 4)), np.zeros((len(points), 4))
+    for i, (_, rows, _, _, zi, xi, _, _) in enumerate(points):
+        comp[i, :len(rows)] = np.arange(len(params), len(params) + len(rows))
+        params.extend(np.asarray(rows, dtype=np.float64).tolist())
+        z[i, :len(rows)], x[i, :len(rows)] = zi, xi
+    T, P = np.array([p[2] for p in points]), np.array([p[3] for p in points])
+    step = max(1, len(points) // args.oracle_sample)
+    t0 = time.perf_counter()
+    sols = [F.flash(rows, zi, t, p) for _, rows, t, p, zi, _, _, _ in points[::step]]
+    oracle = (time.perf_counter() - t0) / len(sols)
+    d_params, d_comp = torch.from_numpy(np.array(params)).to(dev), torch.from_numpy(comp).to(dev)
+    res = []
+    for n in [int(s) for s in args.sizes.split(",")]:
+        idx = np.arange(n) % len(points)
+        o, t, pp, zz, xx = (torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+                            for a in (idx.astype(np.int64), T[idx], P[idx], z[idx], x[idx]))
+        k = _kernel_ms(lambda: pcsaft.mixture_tp_flash(d_params, d_comp, zz, t, pp, o))
+        st = pcsaft.mixture_tp_flash(d_params, d_comp, zz, t, pp, o)[5]
+        kb = _kernel_ms(lambda: pcsaft.mixture_bubble_pressure(d_params, d_comp, xx, t, o))
+        rec = dict(points=n, mix_flash_kernel_ms=k, mix_flash_points_per_s=n / k * 1e3,
+                   failed_points=int((st != 0).sum().item()), mix_bubble_same_tie_lines_kernel_ms=kb,
+                   flash_over_bubble=k / kb, oracle_flash_ms_est=oracle * n * 1e3)
+        print(json.dumps(rec), flush=True)
+        res.append(rec)
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sizes", default="1000,100000,1000000")
     ap.add_argument("--oracle-sample", type=int, default=20)
     ap.add_argument("--mixture", action="store_true")
     ap.add_argument("--bubble", action="store_true")
+    ap.add_argument("--flash", action="store_true")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
-    if args.mixture or args.bubble:
+    if args.mixture or args.bubble or args.flash:
         dev = torch.device("cuda", torch.cuda.current_device())
-        res = (_bubble if args.bubble else _mixture)(args, dev)
+        res = (_flash if args.flash else _bubble if args.bubble else _mixture)(args, dev)
         if args.out:
             with open(args.out, "w") as fh:
                 json.dump(dict(device=torch.cuda.get_device_name(dev), oracle_sample=args.oracle_sample, results=res), fh,
