@@ -25,10 +25,16 @@
 // arithmetic (damped substitution where a Newton step leaves (0, 1]), and three further Newton steps carried on the dual
 // type with the converged Jacobian give dX_A/drho and d2X_A/drho2 exactly (implicit differentiation).
 //
-// One lane per state point; a lane loads the component rows of its mixture through owner -> mix_comp -> params.
-// Components with x_i = 0 (unless init<KEEP>) and slots marked -1 are dropped before anything is computed.  Every loop has a fixed trip cap;
-// a point that runs into one reports a status != 0 and the value 0.0.  No atomics, no shared memory: same input, same
-// bits.  The fp64 arrays indexed at run time live in scratch; the solve is latency-bound per point.
+// Plumbing, shared by the four translation units of the mixture entries.  An entry packs its eight leading arguments
+// into a MixSet and gives mix_launch the functor of its point: one kernel template, k_pcsaft_mix<Point>, one lane per
+// state point.  mix_of(set, i) is the one place that goes owner -> mix_comp / mix_kij / mix_eab; everything below the
+// kernel takes the MixRef it returns.  The fields of both structs and the arrays of the point functors carry no
+// __restrict__, on purpose: state, density, bubble and flash kernels run at the parent's time without it; the two
+// fugacity points of gnx_pcsaft_mix_phi.hip keep it with the rest of their old body.
+// Components with x_i = 0 (unless init<KEEP>) and slots marked -1 are dropped before anything is computed.  Every loop
+// has a fixed trip cap; a point that runs into one reports a status != 0 and the value 0.0.  No atomics, no shared
+// memory: same input, same bits.  The fp64 arrays indexed at run time live in scratch; the solve is latency-bound per
+// point.
 #pragma once
 
 #include "gnx_common.hpp"
@@ -43,6 +49,43 @@ namespace {
 constexpr int NC_MAX = 4;            // components per mixture: every array below has this extent
 constexpr int kSiteIters = 100;      // Newton / damped substitution of the site fractions
 constexpr double kSiteTol = 1e-12;   // largest Newton step that ends the site-fraction solve (the dual steps polish it)
+
+// The mixtures of one call, as every entry receives them (include/gnx.h): built once in the entry, passed by value to
+// the kernel.
+struct MixSet {
+  const double* params;  // [B, 9] pool of component rows
+  int64_t B;
+  const int64_t* comp;   // [M, nc] rows of each mixture, -1 = unused slot
+  const double* kij;     // [M, nc, nc] or NULL
+  const double* eab;     // [M, nc, nc] or NULL
+  int64_t M;
+  int nc;
+  const int64_t* owner;  // [n] mixture of each point
+};
+
+// One mixture of the set: comp, kij and eab are its own slices.  comp is NULL where the set has no such mixture.
+struct MixRef {
+  const double* params;
+  int64_t B;
+  const int64_t* comp;
+  const double* kij;
+  const double* eab;
+  int nc;
+};
+
+// the mixture of point i: the one place that checks owner[i] and slices the set's tables
+__device__ __forceinline__ MixRef mix_of(const MixSet& set, int64_t i) {
+  const int64_t o = set.owner[i];
+  const int nc = set.nc;
+  MixRef m{set.params, set.B, nullptr, nullptr, nullptr, nc};
+  if (o >= 0 && o < set.M) {
+    const int64_t sq = o * nc * nc;
+    m.comp = set.comp + o * nc;
+    m.kij = set.kij ? set.kij + sq : nullptr;
+    m.eab = set.eab ? set.eab + sq : nullptr;
+  }
+  return m;
+}
 
 // J y = r for up to NC_MAX unknowns and NR right-hand sides, by elimination with partial pivoting; r is overwritten by y
 template <int NR>
@@ -108,20 +151,19 @@ struct MixT {
   double kT_pa;                           // p [Pa] = p~ [1/angstrom^3] * kT_pa
   double xa[NC_MAX];                      // site fractions X_A of the last solve: the start of the next one
 
-  // comp / x: the nc slots of this point's mixture; kij / eab: its [nc, nc] matrices or NULL, read from the upper triangle.
+  // mr: this point's mixture, its kij / eab read from the upper triangle; xin: the composition of its nc slots.
   // KEEP: a used slot with x = 0 stays in the mixture (infinite dilution) instead of being dropped.
   template <bool KEEP = false>
-  __device__ bool init(const double* __restrict__ params, int64_t B, const int64_t* __restrict__ comp,
-                       const double* __restrict__ kij, const double* __restrict__ eab, int nc,
-                       const double* __restrict__ xin, double T) {
+  __device__ bool init(const MixRef& mr, const double* __restrict__ xin, double T) {
+    const int nc = mr.nc;
     if (!(T > 0.0) || !isfinite(T)) return false;
     double sum = 0.0;
     int used = 0;
     for (int s = 0; s < nc; ++s) {
-      const int64_t c = comp[s];
+      const int64_t c = mr.comp[s];
       if (c == -1) continue;
       const double xs = xin[s];
-      if (c < 0 || c >= B || !(xs >= 0.0) || !isfinite(xs)) return false;
+      if (c < 0 || c >= mr.B || !(xs >= 0.0) || !isfinite(xs)) return false;
       sum += xs;
       ++used;
     }
@@ -131,9 +173,9 @@ struct MixT {
     int slot[NC_MAX];
     n = 0;
     for (int s = 0; s < nc; ++s) {
-      const int64_t c = comp[s];
+      const int64_t c = mr.comp[s];
       if (c == -1 || (!KEEP && !(xin[s] > 0.0))) continue;
-      const double* row = params + c * 9;
+      const double* row = mr.params + c * 9;
       const double mm = row[0], sg = row[1], ep = row[2], ka = row[3], ea = row[4], mu = row[5], a = row[6], b = row[7];
       if (!valid_row(row)) return false;
       const int i = n++;
@@ -174,7 +216,7 @@ struct MixT {
     for (int i = 0; i < n; ++i)
       for (int j = 0; j < n; ++j) {
         const int lo = slot[i] < slot[j] ? slot[i] : slot[j], hi = slot[i] < slot[j] ? slot[j] : slot[i];
-        const double k_ij = (kij && i != j) ? kij[lo * nc + hi] : 0.0;
+        const double k_ij = (mr.kij && i != j) ? mr.kij[lo * nc + hi] : 0.0;
         if (!isfinite(k_ij)) return false;
         const double sij = 0.5 * (sigma[i] + sigma[j]), sij3 = sij * sij * sij;
         const double et = ::sqrt(eps[i] * eps[j]) * (1.0 - k_ij) / T;  // eps_ij / T
@@ -185,8 +227,8 @@ struct MixT {
         delta0[i][j] = 0.0;
         if (kab[i] > 0.0 && kab[j] > 0.0) {
           double e_ab = 0.5 * (eabv[i] + eabv[j]);
-          if (eab && i != j) {
-            const double given = eab[lo * nc + hi];
+          if (mr.eab && i != j) {
+            const double given = mr.eab[lo * nc + hi];
             if (given == given) e_ab = given;  // NaN: the combining rule
           }
           if (!isfinite(e_ab)) return false;
@@ -413,19 +455,46 @@ struct MixT {
 };
 using Mix = MixT<double>;
 
-__device__ __forceinline__ bool load_mix(const double* __restrict__ params, int64_t B,
-                                         const int64_t* __restrict__ mix_comp, const double* __restrict__ mix_kij,
-                                         const double* __restrict__ mix_eab, int64_t M, int nc,
-                                         const int64_t* __restrict__ owner, const double* __restrict__ x, int64_t i,
-                                         double T, Mix& c) {
-  const int64_t o = owner[i];
-  if (o < 0 || o >= M) return false;
-  return c.init(params, B, mix_comp + o * nc, mix_kij ? mix_kij + o * nc * nc : nullptr,
-                mix_eab ? mix_eab + o * nc * nc : nullptr, nc, x + i * nc, T);
+// the mixture of point i folded at (T, row i of x); false: no such mixture, or bad input as init judges it
+__device__ __forceinline__ bool load_mix(const MixRef& m, const double* __restrict__ x, int64_t i, double T, Mix& c) {
+  return m.comp && c.init(m, x + i * m.nc, T);
+}
+
+// m with the slots that are absent (x <= 0) marked unused: cm receives the slots, the result reads them from there
+__device__ __forceinline__ MixRef mix_present(const MixRef& m, const double* __restrict__ x, int64_t* cm) {
+  for (int s = 0; s < NC_MAX; ++s) cm[s] = (s < m.nc && m.comp[s] != -1 && x[s] > 0.0) ? m.comp[s] : -1;
+  MixRef r = m;
+  r.comp = cm;
+  return r;
+}
+
+// row i of an [n, nc] output: v in the used slots of m, NaN in its -1 slots and in the whole row of a point that failed
+__device__ __forceinline__ void store_row(double* __restrict__ out, int64_t i, const MixRef& m, bool good,
+                                          const double* v) {
+  for (int s = 0; s < m.nc; ++s) out[i * m.nc + s] = (good && m.comp[s] != -1) ? v[s] : NAN;
+}
+
+// One lane per point: Point holds the arrays of one entry and computes point i of the set in operator()(set, i).
+template <typename Point>
+__global__ void __launch_bounds__(256) k_pcsaft_mix(MixSet set, int64_t n, Point point) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) point(set, i);
+}
+
+// The host path of every mixture entry: argument checks, profiling scope under kernel id `kid` (GNX_K_NONE: none) and
+// the launch.  arrays: the entry's own required arrays are all there.
+template <typename Point>
+int32_t mix_launch(gnx_handle* h, const char* name, int kid, double bytes_per_point, const MixSet& set, int64_t n,
+                   bool arrays, const Point& point) {
+  GNX_CHECK_ARG(h && n >= 0 && set.B >= 0 && set.M >= 0 && set.nc >= 1 && set.nc <= NC_MAX,
+                "%s: bad argument (1 <= nc <= 4)", name);
+  if (n == 0) return GNX_OK;
+  GNX_CHECK_ARG(arrays && set.owner && (set.params || set.B == 0) && (set.comp || set.M == 0), "%s: NULL argument",
+                name);
+  gnx_prof_scope prof(h, kid, bytes_per_point * n, 0.0, 0.0, true);
+  GNX_LAUNCH_TIMED(prof, k_pcsaft_mix<Point>, dim3((unsigned)gnx_cdiv(n, 256)), dim3(256), 0, h->stream, set, n, point);
+  GNX_LAUNCH_CHECK();
+  return GNX_OK;
 }
 
 }  // namespace
-
-#define GNX_MIX_CHECK(name)                                                                                       \
-  GNX_CHECK_ARG(h && n >= 0 && B >= 0 && M >= 0 && nc >= 1 && nc <= NC_MAX, name ": bad argument (1 <= nc <= 4)"); \
-  if (n == 0) return GNX_OK;

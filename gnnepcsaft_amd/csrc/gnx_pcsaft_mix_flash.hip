@@ -84,141 +84,117 @@ __device__ bool root_near(Mix& c, double pt, double e0, double& out) {
 }
 
 // flash of point i at (T, P, z)
-__device__ void mix_flash_point(const double* __restrict__ params, int64_t B, const int64_t* __restrict__ mix_comp,
-                                const double* __restrict__ mix_kij, const double* __restrict__ mix_eab, int64_t M, int nc,
-                                const int64_t* __restrict__ owner, const double* __restrict__ T,
-                                const double* __restrict__ P, const double* __restrict__ z, int64_t i,
-                                double* __restrict__ beta, double* __restrict__ x, double* __restrict__ y,
-                                double* __restrict__ rho_l, double* __restrict__ rho_v, int32_t* __restrict__ status) {
-  Mix cl, cv;
-  const double t = T[i], p = P[i];
-  int32_t st = ST_BAD_INPUT;
-  double bt = 0.0, rl = 0.0, rv = 0.0, xv[NC_MAX], yv[NC_MAX];
-  int64_t cm[NC_MAX];  // the mixture's slots with those that are absent (z = 0) marked unused
-  for (int s = 0; s < NC_MAX; ++s) {
-    xv[s] = yv[s] = 0.0;
-    cm[s] = -1;
-  }
-  if (isfinite(p) && p > 0.0 && load_mix(params, B, mix_comp, mix_kij, mix_eab, M, nc, owner, z, i, t, cl)) {
-    st = ST_NO_CONV;
-    const int64_t o = owner[i];
-    const double* kij = mix_kij ? mix_kij + o * nc * nc : nullptr;
-    const double* eab = mix_eab ? mix_eab + o * nc * nc : nullptr;
-    const double* zin = z + i * nc;
-    const int n = cl.n;
-    const double pt = p / cl.kT_pa;
-    double zc[NC_MAX], lnk[NC_MAX], lnkp[NC_MAX], kv[NC_MAX], lnf[2][NC_MAX], sum = 0.0;
-    for (int s = 0; s < nc; ++s) {
-      const int64_t c = mix_comp[o * nc + s];
-      cm[s] = (c != -1 && zin[s] > 0.0) ? c : -1;
-      if (cm[s] != -1) sum += zin[s];
-    }
-    for (int s = 0, k = 0; s < nc; ++s)
-      if (cm[s] != -1) zc[k++] = zin[s] / sum;
-    bool ok = true, conv = false, single = n == 1;  // one component has no split away from its vapour pressure
-    if (!single) {
-      // the start: the liquid z at zero pressure under an ideal vapour; without one, the highest root of z at P
-      double el;
-      ok = density_root(cl, 0.0, el) == ST_OK && el >= kEtaMax / kScanDensity;
-      if (!ok) ok = density_root(cl, pt, el) == ST_OK;
-      ok = ok && mix_lnf_at(params, B, cm, kij, eab, nc, zin, t, number_density(molar_density(el, cl.c3)), cl, lnf[0]);
-      for (int k = 0; ok && k < n; ++k) {
-        lnk[k] = lnkp[k] = lnf[0][k] - ::log(zc[k] * pt);
-        ok = isfinite(lnk[k]);
-      }
-    }
-    int damp = 0;
-    double el0 = 0.0, ev0 = 0.0, step = 1.0;  // the roots and the step in ln K of the last full step
-    bool scans_only = false;
-    for (int it = 0; ok && !single && it < kVleMixIters; ++it) {
-      for (int k = 0; k < n; ++k) kv[k] = ::exp(lnk[k]);
-      const int sp = flash_split(zc, kv, n, bt);
-      single = sp == RR_EMPTY;
-      ok = sp == RR_OK;
-      if (!ok) break;
+struct MixFlashPoint {
+  const double *T, *P, *z;
+  double *beta, *x, *y, *rho_l, *rho_v;
+  int32_t* status;
+  __device__ void operator()(const MixSet& set, int64_t i) const {
+    Mix cl, cv;
+    const MixRef m = mix_of(set, i);
+    const double t = T[i], p = P[i];
+    int32_t st = ST_BAD_INPUT;
+    double bt = 0.0, rl = 0.0, rv = 0.0, xv[NC_MAX], yv[NC_MAX];
+    for (int s = 0; s < NC_MAX; ++s) xv[s] = yv[s] = 0.0;
+    if (isfinite(p) && p > 0.0 && load_mix(m, z, i, t, cl)) {
+      st = ST_NO_CONV;
+      const double* zin = z + i * m.nc;
+      int64_t cm[NC_MAX];
+      const MixRef mp = mix_present(m, zin, cm);  // both phases have the feed's components and no others
+      const int nc = m.nc;
+      const int n = cl.n;
+      const double pt = p / cl.kT_pa;
+      double zc[NC_MAX], lnk[NC_MAX], lnkp[NC_MAX], kv[NC_MAX], lnf[2][NC_MAX], sum = 0.0;
+      for (int s = 0; s < nc; ++s)
+        if (cm[s] != -1) sum += zin[s];
       for (int s = 0, k = 0; s < nc; ++s)
-        if (cm[s] != -1) {
-          xv[s] = zc[k] / (1.0 + bt * (kv[k] - 1.0));
-          yv[s] = kv[k] * xv[s];
-          ok = ok && xv[s] > 0.0 && yv[s] > 0.0 && isfinite(xv[s]) && isfinite(yv[s]);
-          ++k;
+        if (cm[s] != -1) zc[k++] = zin[s] / sum;
+      bool ok = true, conv = false, single = n == 1;  // one component has no split away from its vapour pressure
+      if (!single) {
+        // the start: the liquid z at zero pressure under an ideal vapour; without one, the highest root of z at P
+        double el;
+        ok = density_root(cl, 0.0, el) == ST_OK && el >= kEtaMax / kScanDensity;
+        if (!ok) ok = density_root(cl, pt, el) == ST_OK;
+        ok = ok && mix_lnf_at(mp, zin, t, number_density(molar_density(el, cl.c3)), cl, lnf[0]);
+        for (int k = 0; ok && k < n; ++k) {
+          lnk[k] = lnkp[k] = lnf[0][k] - ::log(zc[k] * pt);
+          ok = isfinite(lnk[k]);
         }
-      ok = ok && cl.init(params, B, cm, kij, eab, nc, xv, t) && cl.n == n && cv.init(params, B, cm, kij, eab, nc, yv, t) &&
-           cv.n == n;
-      if (!ok) break;
-      double el, ev = 0.0;
-      const bool near = !scans_only && el0 > 0.0 && step < kFlashNearRes && root_near(cl, pt, el0, el) &&
-                        root_near(cv, pt, ev0, ev);
-      if (!near) {
-        const bool liquid = density_root(cl, pt, el) == ST_OK;
-        const int vr = liquid ? vapour_root(cv, pt, ev) : VR_NONE;
-        if ((!liquid || vr == VR_NONE) && ++damp <= kVleMixDamp) {
-          for (int k = 0; k < n; ++k) lnk[k] = 0.5 * (lnk[k] + lnkp[k]);  // no root of a phase: half the step back
-          continue;
-        }
-        ok = liquid && vr == VR_OK;
+      }
+      int damp = 0;
+      double el0 = 0.0, ev0 = 0.0, step = 1.0;  // the roots and the step in ln K of the last full step
+      bool scans_only = false;
+      for (int it = 0; ok && !single && it < kVleMixIters; ++it) {
+        for (int k = 0; k < n; ++k) kv[k] = ::exp(lnk[k]);
+        const int sp = flash_split(zc, kv, n, bt);
+        single = sp == RR_EMPTY;
+        ok = sp == RR_OK;
         if (!ok) break;
-      }
-      damp = 0;
-      // at the densities reported, converted as the state forms convert them
-      rl = molar_density(el, cl.c3);
-      rv = molar_density(ev, cv.c3);
-      for (int ph = 0; ok && ph < 2; ++ph)
-        ok = mix_lnf_at(params, B, cm, kij, eab, nc, ph ? yv : xv, t, number_density(ph ? rv : rl), ph ? cv : cl, lnf[ph]);
-      if (!ok) break;
-      double res = 0.0;
-      for (int k = 0; k < n; ++k) res = ::fmax(res, ::fabs(lnf[0][k] - lnf[1][k]));
-      for (int k = 0; k < n; ++k) ok = ok && isfinite(lnf[0][k] - lnf[1][k]);
-      conv = ok && res < kVleMixTol;
-      if (conv && near) {
-        // the liquid root is the highest and the vapour root the lowest only if the scans find them too
-        double es, vs;
-        conv = density_root(cl, pt, es) == ST_OK && vapour_root(cv, pt, vs) == VR_OK &&
-               ::fabs(es - el) <= kFlashSame * el && ::fabs(vs - ev) <= kFlashSame * ev;
-        if (!conv) {
-          scans_only = true;  // this step again, ln K as it is, from the scans
-          continue;
+        for (int s = 0, k = 0; s < nc; ++s)
+          if (cm[s] != -1) {
+            xv[s] = zc[k] / (1.0 + bt * (kv[k] - 1.0));
+            yv[s] = kv[k] * xv[s];
+            ok = ok && xv[s] > 0.0 && yv[s] > 0.0 && isfinite(xv[s]) && isfinite(yv[s]);
+            ++k;
+          }
+        ok = ok && cl.init(mp, xv, t) && cl.n == n && cv.init(mp, yv, t) && cv.n == n;
+        if (!ok) break;
+        double el, ev = 0.0;
+        const bool near = !scans_only && el0 > 0.0 && step < kFlashNearRes && root_near(cl, pt, el0, el) &&
+                          root_near(cv, pt, ev0, ev);
+        if (!near) {
+          const bool liquid = density_root(cl, pt, el) == ST_OK;
+          const int vr = liquid ? vapour_root(cv, pt, ev) : VR_NONE;
+          if ((!liquid || vr == VR_NONE) && ++damp <= kVleMixDamp) {
+            for (int k = 0; k < n; ++k) lnk[k] = 0.5 * (lnk[k] + lnkp[k]);  // no root of a phase: half the step back
+            continue;
+          }
+          ok = liquid && vr == VR_OK;
+          if (!ok) break;
+        }
+        damp = 0;
+        // at the densities reported, converted as the state forms convert them
+        rl = molar_density(el, cl.c3);
+        rv = molar_density(ev, cv.c3);
+        for (int ph = 0; ok && ph < 2; ++ph)
+          ok = mix_lnf_at(mp, ph ? yv : xv, t, number_density(ph ? rv : rl), ph ? cv : cl, lnf[ph]);
+        if (!ok) break;
+        double res = 0.0;
+        for (int k = 0; k < n; ++k) res = ::fmax(res, ::fabs(lnf[0][k] - lnf[1][k]));
+        for (int k = 0; k < n; ++k) ok = ok && isfinite(lnf[0][k] - lnf[1][k]);
+        conv = ok && res < kVleMixTol;
+        if (conv && near) {
+          // the liquid root is the highest and the vapour root the lowest only if the scans find them too
+          double es, vs;
+          conv = density_root(cl, pt, es) == ST_OK && vapour_root(cv, pt, vs) == VR_OK &&
+                 ::fabs(es - el) <= kFlashSame * el && ::fabs(vs - ev) <= kFlashSame * ev;
+          if (!conv) {
+            scans_only = true;  // this step again, ln K as it is, from the scans
+            continue;
+          }
+        }
+        if (conv || !ok) break;
+        el0 = el;
+        ev0 = ev;
+        step = res;
+        for (int k = 0; k < n; ++k) {
+          lnkp[k] = lnk[k];
+          lnk[k] += lnf[0][k] - lnf[1][k];
         }
       }
-      if (conv || !ok) break;
-      el0 = el;
-      ev0 = ev;
-      step = res;
-      for (int k = 0; k < n; ++k) {
-        lnkp[k] = lnk[k];
-        lnk[k] += lnf[0][k] - lnf[1][k];
-      }
+      if (single)
+        st = ST_SINGLE_PHASE;
+      else if (ok && conv)  // equal densities: the trivial solution; beta outside [0, 1]: the feed is off the tie line
+        st = (rv > 0.0 && rl - rv > kVleTrivial * rl && bt >= 0.0 && bt <= 1.0) ? ST_OK : ST_SINGLE_PHASE;
     }
-    if (single)
-      st = ST_SINGLE_PHASE;
-    else if (ok && conv)  // equal densities: the trivial solution; beta outside [0, 1]: the feed lies off the tie line
-      st = (rv > 0.0 && rl - rv > kVleTrivial * rl && bt >= 0.0 && bt <= 1.0) ? ST_OK : ST_SINGLE_PHASE;
+    const bool good = st == ST_OK;
+    beta[i] = good ? bt : 0.0;
+    if (rho_l) rho_l[i] = good ? rl : 0.0;
+    if (rho_v) rho_v[i] = good ? rv : 0.0;
+    store_row(x, i, m, good, xv);
+    store_row(y, i, m, good, yv);
+    status[i] = st;
   }
-  const bool good = st == ST_OK;
-  beta[i] = good ? bt : 0.0;
-  if (rho_l) rho_l[i] = good ? rl : 0.0;
-  if (rho_v) rho_v[i] = good ? rv : 0.0;
-  const int64_t* comp = good ? mix_comp + owner[i] * nc : nullptr;
-  for (int s = 0; s < nc; ++s) {
-    x[i * nc + s] = (comp && comp[s] != -1) ? xv[s] : NAN;
-    y[i * nc + s] = (comp && comp[s] != -1) ? yv[s] : NAN;
-  }
-  status[i] = st;
-}
-
-__global__ void __launch_bounds__(256) k_pcsaft_mix_flash(const double* __restrict__ params, int64_t B,
-                                                          const int64_t* __restrict__ mix_comp,
-                                                          const double* __restrict__ mix_kij,
-                                                          const double* __restrict__ mix_eab, int64_t M, int nc,
-                                                          const int64_t* __restrict__ owner, const double* __restrict__ T,
-                                                          const double* __restrict__ P, const double* __restrict__ z,
-                                                          int64_t n, double* __restrict__ beta, double* __restrict__ x,
-                                                          double* __restrict__ y, double* __restrict__ rho_l,
-                                                          double* __restrict__ rho_v, int32_t* __restrict__ status) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n)
-    mix_flash_point(params, B, mix_comp, mix_kij, mix_eab, M, nc, owner, T, P, z, i, beta, x, y, rho_l, rho_v, status);
-}
+};
 
 }  // namespace
 
@@ -227,13 +203,8 @@ extern "C" int32_t gnx_pcsaft_mix_flash(gnx_handle* h, const double* params, int
                                         const int64_t* owner, const double* T, const double* P, const double* z, int64_t n,
                                         double* beta, double* x, double* y, double* rho_l, double* rho_v,
                                         int32_t* status) {
-  GNX_MIX_CHECK("gnx_pcsaft_mix_flash")
-  GNX_CHECK_ARG(owner && T && P && z && beta && x && y && status && (params || B == 0) && (mix_comp || M == 0),
-                "gnx_pcsaft_mix_flash: NULL argument");
   // no kernel id of its own: under GNX_K_NONE the scope stays off and the launch is a plain one
-  gnx_prof_scope prof(h, GNX_K_NONE, (52.0 + 24.0 * nc) * n, 0.0, 0.0, true);
-  GNX_LAUNCH_TIMED(prof, k_pcsaft_mix_flash, dim3((unsigned)gnx_cdiv(n, 256)), dim3(256), 0, h->stream, params, B,
-                   mix_comp, mix_kij, mix_eab, M, (int)nc, owner, T, P, z, n, beta, x, y, rho_l, rho_v, status);
-  GNX_LAUNCH_CHECK();
-  return GNX_OK;
+  return mix_launch(h, "gnx_pcsaft_mix_flash", GNX_K_NONE, 52.0 + 24.0 * nc,
+                    MixSet{params, B, mix_comp, mix_kij, mix_eab, M, (int)nc, owner}, n,
+                    T && P && z && beta && x && y && status, MixFlashPoint{T, P, z, beta, x, y, rho_l, rho_v, status});
 }

@@ -22,112 +22,91 @@
 namespace {
 
 // bubble point of point i at (T, x)
-__device__ void mix_bubble_point(const double* __restrict__ params, int64_t B, const int64_t* __restrict__ mix_comp,
-                                 const double* __restrict__ mix_kij, const double* __restrict__ mix_eab, int64_t M, int nc,
-                                 const int64_t* __restrict__ owner, const double* __restrict__ T,
-                                 const double* __restrict__ x, int64_t i, double* __restrict__ P, double* __restrict__ y,
-                                 double* __restrict__ rho_l, double* __restrict__ rho_v, int32_t* __restrict__ status) {
-  Mix cl, cv;
-  const double t = T[i];
-  int32_t st = ST_BAD_INPUT;
-  double pt = 0.0, rl = 0.0, rv = 0.0, yv[NC_MAX];
-  int64_t cm[NC_MAX];  // the mixture's slots with those that are absent (x = 0) marked unused
-  for (int s = 0; s < NC_MAX; ++s) {
-    yv[s] = 0.0;
-    cm[s] = -1;
-  }
-  if (load_mix(params, B, mix_comp, mix_kij, mix_eab, M, nc, owner, x, i, t, cl)) {
-    st = ST_NO_CONV;
-    const int64_t o = owner[i];
-    const double* kij = mix_kij ? mix_kij + o * nc * nc : nullptr;
-    const double* eab = mix_eab ? mix_eab + o * nc * nc : nullptr;
-    const double* xin = x + i * nc;
-    for (int s = 0; s < nc; ++s) {
-      const int64_t c = mix_comp[o * nc + s];
-      cm[s] = (c != -1 && xin[s] > 0.0) ? c : -1;
-    }
-    const int n = cl.n;
-    double pprev = 0.0, lnf[2][NC_MAX];
-    int damp = 0;
-    bool ok = true, conv = false;
-    // it = -1 is the start: the liquid at zero pressure under an ideal vapour
-    for (int it = -1; ok && !conv && it < kVleMixIters; ++it) {
-      const bool start = it < 0;
-      double el, ev = 0.0;
-      ok = density_root(cl, start ? 0.0 : pt, el) == ST_OK;
-      // without a liquid at zero pressure the scan runs out at its lowest step and the root is the dilute gas: the point
-      // is too close to the mixture's critical region for this method
-      if (ok && start) ok = el >= kEtaMax / kScanDensity;
-      if (!ok) break;
-      if (!start) {
-        ok = cv.init(params, B, cm, kij, eab, nc, yv, t) && cv.n == n;
+struct MixBubblePoint {
+  const double *T, *x;
+  double *P, *y, *rho_l, *rho_v;
+  int32_t* status;
+  __device__ void operator()(const MixSet& set, int64_t i) const {
+    Mix cl, cv;
+    const MixRef m = mix_of(set, i);
+    const double t = T[i];
+    int32_t st = ST_BAD_INPUT;
+    double pt = 0.0, rl = 0.0, rv = 0.0, yv[NC_MAX];
+    for (int s = 0; s < NC_MAX; ++s) yv[s] = 0.0;
+    if (load_mix(m, x, i, t, cl)) {
+      st = ST_NO_CONV;
+      const double* xin = x + i * m.nc;
+      int64_t cm[NC_MAX];
+      const MixRef mp = mix_present(m, xin, cm);  // the vapour has the liquid's components and no others
+      const int nc = m.nc;
+      const int n = cl.n;
+      double pprev = 0.0, lnf[2][NC_MAX];
+      int damp = 0;
+      bool ok = true, conv = false;
+      // it = -1 is the start: the liquid at zero pressure under an ideal vapour
+      for (int it = -1; ok && !conv && it < kVleMixIters; ++it) {
+        const bool start = it < 0;
+        double el, ev = 0.0;
+        ok = density_root(cl, start ? 0.0 : pt, el) == ST_OK;
+        // without a liquid at zero pressure the scan runs out at its lowest step and the root is the dilute gas: the
+        // point is too close to the mixture's critical region for this method
+        if (ok && start) ok = el >= kEtaMax / kScanDensity;
         if (!ok) break;
-        const int vr = vapour_root(cv, pt, ev);
-        if (vr == VR_NONE && ++damp <= kVleMixDamp) {
-          pt = 0.5 * (pt + pprev);  // no vapour of y at this pressure: half the step back
-          continue;
+        if (!start) {
+          ok = cv.init(mp, yv, t) && cv.n == n;
+          if (!ok) break;
+          const int vr = vapour_root(cv, pt, ev);
+          if (vr == VR_NONE && ++damp <= kVleMixDamp) {
+            pt = 0.5 * (pt + pprev);  // no vapour of y at this pressure: half the step back
+            continue;
+          }
+          ok = vr == VR_OK;
+          if (!ok) break;
+          damp = 0;
         }
-        ok = vr == VR_OK;
+        // at the densities reported, converted as the state forms convert them
+        rl = molar_density(el, cl.c3);
+        rv = start ? 0.0 : molar_density(ev, cv.c3);
+        for (int ph = 0; ok && ph < (start ? 1 : 2); ++ph)
+          ok = mix_lnf_at(mp, ph ? yv : xin, t, number_density(ph ? rv : rl), ph ? cv : cl, lnf[ph]);
         if (!ok) break;
-        damp = 0;
-      }
-      // at the densities reported, converted as the state forms convert them
-      rl = molar_density(el, cl.c3);
-      rv = start ? 0.0 : molar_density(ev, cv.c3);
-      for (int ph = 0; ok && ph < (start ? 1 : 2); ++ph)
-        ok = mix_lnf_at(params, B, cm, kij, eab, nc, ph ? yv : xin, t, number_density(ph ? rv : rl), ph ? cv : cl,
-                        lnf[ph]);
-      if (!ok) break;
-      double xk[NC_MAX], s = 0.0;  // x_i K_i = y_i f_i^L / f_i^V; at the start f_i^L itself
-      for (int q = 0, k = 0; q < nc; ++q)
-        if (cm[q] != -1) {
-          xk[k] = start ? ::exp(lnf[0][k]) : yv[q] * ::exp(lnf[0][k] - lnf[1][k]);
-          s += xk[k++];
+        double xk[NC_MAX], s = 0.0;  // x_i K_i = y_i f_i^L / f_i^V; at the start f_i^L itself
+        for (int q = 0, k = 0; q < nc; ++q)
+          if (cm[q] != -1) {
+            xk[k] = start ? ::exp(lnf[0][k]) : yv[q] * ::exp(lnf[0][k] - lnf[1][k]);
+            s += xk[k++];
+          }
+        ok = s > 0.0 && isfinite(s);
+        if (!ok) break;
+        if (!start) {
+          const double ls = ::log(s);
+          double res = ::fabs(ls);
+          for (int k = 0; k < n; ++k) res = ::fmax(res, ::fabs(lnf[0][k] - lnf[1][k] - ls));
+          ok = res == res;
+          conv = res < kVleMixTol;
+          if (conv || !ok) break;
         }
-      ok = s > 0.0 && isfinite(s);
-      if (!ok) break;
-      if (!start) {
-        const double ls = ::log(s);
-        double res = ::fabs(ls);
-        for (int k = 0; k < n; ++k) res = ::fmax(res, ::fabs(lnf[0][k] - lnf[1][k] - ls));
-        ok = res == res;
-        conv = res < kVleMixTol;
-        if (conv || !ok) break;
+        int k = 0;
+        for (int q = 0; q < nc; ++q)
+          if (cm[q] != -1) {
+            yv[q] = xk[k++] / s;
+            ok = ok && yv[q] > 0.0;
+          }
+        pprev = start ? 0.0 : pt;
+        pt = start ? s : pt * s;
+        ok = ok && pt > 0.0 && isfinite(pt);
       }
-      int k = 0;
-      for (int q = 0; q < nc; ++q)
-        if (cm[q] != -1) {
-          yv[q] = xk[k++] / s;
-          ok = ok && yv[q] > 0.0;
-        }
-      pprev = start ? 0.0 : pt;
-      pt = start ? s : pt * s;
-      ok = ok && pt > 0.0 && isfinite(pt);
+      // equal densities: the trivial solution, both phases the same fluid
+      if (ok && conv && rv > 0.0 && rl - rv > kVleTrivial * rl) st = ST_OK;
     }
-    // equal densities: the trivial solution, both phases the same fluid
-    if (ok && conv && rv > 0.0 && rl - rv > kVleTrivial * rl) st = ST_OK;
+    const bool good = st == ST_OK;
+    P[i] = good ? pt * cl.kT_pa : 0.0;
+    if (rho_l) rho_l[i] = good ? rl : 0.0;
+    if (rho_v) rho_v[i] = good ? rv : 0.0;
+    store_row(y, i, m, good, yv);
+    status[i] = st;
   }
-  const bool good = st == ST_OK;
-  P[i] = good ? pt * cl.kT_pa : 0.0;
-  if (rho_l) rho_l[i] = good ? rl : 0.0;
-  if (rho_v) rho_v[i] = good ? rv : 0.0;
-  const int64_t* comp = good ? mix_comp + owner[i] * nc : nullptr;
-  for (int s = 0; s < nc; ++s) y[i * nc + s] = (comp && comp[s] != -1) ? yv[s] : NAN;
-  status[i] = st;
-}
-
-__global__ void __launch_bounds__(256) k_pcsaft_mix_bubble(const double* __restrict__ params, int64_t B,
-                                                           const int64_t* __restrict__ mix_comp,
-                                                           const double* __restrict__ mix_kij,
-                                                           const double* __restrict__ mix_eab, int64_t M, int nc,
-                                                           const int64_t* __restrict__ owner, const double* __restrict__ T,
-                                                           const double* __restrict__ x, int64_t n,
-                                                           double* __restrict__ P, double* __restrict__ y,
-                                                           double* __restrict__ rho_l, double* __restrict__ rho_v,
-                                                           int32_t* __restrict__ status) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) mix_bubble_point(params, B, mix_comp, mix_kij, mix_eab, M, nc, owner, T, x, i, P, y, rho_l, rho_v, status);
-}
+};
 
 }  // namespace
 
@@ -135,13 +114,8 @@ extern "C" int32_t gnx_pcsaft_mix_bubble(gnx_handle* h, const double* params, in
                                          const double* mix_kij, const double* mix_eab, int64_t M, int32_t nc,
                                          const int64_t* owner, const double* T, const double* x, int64_t n, double* P,
                                          double* y, double* rho_l, double* rho_v, int32_t* status) {
-  GNX_MIX_CHECK("gnx_pcsaft_mix_bubble")
-  GNX_CHECK_ARG(owner && T && x && P && y && status && (params || B == 0) && (mix_comp || M == 0),
-                "gnx_pcsaft_mix_bubble: NULL argument");
   // no kernel id of its own: under GNX_K_NONE the scope stays off and the launch is a plain one
-  gnx_prof_scope prof(h, GNX_K_NONE, (44.0 + 16.0 * nc) * n, 0.0, 0.0, true);
-  GNX_LAUNCH_TIMED(prof, k_pcsaft_mix_bubble, dim3((unsigned)gnx_cdiv(n, 256)), dim3(256), 0, h->stream, params, B,
-                   mix_comp, mix_kij, mix_eab, M, (int)nc, owner, T, x, n, P, y, rho_l, rho_v, status);
-  GNX_LAUNCH_CHECK();
-  return GNX_OK;
+  return mix_launch(h, "gnx_pcsaft_mix_bubble", GNX_K_NONE, 44.0 + 16.0 * nc,
+                    MixSet{params, B, mix_comp, mix_kij, mix_eab, M, (int)nc, owner}, n, T && x && P && y && status,
+                    MixBubblePoint{T, x, P, y, rho_l, rho_v, status});
 }

@@ -47,33 +47,34 @@ __device__ int vapour_root(Mix& c, double pt, double& out) {
 }
 
 // ln f_i = mu_i^res/kT + ln(rn x_i) of the components present, in their compact order, at (T, number density rn, x).  c
-// is the mixture in real arithmetic, initialised from the same arguments; every used slot must have x > 0.  The sibling
-// of gnx_pcsaft_mix_phi.hip's mix_lnphi_at without the ln Z:
+// is mixture m in real arithmetic, initialised from the same arguments; every used slot of m must have x > 0.  The
+// sibling of gnx_pcsaft_mix_phi.hip's mix_lnphi_at without the ln Z:
 //   mu_i^res/kT = a + (Z - 1) + a_xi - sum_j x_j a_xj,  a_xi = da/dx_i at fixed T, rho, the x independent
-__device__ bool mix_lnf_at(const double* __restrict__ params, int64_t B, const int64_t* comp,
-                           const double* __restrict__ kij, const double* __restrict__ eab, int nc, const double* xin,
-                           double T, double rn, Mix& c, double* lnf) {
+// The two are the same up to their last statements.  Sharing that part is deferred, not done: with the common part in
+// one function (results through a struct, through references) the bubble kernel ran 1.0 % and the fugacity state kernel
+// 1.9 % slower (profiles/pcsaft_mix_set_ab.json).  A further entry calls one of the two; it does not copy them again.
+__device__ bool mix_lnf_at(const MixRef& m, const double* xin, double T, double rn, Mix& c, double* lnf) {
   if (!(rn > 0.0) || !(rn * c.c3 < 1.0)) return false;
   const Mix::Eval e = c.eval_rho(rn);  // Z from the second-order dual in rho; leaves the converged X_A in c.xa
   if (!e.ok || !isfinite(e.a) || !isfinite(e.z)) return false;
   MixT<GX> g;
-  if (!g.init(params, B, comp, kij, eab, nc, xin, T)) return false;
+  if (!g.init(m, xin, T)) return false;
   GX xaG[NC_MAX];
   for (int i = 0; i < NC_MAX; ++i) xaG[i] = GX(1.0);
   if (c.assoc && !mix_sites_grad(c, g, rn, xaG)) return false;
   const GX a = g.a_res(GX(rn), xaG);
   double sum = 0.0;
-  for (int s = 0; s < nc; ++s)
-    if (comp[s] != -1) sum += xin[s];
+  for (int s = 0; s < m.nc; ++s)
+    if (m.comp[s] != -1) sum += xin[s];
   double xs = 0.0;
   int k = 0;
-  for (int s = 0; s < nc; ++s)
-    if (comp[s] != -1) xs += xin[s] / sum * a.g[k++];
+  for (int s = 0; s < m.nc; ++s)
+    if (m.comp[s] != -1) xs += xin[s] / sum * a.g[k++];
   const double base = a.v + (e.z - 1.0) - xs;
   k = 0;
   bool fin = true;
-  for (int s = 0; s < nc; ++s)
-    if (comp[s] != -1) {
+  for (int s = 0; s < m.nc; ++s)
+    if (m.comp[s] != -1) {
       lnf[k] = base + a.g[k] + ::log(rn * (xin[s] / sum));
       fin = fin && isfinite(lnf[k]);
       ++k;
