@@ -8,7 +8,7 @@
 
 #define BN_ROWS_PER_BLOCK 256
 
-// workspace layout (floats): [2*H] alpha/beta' | [nchunk * 2 * H] partials
+// workspace layout (floats): [4*H] forward: alpha, beta'; backward: k0, k1, k2, beta' | [nchunk * 2 * H] partials
 extern "C" size_t gnx_batchnorm_workspace_bytes(int64_t M, int32_t H) {
   if (M < 0) M = 0;
   size_t chunks = (size_t)gnx_cdiv(M > 0 ? M : 1, BN_ROWS_PER_BLOCK);
@@ -98,11 +98,32 @@ __global__ void __launch_bounds__(256) k_bn_partial_v4(const float* __restrict__
   }
 }
 
+// The forward's per-element expression, the ONE spelling of it: k_bn_apply writes max(bn_affine(x, a, b'), 0) and the
+// XMASK backward kernels recompute bn_affine(x, a, b') > 0 instead of reading y back.  The library is built with
+// -ffp-contract=off, so this is a multiply and an add wherever it is inlined and the predicate equals y > 0 bit for bit
+// (NaN and +-0 give false on both sides).
+__device__ __forceinline__ float bn_affine(float x, float a, float b) { return x * a + b; }
+
+// a = rstd * gamma, b' = beta - mean * a of column c, exactly as k_bn_finalize forms them (NULL gamma / beta: 1 / 0)
+__device__ __forceinline__ void bn_col_ab(const float* __restrict__ gamma, const float* __restrict__ beta,
+                                          const float* __restrict__ mean, const float* __restrict__ rstd, int c, float& a,
+                                          float& b) {
+  a = rstd[c] * (gamma ? gamma[c] : 1.f);
+  b = (beta ? beta[c] : 0.f) - mean[c] * a;
+}
+
+// XMASK = false: the ReLU mask is y > 0 (gnx_batchnorm_bwd; two rows = six loads in flight).
+// XMASK = true:  the mask is recomputed from x (gnx_batchnorm_bwd_x; y is not read; four rows = eight loads in flight).
+// Either way a thread adds its rows in the same order, so the partial sums are the same bits.
+template <bool XMASK>
 __global__ void __launch_bounds__(256) k_bn_bwd_partial_v4(const float* __restrict__ dy, const float* __restrict__ x,
                                                            const float* __restrict__ y, int64_t M, int H,
                                                            const float* __restrict__ mean,
-                                                           const float* __restrict__ rstd, int relu,
+                                                           const float* __restrict__ rstd,
+                                                           const float* __restrict__ gamma,
+                                                           const float* __restrict__ beta, int relu,
                                                            float* __restrict__ part) {
+  constexpr int RIF = XMASK ? 4 : 2;  // rows in flight
   __shared__ f32x4 s1[8][32], s2[8][32];
   const int cq = threadIdx.x & 31, ry = threadIdx.x >> 5;
   const int col = blockIdx.y * 128 + cq * 4;
@@ -113,28 +134,39 @@ __global__ void __launch_bounds__(256) k_bn_bwd_partial_v4(const float* __restri
   if (col < H) {
     const f32x4 mu = *reinterpret_cast<const f32x4*>(mean + col);
     const f32x4 rs = *reinterpret_cast<const f32x4*>(rstd + col);
+    f32x4 fa = {0.f, 0.f, 0.f, 0.f}, fb = {0.f, 0.f, 0.f, 0.f};
+    if (XMASK && relu)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        float ae, be;
+        bn_col_ab(gamma, beta, mean, rstd, col + e, ae, be);
+        fa[e] = ae;
+        fb[e] = be;
+      }
     auto row = [&](int64_t r, f32x4& g, f32x4& xv, f32x4& yv) {
       g = *reinterpret_cast<const f32x4*>(dy + r * H + col);
       xv = *reinterpret_cast<const f32x4*>(x + r * H + col);
-      yv = *reinterpret_cast<const f32x4*>((relu ? y : x) + r * H + col);  // (unconditional: keeps the loads countable)
+      if constexpr (!XMASK)
+        yv = *reinterpret_cast<const f32x4*>((relu ? y : x) + r * H + col);  // (unconditional: keeps the loads countable)
     };
     auto fold = [&](f32x4 g, const f32x4& xv, const f32x4& yv) {
       if (relu) {
-        g.x = yv.x > 0.f ? g.x : 0.f;
-        g.y = yv.y > 0.f ? g.y : 0.f;
-        g.z = yv.z > 0.f ? g.z : 0.f;
-        g.w = yv.w > 0.f ? g.w : 0.f;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const float o = XMASK ? bn_affine(xv[e], fa[e], fb[e]) : yv[e];
+          g[e] = o > 0.f ? g[e] : 0.f;
+        }
       }
       a1 += g;
       a2 += g * ((xv - mu) * rs);
     };
     int64_t r = r0 + ry;
-    for (; r + 8 < r1; r += 16) {  // two rows (six loads) in flight; same order of additions as the one-row loop below
-      f32x4 g0, x0, y0, g1, x1, y1;
-      row(r, g0, x0, y0);
-      row(r + 8, g1, x1, y1);
-      fold(g0, x0, y0);
-      fold(g1, x1, y1);
+    for (; r + 8 * (RIF - 1) < r1; r += 8 * RIF) {  // RIF rows in flight; same order of additions as the one-row loop below
+      f32x4 g[RIF], xv[RIF], yv[RIF];
+#pragma unroll
+      for (int q = 0; q < RIF; ++q) row(r + 8 * q, g[q], xv[q], yv[q]);
+#pragma unroll
+      for (int q = 0; q < RIF; ++q) fold(g[q], xv[q], yv[q]);
     }
     for (; r < r1; r += 8) {
       f32x4 g, xv, yv;
@@ -157,7 +189,7 @@ __global__ void __launch_bounds__(256) k_bn_bwd_partial_v4(const float* __restri
   }
 }
 
-template <int VEC>
+template <int VEC, bool XMASK>
 __global__ void __launch_bounds__(256) k_bn_bwd_apply_v(const float* __restrict__ dy, const float* __restrict__ x,
                                                         const float* __restrict__ y, int64_t total, int H,
                                                         const float* __restrict__ mean, const float* __restrict__ rstd,
@@ -169,16 +201,23 @@ __global__ void __launch_bounds__(256) k_bn_bwd_apply_v(const float* __restrict_
     const int c = (int)(i % H);
     f32x4 g = *reinterpret_cast<const f32x4*>(dy + i);
     const f32x4 xv = *reinterpret_cast<const f32x4*>(x + i);
+    const f32x4 k0 = *reinterpret_cast<const f32x4*>(coef + c), k1 = *reinterpret_cast<const f32x4*>(coef + H + c),
+                k2 = *reinterpret_cast<const f32x4*>(coef + 2 * H + c);
     if (relu) {
-      const f32x4 yv = *reinterpret_cast<const f32x4*>(y + i);
+      f32x4 yv;
+      if constexpr (XMASK) {  // a = k0 (gamma * rstd = rstd * gamma), b' = coef row 3 (k_bn_bwd_finalize)
+        const f32x4 k3 = *reinterpret_cast<const f32x4*>(coef + 3 * H + c);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) yv[e] = bn_affine(xv[e], k0[e], k3[e]);
+      } else {
+        yv = *reinterpret_cast<const f32x4*>(y + i);
+      }
       g.x = yv.x > 0.f ? g.x : 0.f;
       g.y = yv.y > 0.f ? g.y : 0.f;
       g.z = yv.z > 0.f ? g.z : 0.f;
       g.w = yv.w > 0.f ? g.w : 0.f;
     }
     const f32x4 mu = *reinterpret_cast<const f32x4*>(mean + c), rs = *reinterpret_cast<const f32x4*>(rstd + c);
-    const f32x4 k0 = *reinterpret_cast<const f32x4*>(coef + c), k1 = *reinterpret_cast<const f32x4*>(coef + H + c),
-                k2 = *reinterpret_cast<const f32x4*>(coef + 2 * H + c);
     const f32x4 xh = (xv - mu) * rs;
     *reinterpret_cast<f32x4*>(dx + i) = k0 * (g - k1 - xh * k2);
   }
@@ -274,7 +313,7 @@ __global__ void __launch_bounds__(256) k_bn_apply(const float* __restrict__ x, i
       f32x4 v = *reinterpret_cast<const f32x4*>(x + i);
       f32x4 a = *reinterpret_cast<const f32x4*>(ab + c);
       f32x4 b = *reinterpret_cast<const f32x4*>(ab + H + c);
-      f32x4 o = {v.x * a.x + b.x, v.y * a.y + b.y, v.z * a.z + b.z, v.w * a.w + b.w};
+      f32x4 o = {bn_affine(v.x, a.x, b.x), bn_affine(v.y, a.y, b.y), bn_affine(v.z, a.z, b.z), bn_affine(v.w, a.w, b.w)};
       if (relu) {
         o.x = fmaxf(o.x, 0.f);
         o.y = fmaxf(o.y, 0.f);
@@ -283,7 +322,7 @@ __global__ void __launch_bounds__(256) k_bn_apply(const float* __restrict__ x, i
       }
       *reinterpret_cast<f32x4*>(y + i) = o;
     } else {
-      float o = x[i] * ab[c] + ab[H + c];
+      float o = bn_affine(x[i], ab[c], ab[H + c]);
       y[i] = relu ? fmaxf(o, 0.f) : o;
     }
   }
@@ -336,9 +375,11 @@ extern "C" int32_t gnx_batchnorm_fwd(gnx_handle* h, const float* x, int64_t M, i
 // ---------------------------------------------------------------------------------------------------------------
 // backward: g = dy * (y>0 if relu); dbeta = sum g; dgamma = sum g*xhat; dx = gamma*rstd*(g - dbeta/M - xhat*dgamma/M)
 // ---------------------------------------------------------------------------------------------------------------
+template <bool XMASK>
 __global__ void __launch_bounds__(256) k_bn_bwd_partial(const float* __restrict__ dy, const float* __restrict__ x,
                                                         const float* __restrict__ y, int64_t M, int H,
                                                         const float* __restrict__ mean, const float* __restrict__ rstd,
+                                                        const float* __restrict__ gamma, const float* __restrict__ beta,
                                                         int relu, float* __restrict__ part) {
   __shared__ float s1[4][64], s2[4][64];
   const int cx = threadIdx.x & 63, ry = threadIdx.x >> 6;
@@ -349,11 +390,14 @@ __global__ void __launch_bounds__(256) k_bn_bwd_partial(const float* __restrict_
   float a1 = 0.f, a2 = 0.f;
   if (col < H) {
     const float mu = mean[col], rs = rstd[col];
+    float fa = 0.f, fb = 0.f;
+    if (XMASK && relu) bn_col_ab(gamma, beta, mean, rstd, col, fa, fb);
     for (int64_t r = r0 + ry; r < r1; r += 4) {
       float g = dy[r * H + col];
-      if (relu && !(y[r * H + col] > 0.f)) g = 0.f;
+      const float xv = x[r * H + col];
+      if (relu && !((XMASK ? bn_affine(xv, fa, fb) : y[r * H + col]) > 0.f)) g = 0.f;
       a1 += g;
-      a2 += g * ((x[r * H + col] - mu) * rs);
+      a2 += g * ((xv - mu) * rs);
     }
   }
   s1[ry][cx] = a1;
@@ -365,9 +409,11 @@ __global__ void __launch_bounds__(256) k_bn_bwd_partial(const float* __restrict_
   }
 }
 
-// coef[c] = (gamma*rstd, dbeta/M, dgamma/M * rstd... ) stored as 4 rows of H: k0 = gamma*rstd, k1 = dbeta/M, k2 = dgamma/M
+// coef[c] = (gamma*rstd, dbeta/M, dgamma/M * rstd... ) stored as 4 rows of H: k0 = gamma*rstd, k1 = dbeta/M, k2 = dgamma/M,
+// k3 = the forward's b' = beta - mean * a (only with mean != NULL: the apply kernels that derive the ReLU mask from x)
 __global__ void k_bn_bwd_finalize(const float* __restrict__ part, int64_t chunks, int64_t M, int H,
-                                  const float* __restrict__ gamma, const float* __restrict__ rstd,
+                                  const float* __restrict__ gamma, const float* __restrict__ beta,
+                                  const float* __restrict__ mean, const float* __restrict__ rstd,
                                   float* __restrict__ dgamma, float* __restrict__ dbeta, float* __restrict__ coef) {
   const int c = blockIdx.x * 16 + (threadIdx.x & 15);
   float t1 = 0.f, t2 = 0.f;
@@ -379,8 +425,14 @@ __global__ void k_bn_bwd_finalize(const float* __restrict__ part, int64_t chunks
   coef[c] = (gamma ? gamma[c] : 1.f) * rstd[c];
   coef[H + c] = t1 * inv;
   coef[2 * H + c] = t2 * inv;
+  if (mean != nullptr) {
+    float a, b;
+    bn_col_ab(gamma, beta, mean, rstd, c, a, b);
+    coef[3 * H + c] = b;
+  }
 }
 
+template <bool XMASK>
 __global__ void __launch_bounds__(256) k_bn_bwd_apply(const float* __restrict__ dy, const float* __restrict__ x,
                                                       const float* __restrict__ y, int64_t total, int H,
                                                       const float* __restrict__ mean, const float* __restrict__ rstd,
@@ -390,10 +442,51 @@ __global__ void __launch_bounds__(256) k_bn_bwd_apply(const float* __restrict__ 
   for (; i < total; i += stride) {
     int c = (int)(i % H);
     float g = dy[i];
-    if (relu && !(y[i] > 0.f)) g = 0.f;
-    float xh = (x[i] - mean[c]) * rstd[c];
+    const float xv = x[i];
+    if (relu && !((XMASK ? bn_affine(xv, coef[c], coef[3 * H + c]) : y[i]) > 0.f)) g = 0.f;
+    float xh = (xv - mean[c]) * rstd[c];
     dx[i] = coef[c] * (g - coef[H + c] - xh * coef[2 * H + c]);
   }
+}
+
+// One launch path for both entries.  XMASK = false: gnx_batchnorm_bwd (mask from y).  XMASK = true: gnx_batchnorm_bwd_x
+// (mask from bn_affine(x, a, b'); two of the seven [M, H] passes less).
+template <bool XMASK>
+static int32_t bn_bwd_launch(gnx_handle* h, const float* dy, const float* x, const float* y, int64_t M, int32_t H,
+                             const float* gamma, const float* beta, const float* save_mean, const float* save_rstd,
+                             int32_t relu, float* dx, float* dgamma, float* dbeta, void* ws, size_t ws_bytes) {
+  if (ws_bytes < gnx_batchnorm_workspace_bytes(M, H)) {
+    gnx_set_error("gnx_batchnorm_bwd: workspace %zu < %zu", ws_bytes, gnx_batchnorm_workspace_bytes(M, H));
+    return GNX_E_WORKSPACE;
+  }
+  float* coef = reinterpret_cast<float*>(ws);
+  float* part = coef + 4 * (size_t)H;
+  int64_t chunks = gnx_cdiv(M, BN_ROWS_PER_BLOCK);
+  gnx_prof_scope prof(h, GNX_K_BN_BWD, (XMASK ? 20.0 : 28.0) * M * H);  // two passes over dy, x (, y) + write dx
+  if (H % 4 == 0)
+    hipLaunchKernelGGL(k_bn_bwd_partial_v4<XMASK>, dim3((unsigned)chunks, (unsigned)gnx_cdiv(H, 128)), dim3(256), 0,
+                       h->stream, dy, x, y, M, (int)H, save_mean, save_rstd, gamma, beta, (int)relu, part);
+  else
+    hipLaunchKernelGGL(k_bn_bwd_partial<XMASK>, dim3((unsigned)chunks, (unsigned)gnx_cdiv(H, 64)), dim3(256), 0, h->stream,
+                       dy, x, y, M, (int)H, save_mean, save_rstd, gamma, beta, (int)relu, part);
+  GNX_LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_bn_bwd_finalize, dim3((unsigned)gnx_cdiv(H, 16)), dim3(256), 0, h->stream, part, chunks, M, (int)H,
+                     gamma, beta, XMASK ? save_mean : nullptr, save_rstd, dgamma, dbeta, coef);
+  GNX_LAUNCH_CHECK();
+  int64_t total = M * H;
+  if (H % 4 == 0) {
+    int64_t blocks = gnx_cdiv(total / 4, 256);
+    if (blocks > 4096) blocks = 4096;
+    hipLaunchKernelGGL((k_bn_bwd_apply_v<4, XMASK>), dim3((unsigned)blocks), dim3(256), 0, h->stream, dy, x, y, total,
+                       (int)H, save_mean, save_rstd, coef, (int)relu, dx);
+  } else {
+    int64_t blocks = gnx_cdiv(total, 256);
+    if (blocks > 8192) blocks = 8192;
+    hipLaunchKernelGGL(k_bn_bwd_apply<XMASK>, dim3((unsigned)blocks), dim3(256), 0, h->stream, dy, x, y, total, (int)H,
+                       save_mean, save_rstd, coef, (int)relu, dx);
+  }
+  GNX_LAUNCH_CHECK();
+  return GNX_OK;
 }
 
 extern "C" int32_t gnx_batchnorm_bwd(gnx_handle* h, const float* dy, const float* x, const float* y, int64_t M,
@@ -402,38 +495,19 @@ extern "C" int32_t gnx_batchnorm_bwd(gnx_handle* h, const float* dy, const float
   GNX_CHECK_ARG(h && H > 0 && M >= 0, "gnx_batchnorm_bwd: bad argument");
   if (M == 0) return GNX_OK;
   GNX_CHECK_ARG(dy && x && save_mean && save_rstd && dx && ws && (!relu || y), "gnx_batchnorm_bwd: NULL argument");
-  if (ws_bytes < gnx_batchnorm_workspace_bytes(M, H)) {
-    gnx_set_error("gnx_batchnorm_bwd: workspace %zu < %zu", ws_bytes, gnx_batchnorm_workspace_bytes(M, H));
-    return GNX_E_WORKSPACE;
-  }
-  float* coef = reinterpret_cast<float*>(ws);
-  float* part = coef + 4 * (size_t)H;
-  int64_t chunks = gnx_cdiv(M, BN_ROWS_PER_BLOCK);
-  gnx_prof_scope prof(h, GNX_K_BN_BWD, 28.0 * M * H);  // two passes over dy, x, y + write dx
-  if (H % 4 == 0)
-    hipLaunchKernelGGL(k_bn_bwd_partial_v4, dim3((unsigned)chunks, (unsigned)gnx_cdiv(H, 128)), dim3(256), 0, h->stream,
-                       dy, x, y, M, (int)H, save_mean, save_rstd, (int)relu, part);
-  else
-    hipLaunchKernelGGL(k_bn_bwd_partial, dim3((unsigned)chunks, (unsigned)gnx_cdiv(H, 64)), dim3(256), 0, h->stream, dy,
-                       x, y, M, (int)H, save_mean, save_rstd, (int)relu, part);
-  GNX_LAUNCH_CHECK();
-  hipLaunchKernelGGL(k_bn_bwd_finalize, dim3((unsigned)gnx_cdiv(H, 16)), dim3(256), 0, h->stream, part, chunks, M, (int)H,
-                     gamma, save_rstd, dgamma, dbeta, coef);
-  GNX_LAUNCH_CHECK();
-  int64_t total = M * H;
-  if (H % 4 == 0) {
-    int64_t blocks = gnx_cdiv(total / 4, 256);
-    if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(k_bn_bwd_apply_v<4>, dim3((unsigned)blocks), dim3(256), 0, h->stream, dy, x, y, total, (int)H,
-                       save_mean, save_rstd, coef, (int)relu, dx);
-  } else {
-    int64_t blocks = gnx_cdiv(total, 256);
-    if (blocks > 8192) blocks = 8192;
-    hipLaunchKernelGGL(k_bn_bwd_apply, dim3((unsigned)blocks), dim3(256), 0, h->stream, dy, x, y, total, (int)H,
-                       save_mean, save_rstd, coef, (int)relu, dx);
-  }
-  GNX_LAUNCH_CHECK();
-  return GNX_OK;
+  return bn_bwd_launch<false>(h, dy, x, y, M, H, gamma, nullptr, save_mean, save_rstd, relu, dx, dgamma, dbeta, ws,
+                              ws_bytes);
+}
+
+extern "C" int32_t gnx_batchnorm_bwd_x(gnx_handle* h, const float* dy, const float* x, int64_t M, int32_t H,
+                                       const float* gamma, const float* beta, const float* save_mean,
+                                       const float* save_rstd, int32_t relu, float* dx, float* dgamma, float* dbeta,
+                                       void* ws, size_t ws_bytes) {
+  GNX_CHECK_ARG(h && H > 0 && M >= 0, "gnx_batchnorm_bwd_x: bad argument");
+  if (M == 0) return GNX_OK;
+  GNX_CHECK_ARG(dy && x && save_mean && save_rstd && dx && ws, "gnx_batchnorm_bwd_x: NULL argument");
+  return bn_bwd_launch<true>(h, dy, x, nullptr, M, H, gamma, beta, save_mean, save_rstd, relu, dx, dgamma, dbeta, ws,
+                             ws_bytes);
 }
 
 // ---------------------------------------------------------------------------------------------------------------

@@ -204,18 +204,19 @@ class BatchNormFn(torch.autograd.Function):
         x = x.contiguous()
         y, mean, rstd = ops.batchnorm_fwd(x, gamma, beta, running_mean, running_var, momentum, eps, training, relu,
                                           num_batches_tracked=nbt)
-        ctx.save_for_backward(x, y, gamma, mean, rstd)
+        ctx.save_for_backward(x, gamma, beta, mean, rstd)  # (not y: the backward recomputes the ReLU mask from x)
         ctx.relu, ctx.training = relu, training
         ctx.sinks = grad_sinks([gamma, beta])
         return y
 
     @staticmethod
     def backward(ctx, dy):
-        x, y, gamma, mean, rstd = ctx.saved_tensors
+        x, gamma, beta, mean, rstd = ctx.saved_tensors
         if not ctx.training:
             raise NotImplementedError("BatchNorm backward in eval mode is not on the reference's training path")
         sg, sb = ctx.sinks
-        dx, dgamma, dbeta = ops.batchnorm_bwd(dy.contiguous(), x, y, gamma, mean, rstd, ctx.relu, dgamma=sg, dbeta=sb)
+        dx, dgamma, dbeta = ops.batchnorm_bwd(dy.contiguous(), x, None, gamma, mean, rstd, ctx.relu, dgamma=sg, dbeta=sb,
+                                              beta=beta)
         return dx, (None if sg is not None else dgamma), (None if sb is not None else dbeta), None, None, None, None, \
             None, None, None
 

@@ -1207,8 +1207,14 @@ def batchnorm_fwd(x, gamma, beta, running_mean, running_var, momentum: float, ep
     return y, mean, rstd
 
 
-def batchnorm_bwd(dy, x, y, gamma, mean, rstd, relu: bool, dgamma=None, dbeta=None):
-    """dgamma / dbeta: optional existing buffers to accumulate (+=) into; fresh zero buffers otherwise."""
+_NO_BETA = object()  # batchnorm_bwd(beta=...) not given (None is a value: a BatchNorm without affine parameters)
+
+
+def batchnorm_bwd(dy, x, y, gamma, mean, rstd, relu: bool, dgamma=None, dbeta=None, *, beta=_NO_BETA):
+    """dgamma / dbeta: optional existing buffers to accumulate (+=) into; fresh zero buffers otherwise.
+
+    With ``beta=`` (the forward's beta, or None where the forward had none) the ReLU mask is recomputed from ``x``
+    (gnx_batchnorm_bwd_x) and ``y`` is ignored (may be None): the same bits, two passes over [M, H] less."""
     M, H = x.shape
     dx = torch.empty_like(x)
     if dgamma is None:
@@ -1216,6 +1222,11 @@ def batchnorm_bwd(dy, x, y, gamma, mean, rstd, relu: bool, dgamma=None, dbeta=No
     if dbeta is None:
         dbeta = zeros(H, device=x.device)
     ws, nbytes = _bn_ws(M, H, x.device)
+    if beta is not _NO_BETA:
+        check(_lib.load().gnx_batchnorm_bwd_x(handle(x.device), dy.data_ptr(), x.data_ptr(), M, H, _ptr(gamma), _ptr(beta),
+                                              mean.data_ptr(), rstd.data_ptr(), int(relu), dx.data_ptr(),
+                                              dgamma.data_ptr(), dbeta.data_ptr(), ws.data_ptr(), nbytes))
+        return dx, dgamma, dbeta
     check(_lib.load().gnx_batchnorm_bwd(handle(x.device), dy.data_ptr(), x.data_ptr(), y.data_ptr(), M, H, _ptr(gamma),
                                         mean.data_ptr(), rstd.data_ptr(), int(relu), dx.data_ptr(), dgamma.data_ptr(),
                                         dbeta.data_ptr(), ws.data_ptr(), nbytes))

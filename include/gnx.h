@@ -527,6 +527,14 @@ int32_t gnx_batchnorm_fwd(gnx_handle* h, const float* x, int64_t M, int32_t H, c
 int32_t gnx_batchnorm_bwd(gnx_handle* h, const float* dy, const float* x, const float* y, int64_t M, int32_t H,
                           const float* gamma, const float* save_mean, const float* save_rstd, int32_t relu,
                           float* dx, float* dgamma, float* dbeta, void* ws, size_t ws_bytes);
+/* The same without y: the ReLU mask is recomputed as x * a + b' > 0 with a = rstd * gamma and b' = beta - mean * a, the
+ * forward's own expression (one device helper, no contraction), so dx / dgamma / dbeta are bit-identical to
+ * gnx_batchnorm_bwd given the y of a training-mode gnx_batchnorm_fwd with the same x, gamma, beta.  Two of the seven
+ * [M, H] passes less.  gamma / beta may be NULL (1 / 0).  Same workspace size.  gamma and beta must still hold the
+ * forward's values when this runs (the optimizer step comes after the backward). */
+int32_t gnx_batchnorm_bwd_x(gnx_handle* h, const float* dy, const float* x, int64_t M, int32_t H, const float* gamma,
+                            const float* beta, const float* save_mean, const float* save_rstd, int32_t relu, float* dx,
+                            float* dgamma, float* dbeta, void* ws, size_t ws_bytes);
 
 /* ---- dropout (ref: train/models.py:177, 209; p = 0.25 in configs/pna_msigmae_7.py:40) --------------------------- */
 /* y[i] = keep(i) ? x[i] / (1 - p) : 0 with keep(i) decided by Philox4x32-10 on the counter (i / 4, offset) under the
