@@ -310,17 +310,30 @@ struct weff_batch_args {
   int F, D;
 };
 
-__global__ void k_pna_weff_batched(weff_batch_args a) {
+// Entry-wise within 4 u (|W1| + amp |W2| + att |W3|) of the exact value (u = 2^-24; tests/test_wgrad_gpu.py): the two
+// factors are evaluated in double and rounded once (<= 1 u each; fp32 logf-and-divide is up to 3 u), then each scaled
+// term carries its factor's and its product's rounding (2 u of the term) and the two additions one rounding each.  Once
+// per block instead of per thread: a block's 256 consecutive elements belong to at most 256 / (4 F^2) + 2 <= 66 classes.
+#define WEFF_BLOCK 256
+#define WEFF_CLS (WEFF_BLOCK / 4 + 2)
+__global__ void __launch_bounds__(WEFF_BLOCK) k_pna_weff_batched(weff_batch_args a) {
+  __shared__ float s_amp[WEFF_CLS], s_att[WEFF_CLS];
   const int b = blockIdx.y;
   const int F = a.F;
-  int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int64_t first = (int64_t)blockIdx.x * WEFF_BLOCK;
+  int64_t i = first + threadIdx.x;
   int64_t per = (int64_t)F * 4 * F;
+  const int d0 = (int)(first / per);
+  if (threadIdx.x < WEFF_CLS) {
+    const double dd = (double)(d0 + (int)threadIdx.x), avg = (double)a.avg_log[b];
+    s_amp[threadIdx.x] = (float)(log(dd + 1.0) / avg);
+    s_att[threadIdx.x] = (float)(avg / log(fmax(dd, 1.0) + 1.0));
+  }
+  __syncthreads();
   if (i >= per * a.D) return;
   int d = (int)(i / per);
   int o = (int)((i % per) / (4 * F)), j = (int)(i % (4 * F));
-  float dd = (float)d;
-  float amp = logf(dd + 1.0f) / a.avg_log[b];
-  float att = a.avg_log[b] / logf(fmaxf(dd, 1.0f) + 1.0f);
+  const float amp = s_amp[d - d0], att = s_att[d - d0];
   const float* w = a.W[b] + (int64_t)o * a.ldw;
   a.out[b][i] = w[F + j] + amp * w[5 * F + j] + att * w[9 * F + j];
 }

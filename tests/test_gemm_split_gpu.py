@@ -18,7 +18,11 @@ TOL = 1e-5
 
 @pytest.fixture(params=[1, 0], ids=["wave_specialised", "two_barrier"])
 def wgrad_kernel(request, gpu_device):
-    """Runs a weight-gradient test through k_gemm_wgrad3p (default) and through k_gemm_wgrad3 (GNX_OPT_WGRAD_PIPE = 0)."""
+    """GNX_OPT_WGRAD_PIPE = 1 (default) and 0.  With 0 every split weight gradient runs k_gemm_wgrad3 (batched:
+    k_gemm_wgrad3_batched).  With 1 a batched launch runs k_gemm_wgrad3p_batched, and a single launch runs k_gemm_wgrad3p
+    only for 16-byte aligned operands with N, K multiples of 4 AND rows >= 512 per workgroup (wgrad_launch; rows =
+    M over the workgroup target, rounded up to 32) -- at one workgroup per CU that needs M >= 512 CUs, so a test that
+    means to reach it pins GNX_OPT_WGRAD_WGS (tests/wgrad_ref.py: takes_wave_specialised)."""
     from gnnepcsaft_amd import ops
     ops.set_option(torch.device("cuda:0"), _lib.OPT_WGRAD_PIPE, request.param)
     yield request.param
@@ -337,15 +341,25 @@ def test_split_and_exact_kernels_agree(gpu_device):
 @pytest.mark.parametrize("M,N,K", [(20001, 128, 128), (8192, 36, 100), (5000, 130, 260)])
 def test_split_weight_gradient_single(gpu_device, wgrad_kernel, M, N, K):
     """dW += dC^T A and db += column sums on the split-operand kernel (no row scale, M >= 4096): ragged shapes, strided
-    views, accumulation into existing values."""
+    views, accumulation into existing values.  Eight workgroups per output tile (GNX_OPT_WGRAD_WGS), so that under the
+    wave_specialised fixture the two aligned shapes do run k_gemm_wgrad3p (2528 and 1024 rows per workgroup)."""
     from gnnepcsaft_amd import ops
+    from tests.wgrad_ref import takes_wave_specialised, wgrad_kernel_name
+    vec = N % 4 == 0 and K % 4 == 0  # the views below are 16-byte aligned with leading dimensions N + 8, K + 12
+    assert takes_wave_specialised(M, N, K, 8, vec=vec, pipe=wgrad_kernel != 0) == (vec and wgrad_kernel != 0)
+    if not (vec and wgrad_kernel != 0):
+        assert wgrad_kernel_name(M, N, K, 8, vec=vec, pipe=wgrad_kernel != 0) == "k_gemm_wgrad3<false>"
     torch.manual_seed(M + N)
     wide_dc, wide_a = torch.randn(M, N + 8), torch.randn(M, K + 12)
     dc, a = wide_dc[:, 4:4 + N], wide_a[:, 8:8 + K]
     dcd, ad = wide_dc.to(gpu_device)[:, 4:4 + N], wide_a.to(gpu_device)[:, 8:8 + K]
     dw = torch.full((N, K), 2.0, device=gpu_device)
     db = torch.full((N,), -1.0, device=gpu_device)
-    ops.gemm_wgrad(dcd, ad, dw, dbias=db)
+    ops.set_option(torch.device("cuda:0"), _lib.OPT_WGRAD_WGS, 8)
+    try:
+        ops.gemm_wgrad(dcd, ad, dw, dbias=db)
+    finally:
+        ops.set_option(torch.device("cuda:0"), _lib.OPT_WGRAD_WGS, 0)
     assert rel_err(dw, 2.0 + dc.double().T @ a.double()) <= TOL
     assert rel_err(db, -1.0 + dc.double().sum(0)) <= TOL
 
