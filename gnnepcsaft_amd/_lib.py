@@ -18,6 +18,10 @@ GNX_OK, GNX_E_INVALID, GNX_E_HIP, GNX_E_RANGE, GNX_E_WORKSPACE = 0, -1, -2, -3, 
 OPT_GEMM_SPLIT, OPT_WGRAD_WGS, OPT_EMBED_BWD_MFMA, OPT_STD_BWD_CENTERED, OPT_GEMM_PIPE, OPT_WGRAD_PIPE, OPT_GEMM_AS, \
     OPT_GEMM_WS_FAST, OPT_GEMM_TILE_ROWS, OPT_GEMM_MID = range(10)
 GEMM_RELU, GEMM_ACCUMULATE, GEMM_B_TRANS, GEMM_SPLIT_ONLY, GEMM_PRESPLIT = 1, 2, 4, 8, 16
+# GNX_GEMM_KERNEL_*, by value (gnx_gemm_plan)
+GEMM_KERNEL_NAMES = ("none", "k_gemm<vec>", "k_gemm<generic>", "k_gemm_ws", "k_gemm_ws3", "k_gemm_ws3<fast,8>",
+                     "k_gemm_ws3<fast,4>", "k_gemm3", "k_gemm3p<96>", "k_gemm3p<128>", "k_gemm_as3", "k_gemm_mid",
+                     "k_gemm_small_batched")
 POOL_ADD, POOL_MEAN, POOL_MAX = 0, 1, 2
 K_NONE, K_PNA_AGG_FWD, K_PNA_AGG_BWD, K_GEMM_WS, K_GEMM_WGRAD, K_GINE_AGG_FWD, K_GINE_AGG_BWD, K_EDGE_COMBINE_FWD, \
     K_EDGE_COMBINE_BWD, K_BN_FWD, K_BN_BWD, K_GEMM_TILED, K_GEMM_SMALL, K_GEMM_WGRAD_BATCHED, K_KEY_SEGMENT_SUM, \
@@ -45,6 +49,11 @@ class GnxError(RuntimeError):
 class GemmSeg(C.Structure):
     _fields_ = [("a", C.c_void_p), ("lda", C.c_int64), ("rowscale", C.c_void_p), ("b", C.c_void_p),
                 ("ldb", C.c_int64), ("k", C.c_int32), ("_pad", C.c_int32)]
+
+
+class GemmPlanInfo(C.Structure):
+    _fields_ = [("kernel", C.c_int32), ("tile_rows", C.c_int32), ("grid_x", C.c_uint32), ("grid_y", C.c_uint32),
+                ("block", C.c_uint32), ("runs_split", C.c_int32), ("image_bytes", C.c_size_t)]
 
 
 class WgradProb(C.Structure):
@@ -144,6 +153,8 @@ SIGNATURES = {
     "gnx_gemm_tile_rows": (_i32, [_vp, _i64, _i32]),
     "gnx_gemm_grouped_rows": (_i32, [_vp, _i32, C.POINTER(GemmSeg), C.POINTER(_i64), _i32, _i64, _i32, _vp, _vp, _i64, _vp,
                                      _i64, _i32, _vp, _vp, _vp, _i64, _vp, _sz, _i32]),
+    "gnx_gemm_plan": (_i32, [_vp, _i32, C.POINTER(GemmSeg), C.POINTER(_i64), _i32, _i64, _i32, _vp, _vp, _i64, _vp, _i64, _i32,
+                             _vp, _vp, _vp, _i64, _vp, _sz, _i32, C.POINTER(GemmPlanInfo)]),
     "gnx_gemm_wgrad_grouped": (_i32, [_vp, _vp, _i64, _vp, _i64, _i64, _i32, _i32, _vp, _i64, _i64, _vp, _vp, _vp,
                                       _i64]),
     "gnx_pna_weff": (_i32, [_vp, _vp, _i64, _i32, _i32, _f32, _vp]),

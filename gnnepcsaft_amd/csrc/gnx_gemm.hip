@@ -22,6 +22,7 @@
 //        the 16 lanes of every ds_read_b128 group hit 16 distinct 16-byte slots (MI355X_MICROARCH.md, LDS table).
 //   "k-row" image  T[k][col]  (B when the weight is [k][n], i.e. NN; both operands of the weight gradient):
 //        row stride 128 floats, read with ds_read_b32 (32 consecutive columns per half-wave: conflict-free).
+#include "gnx_gemm_plan.hpp"
 #include "gnx_split.hpp"
 
 #include <cstdlib>
@@ -490,14 +491,6 @@ __global__ void __launch_bounds__(512, 1) k_gemm_ws(ws_args g) {
     cur ^= 1;
     tile = next;
   }
-}
-
-template <bool BT, int EPI>
-static hipError_t ws_launch_one(gnx_handle* h, const ws_args& g, int grid, size_t lds_bytes) {
-  const hipError_t e = gnx_raise_lds_limit<&k_gemm_ws<BT, EPI>>(160 * 1024);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL((k_gemm_ws<BT, EPI>), dim3(grid), dim3(512), lds_bytes, h->stream, g);
-  return hipGetLastError();
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -1703,80 +1696,6 @@ __global__ void __launch_bounds__(256, 3) k_gemm_as3(gemm_args g) {
 #endif
 }
 
-template <bool BT, int EPI, bool FAST, int NW>
-static hipError_t ws3_launch_fast(gnx_handle* h, const ws_args& g, int grid) {
-  // LDS: two stages of a TM-row tile, and at least the 64 KB the NN weight staging image needs
-  constexpr size_t lds = (NW == 8) ? (size_t)(2 * W3_BUF) : (size_t)(64 * 1024);
-  const hipError_t e = gnx_raise_lds_limit<&k_gemm_ws3<BT, EPI, FAST, NW>>(NW == 8 ? 160 * 1024 : 64 * 1024);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL((k_gemm_ws3<BT, EPI, FAST, NW>), dim3(grid), dim3(64 * NW), lds, h->stream, g);
-  return hipGetLastError();
-}
-
-template <bool BT, int EPI>
-static hipError_t ws3_launch_one(gnx_handle* h, const ws_args& g, int grid) {
-  if constexpr (EPI != EPI_ACCUM) {
-    // the predicate-free kernel: all 128 columns, 16-byte stores (and mask loads), no read-modify-write of C
-    const bool fast = h->opt[GNX_OPT_GEMM_WS_FAST] != 0 && g.N == 128 && aligned16(g.C) && g.ldc % 4 == 0 &&
-                      (g.mask == nullptr || (aligned16(g.mask) && g.ldmask % 4 == 0));
-    if (fast && h->opt[GNX_OPT_GEMM_WS_FAST] == 2) {  // two 4-wave workgroups per CU on 32-row tiles
-      ws_args g2 = g;
-      g2.ntiles = (int)gnx_cdiv(g.M, (int64_t)32);
-      const int cus = h->num_cus > 0 ? h->num_cus : 256;
-      const int grid2 = g2.ntiles < 2 * cus ? g2.ntiles : 2 * cus;
-      return ws3_launch_fast<BT, EPI, true, 4>(h, g2, grid2);
-    }
-    if (fast) return ws3_launch_fast<BT, EPI, true, 8>(h, g, grid);
-  }
-  return ws3_launch_fast<BT, EPI, false, 8>(h, g, grid);
-}
-
-static int32_t gemm_ws_launch(gnx_handle* h, const gnx_gemm_seg& s, int64_t M, int32_t N, const float* bias,
-                              const float* mask, int64_t ldmask, float* C, int64_t ldc, int32_t flags) {
-  ws_args g;
-  g.A = s.a;
-  g.lda = s.lda;
-  g.B = s.b;
-  g.ldb = s.ldb;
-  g.M = M;
-  g.N = N;
-  g.K = s.k;
-  g.bias = bias;
-  g.mask = mask;
-  g.ldmask = ldmask;
-  g.C = C;
-  g.ldc = ldc;
-  g.relu = (flags & GNX_GEMM_RELU) ? 1 : 0;
-  g.ntiles = (int)gnx_cdiv(M, WS_BM);
-  const bool bt = (flags & GNX_GEMM_B_TRANS) != 0;
-  const int epi = mask ? EPI_MASK : ((flags & GNX_GEMM_ACCUMULATE) ? EPI_ACCUM : EPI_PLAIN);
-  const size_t lds_bytes = sizeof(float) * (128 * WS_LD + 2 * WS_BM * WS_LD);
-  const int cus = h->num_cus > 0 ? h->num_cus : 256;
-  const int grid = g.ntiles < cus ? g.ntiles : cus;
-  const bool split = h->opt[GNX_OPT_GEMM_SPLIT] != 0;  // 0 = exact-fp32 MFMA kernel (A/B switch)
-  const double fl = 2.0 * (double)M * N * s.k;
-  gnx_prof_scope prof(h, GNX_K_GEMM_WS, 4.0 * M * (s.k + N) + ((mask || (flags & GNX_GEMM_ACCUMULATE)) ? 4.0 * M * N : 0.0) +
-                                            4.0 * N * s.k, fl, split ? 6.0 * fl : 0.0);
-  const hipError_t e = epi_dispatch(bt, epi, [&](auto BT, auto EPI) {
-    return split ? ws3_launch_one<BT, EPI>(h, g, grid) : ws_launch_one<BT, EPI>(h, g, grid, lds_bytes);
-  });
-  if (e != hipSuccess) {
-    gnx_set_error("gnx_gemm (weights-stationary): %s", hipGetErrorString(e));
-    return GNX_E_HIP;
-  }
-  return GNX_OK;
-}
-
-// eligibility of the weights-stationary path (everything else goes to the tiled kernel)
-static bool gemm_ws_eligible(int32_t nseg, const gnx_gemm_seg* segs, int64_t M, int32_t N, const float* mask, int32_t flags) {
-  if (nseg != 1 || M < 8192) return false;
-  const gnx_gemm_seg& s = segs[0];
-  if (s.rowscale != nullptr || s.k > 128 || s.k < 32 || N > 128 || N < 32) return false;
-  if ((s.k % 4) != 0 || (N % 4) != 0) return false;
-  if (!aligned16(s.a) || (s.lda % 4) != 0 || !aligned16(s.b) || (s.ldb % 4) != 0) return false;
-  return !(mask != nullptr && (flags & GNX_GEMM_ACCUMULATE));
-}
-
 // ---------------------------------------------------------------------------------------------------------------
 // Mid-size product (M < 4096 rows and few 128 x 128 tiles: a 32-graph batch's 640 atoms / 1 280 bonds): the whole gnx_gemm
 // contract (segments, row scale, degree-class grouping, every epilogue) on 16 x 16 output patches, one output per thread,
@@ -2030,60 +1949,18 @@ extern "C" int32_t gnx_gemm_small_batched(gnx_handle* h, int32_t nprob, const gn
   return GNX_OK;
 }
 
-// Which products take the split-operand tiled kernel (k_split_weights -> k_gemm3) and how many bytes of split weight
-// images they need.  Shared by gnx_gemm_workspace_bytes and the launch path so both always agree.
-static size_t gemm_split_bytes(const gnx_handle* h, int32_t nseg, const gnx_gemm_seg* segs, const int64_t* cls_strides,
-                               int32_t num_classes, int64_t M, int32_t N, const float* mask, int32_t flags,
-                               bool grouped) {
-  if (h == nullptr || segs == nullptr || nseg < 1 || nseg > MAX_SEGS || M < 4096 || N <= 0) return 0;
-  if (h->opt[GNX_OPT_GEMM_SPLIT] == 0) return 0;
-  if (!grouped && gemm_ws_eligible(nseg, segs, M, N, mask, flags)) return 0;  // weights live in registers there
-  const bool bt = (flags & GNX_GEMM_B_TRANS) != 0;
-  int64_t kpad = 0;
-  int ksteps = 0;
-  for (int q = 0; q < nseg; ++q) {
-    const gnx_gemm_seg& in = segs[q];
-    const int64_t cs = cls_strides ? cls_strides[q] : 0;
-    if (in.rowscale != nullptr || in.k <= 0) return 0;
-    if (!aligned16(in.a) || (in.lda % 4) != 0 || !aligned16(in.b) || (in.ldb % 4) != 0 || (cs % 4) != 0) return 0;
-    if ((in.k % 4) != 0 || (!bt && (N % 4) != 0)) return 0;
-    ksteps += (int)gnx_cdiv((int64_t)in.k, BK);
-    kpad += gnx_cdiv((int64_t)in.k, BK) * BK;
-  }
-  if (ksteps < 2) return 0;
-  const int64_t npad = gnx_cdiv((int64_t)N, BN) * BN;
-  const int64_t D = num_classes > 0 ? num_classes : 1;
-  return (size_t)(D * 3 * npad * kpad) * sizeof(__bf16);
-}
+// Host side of gnx_gemm / gnx_gemm_grouped / gnx_gemm_grouped_rows: check the arguments, ask gnx_gemm_plan.hpp which kernel
+// the call takes, launch from the plan.  The plan's copies of the kernels' geometry:
+static_assert(PLAN_MAX_SEGS == MAX_SEGS && PLAN_BM == BM && PLAN_BN == BN && PLAN_BK == BK, "plan / tiled kernel geometry");
+static_assert(PLAN_EPI_PLAIN == EPI_PLAIN && PLAN_EPI_ACCUM == EPI_ACCUM && PLAN_EPI_MASK == EPI_MASK, "plan / epilogue kinds");
+static_assert(PLAN_WS_BM == WS_BM && PLAN_WS_LDS == sizeof(float) * (128 * WS_LD + 2 * WS_BM * WS_LD), "plan / k_gemm_ws");
+static_assert(PLAN_WS_BM == W3_BM && PLAN_WS3_LDS8 == 2 * W3_BUF, "plan / k_gemm_ws3");
+static_assert(PLAN_G3P_MIN_KTILES == G3P_MIN_KTILES && plan_g3p_lds(3) == G3P_LDS(3) && plan_g3p_lds(4) == G3P_LDS(4), "plan / k_gemm3p");
+static_assert(PLAN_AS_BM == AS_BM && PLAN_AS_LDS == AS_LDS, "plan / k_gemm_as3");
+static_assert(PLAN_PATCH == MID_T && PLAN_PATCH == SM_T, "plan / k_gemm_mid, k_gemm_small_batched");
 
-// Row-tile height of the pipelined tiled product for M rows x N columns: 96 where that shortens the longest workgroup's
-// walk (rounds x tile height; persistent workgroups, two per CU), else 128.  GNX_OPT_GEMM_TILE_ROWS forces 96 / 128.
-static int gemm_pipe_tile_rows(const gnx_handle* h, int64_t M, int32_t N) {
-  const int forced = h->opt[GNX_OPT_GEMM_TILE_ROWS];
-  if (forced == 96 || forced == 128) return forced;
-  const int64_t ny = gnx_cdiv((int64_t)N, BN);
-  const int64_t slots = 2 * (int64_t)(h->num_cus > 0 ? h->num_cus : 256);
-  int best = 128;
-  int64_t best_cost = gnx_cdiv(gnx_cdiv(M, (int64_t)128) * ny, slots) * 128;
-  for (int rows : {96}) {  // strictly shorter longest walk only (ties keep 128, the most measured shape)
-    const int64_t c = gnx_cdiv(gnx_cdiv(M, (int64_t)rows) * ny, slots) * rows;
-    if (c < best_cost) {
-      best_cost = c;
-      best = rows;
-    }
-  }
-  return best;
-}
-
-extern "C" int32_t gnx_gemm_tile_rows(gnx_handle* h, int64_t M, int32_t N) {
-  if (h == nullptr || M <= 0 || N <= 0) return 128;
-  return gemm_pipe_tile_rows(h, M, N);
-}
-
-static int32_t gemm_launch(gnx_handle* h, int32_t nseg, const gnx_gemm_seg* segs, const int64_t* cls_strides,
-                           int32_t num_classes, int64_t M, int32_t N, const float* bias, const float* mask, int64_t ldmask, float* C,
-                           int64_t ldc, int32_t flags, const int32_t* row_index, const int32_t* tile_info,
-                           const int32_t* ntiles, int64_t max_tiles, void* ws, size_t ws_bytes, int32_t tile_rows = 0) {
+static int32_t gemm_check(gnx_handle* h, int32_t nseg, const gnx_gemm_seg* segs, int64_t M, int32_t N, const float* mask,
+                          int64_t ldmask, const float* C, int64_t ldc, int32_t flags, int32_t tile_rows) {
   GNX_CHECK_ARG(h && segs && C, "gnx_gemm: NULL argument");
   GNX_CHECK_ARG(tile_rows == 0 || tile_rows == 96 || tile_rows == 128, "gnx_gemm: tile_rows=%d not in {0, 96, 128}", tile_rows);
   GNX_CHECK_ARG(nseg >= 1 && nseg <= MAX_SEGS, "gnx_gemm: nseg=%d not in [1,%d]", nseg, MAX_SEGS);
@@ -2099,155 +1976,91 @@ static int32_t gemm_launch(gnx_handle* h, int32_t nseg, const gnx_gemm_seg* segs
     GNX_CHECK_ARG(in.lda >= in.k, "gnx_gemm: segment %d: lda < k", s);
     GNX_CHECK_ARG(bt ? in.ldb >= in.k : in.ldb >= N, "gnx_gemm: segment %d: ldb too small", s);
   }
-  const bool split_only = (flags & GNX_GEMM_SPLIT_ONLY) != 0;  // only the weight images (if this call uses any) are written
-  if (tile_info == nullptr && gemm_ws_eligible(nseg, segs, M, N, mask, flags))
-    return split_only ? GNX_OK : gemm_ws_launch(h, segs[0], M, N, bias, mask, ldmask, C, ldc, flags);
-  if (split_only && M < 4096) return GNX_OK;  // (no split path below 4096 rows)
-  if (tile_info == nullptr && nseg == 1 && M <= 256 && mask == nullptr && segs[0].rowscale == nullptr &&
-      h->opt[GNX_OPT_GEMM_MID] == 0) {  // (k_gemm_mid below computes the same k-ordered chain with 16-byte staging loads and
-                                        // the next chunk prefetched: 3-4 us instead of 7-10 us for a 20-row product)
-    const gnx_gemm_seg& s0 = segs[0];
-    const gnx_small_prob p = {s0.a, s0.lda, s0.b, s0.ldb, bias, C, ldc, (int32_t)M, N, s0.k,
-                              (bt ? GNX_SB_B_TRANS : 0) | ((flags & GNX_GEMM_RELU) ? GNX_SB_RELU : 0) |
-                                  ((flags & GNX_GEMM_ACCUMULATE) ? GNX_SB_ACCUMULATE : 0)};
-    return gnx_gemm_small_batched(h, 1, &p);
-  }
+  return GNX_OK;
+}
 
-  gemm_args g;
-  for (int s = 0; s < MAX_SEGS; ++s) g.seg[s] = seg_dev{nullptr, nullptr, nullptr, 0, 0, 0, 0, 0, 0};
-  for (int s = 0; s < nseg; ++s) {
-    const gnx_gemm_seg& in = segs[s];
-    seg_dev d;
-    d.a = in.a;
-    d.rs = in.rowscale;
-    d.b = in.b;
-    d.lda = in.lda;
-    d.ldb = in.ldb;
-    d.cls_stride = cls_strides ? cls_strides[s] : 0;
-    d.k = in.k;
-    d.vec_a = aligned16(in.a) && (in.lda % 4 == 0);
-    d.vec_b = aligned16(in.b) && (in.ldb % 4 == 0) && (d.cls_stride % 4 == 0);
-    g.seg[s] = d;
+static int32_t gemm_launch(gnx_handle* h, int32_t nseg, const gnx_gemm_seg* segs, const int64_t* cls_strides,
+                           int32_t num_classes, int64_t M, int32_t N, const float* bias, const float* mask, int64_t ldmask, float* C,
+                           int64_t ldc, int32_t flags, const int32_t* row_index, const int32_t* tile_info,
+                           const int32_t* ntiles, int64_t max_tiles, void* ws, size_t ws_bytes, int32_t tile_rows = 0) {
+  const int32_t st = gemm_check(h, nseg, segs, M, N, mask, ldmask, C, ldc, flags, tile_rows);
+  if (st != GNX_OK) return st;
+  const gemm_plan p = gemm_plan_of(nseg, segs, cls_strides, num_classes, M, N, bias, mask, ldmask, C, ldc, flags, tile_info,
+                                   max_tiles, ws, tile_rows, h->opt, h->num_cus);
+  if (p.images && ws_bytes < p.image_bytes) {
+    gnx_set_error("gnx_gemm: workspace of %zu bytes, the split weight images need %zu", ws_bytes, p.image_bytes);
+    return GNX_E_WORKSPACE;
   }
-  g.nseg = nseg;
-  g.M = M;
-  g.N = N;
-  g.bias = bias;
-  g.mask = mask;
-  g.ldmask = ldmask;
-  g.C = C;
-  g.ldc = ldc;
-  g.relu = (flags & GNX_GEMM_RELU) ? 1 : 0;
-  g.row_index = row_index;
-  g.tile_info = tile_info;
-  g.ntiles = ntiles;
-  const int epi = mask ? EPI_MASK : ((flags & GNX_GEMM_ACCUMULATE) ? EPI_ACCUM : EPI_PLAIN);
-  dim3 grid((unsigned)(tile_info ? max_tiles : gnx_cdiv(M, BM)), (unsigned)gnx_cdiv(N, BN));
-  g.ny = (int)grid.y;
-  if (h->opt[GNX_OPT_GEMM_MID] != 0 && M < 4096 && gnx_cdiv(M, BM) * (int64_t)grid.y <= 48) {  // (a grouped call's
-    // max_tiles is an upper bound with one partial tile per class: the row count decides)
-    // few 128 x 128 tiles: 16 x 16 patches on many workgroups instead (see k_gemm_mid)
-    double ktot = 0.0;
-    for (int q = 0; q < nseg; ++q) ktot += g.seg[q].k;
-    gnx_prof_scope prof(h, GNX_K_GEMM_SMALL, 4.0 * M * (ktot + N) + 4.0 * N * ktot, 2.0 * (double)M * N * ktot, 0.0);
-    const dim3 gm((unsigned)(tile_info ? max_tiles * 8 : gnx_cdiv(M, MID_T)), (unsigned)gnx_cdiv(N, MID_T));
-    epi_dispatch(bt, epi, [&](auto BT, auto EPI) { hipLaunchKernelGGL((k_gemm_mid<BT, EPI>), gm, dim3(256), 0, h->stream, g); });
+  GNX_CHECK_ARG(!p.images || aligned16(ws), "gnx_gemm: workspace must be 16-byte aligned");
+  if (p.kernel == GNX_GEMM_KERNEL_NONE && p.prof_id == GNX_K_NONE) return GNX_OK;
+
+  const int relu = (flags & GNX_GEMM_RELU) ? 1 : 0;
+  __bf16* const images = reinterpret_cast<__bf16*>(ws);
+  gemm_args g = {{},      nseg, M, N, bias, mask, ldmask, C, ldc, relu, row_index, tile_info, ntiles, p.ny, images, p.Npad,
+                 p.Kpad, {},   p.Kpad / BK};  // the tiled kernels and k_gemm_mid
+  split_args sa = {{}, {}, nseg, N, p.Npad, p.Kpad, p.classes, p.frag, images};
+  for (int s = 0; s < MAX_SEGS; ++s) {
+    seg_dev d = {nullptr, nullptr, nullptr, 0, 0, 0, 0, 0, 0};
+    if (s < nseg) {
+      const gnx_gemm_seg& in = segs[s];
+      const int64_t cs = cls_strides ? cls_strides[s] : 0;
+      d = seg_dev{in.a, in.rowscale, in.b, in.lda, in.ldb, cs, in.k, plan_vec_a(in), plan_vec_b(in, cs)};
+    }
+    g.seg[s] = sa.seg[s] = d;
+    g.koff[s] = p.koff[s];
+  }
+  for (int s = 0; s <= MAX_SEGS; ++s) sa.koff[s] = p.koff[s];
+  const gnx_gemm_seg& s0 = segs[0];  // the one segment of the weights-stationary kernels and of k_gemm_small_batched
+  const ws_args w = {s0.a, s0.lda, s0.b, s0.ldb, M, N, s0.k, bias, mask, ldmask, C, ldc, relu, p.row_tiles};
+
+  gnx_prof_scope prof(h, p.prof_id, p.bytes, p.flops, p.mfma);
+  if (p.run_split) {
+    const dim3 gs((unsigned)gnx_cdiv((int64_t)sa.D * sa.Npad * (sa.Kpad / 8), 256));
+    if (p.bt)
+      hipLaunchKernelGGL(k_split_weights<true>, gs, dim3(256), 0, h->stream, sa);
+    else
+      hipLaunchKernelGGL(k_split_weights<false>, gs, dim3(256), 0, h->stream, sa);
+  }
+  if (p.stop_after_split || p.kernel == GNX_GEMM_KERNEL_NONE) {
     GNX_LAUNCH_CHECK();
     return GNX_OK;
   }
-  // k_gemm3 / k_gemm3p: persistent workgroups, two per CU, count a multiple of 8 * ny (the XCD-aware tile walk needs it)
-  auto persistent_grid = [&](unsigned row_tiles) {
-    unsigned g3 = (unsigned)(gnx_cdiv((int64_t)row_tiles, 8) * 8 * grid.y);
-    const unsigned unit = 8u * grid.y;
-    unsigned slots = 2u * (unsigned)(h->num_cus > 0 ? h->num_cus : 256);
-    slots = slots / unit * unit;
-    if (slots < unit) slots = unit;
-    return g3 > slots ? slots : g3;
-  };
-  dim3 grid3(persistent_grid(grid.x));
-  bool pipe = h->opt[GNX_OPT_GEMM_PIPE] != 0;  // decided below: needs >= G3P_MIN_KTILES K-tiles per output tile
-  bool as3 = false;                            // decided below: one segment, 4 K-tiles, >= 2 column tiles
-  bool mi3 = false;                            // pipelined kernel with 96-row tiles
-  bool vec = true;
-  for (int s = 0; s < nseg; ++s)
-    vec = vec && g.seg[s].vec_a && g.seg[s].vec_b && (g.seg[s].k % 4 == 0) && (bt || (N % 4 == 0));
-  // Split-operand path (M >= 4096, >= 2 K-tiles, no row scale): needs the caller's workspace for the split weight
-  // images (gnx_gemm_workspace_bytes).  Row-scaled segments (the 4-segment post-layer-0 of hub-heavy batches) and
-  // small, launch-bound problems stay on the fp32-MFMA kernel, and so does a call without a workspace.
-  const size_t need = gemm_split_bytes(h, nseg, segs, cls_strides, num_classes, M, N, mask, flags, tile_info != nullptr);
-  const bool split = need > 0 && ws != nullptr;
-  if (split && ws_bytes < need) {
-    gnx_set_error("gnx_gemm: workspace of %zu bytes, the split weight images need %zu", ws_bytes, need);
-    return GNX_E_WORKSPACE;
-  }
-  GNX_CHECK_ARG(!split || aligned16(ws), "gnx_gemm: workspace must be 16-byte aligned");
-  double ktot = 0.0;
-  for (int q = 0; q < nseg; ++q) ktot += g.seg[q].k;
-  const double fl = 2.0 * (double)M * N * ktot;
-  gnx_prof_scope prof(h, GNX_K_GEMM_TILED, 4.0 * M * (ktot + N) + ((mask || (flags & GNX_GEMM_ACCUMULATE)) ? 4.0 * M * N : 0.0) +
-                                               4.0 * N * ktot * (num_classes > 0 ? num_classes : 1), fl, split ? 6.0 * fl : 0.0);
-  if (split) {
-    split_args sa;
-    for (int q = 0; q < MAX_SEGS; ++q) sa.seg[q] = g.seg[q];
-    int kp = 0;
-    for (int q = 0; q < nseg; ++q) {
-      sa.koff[q] = kp;
-      kp += (int)gnx_cdiv((int64_t)g.seg[q].k, BK) * BK;
+  const dim3 grid(p.grid_x, p.grid_y), block(p.block);
+  // one launch per kernel kind, instantiated where COND holds; LDS_LIMIT > 0: raised on the kernel's first launch
+#define GEMM_CASE(KIND, COND, KERNEL, ARGS, LDS_LIMIT)                                               \
+  case KIND:                                                                                         \
+    if constexpr (COND) {                                                                            \
+      if constexpr ((LDS_LIMIT) > 0)                                                                 \
+        if (const hipError_t e = gnx_raise_lds_limit<&KERNEL>(LDS_LIMIT); e != hipSuccess) return e; \
+      hipLaunchKernelGGL((KERNEL), grid, block, p.lds, h->stream, ARGS);                             \
+    }                                                                                                \
+    return hipSuccess
+  const hipError_t lds_limit = epi_dispatch(p.bt, p.epi, [&](auto BT, auto EPI) -> hipError_t {
+    constexpr bool no_rmw = EPI != EPI_ACCUM;  // the predicate-free forms have no accumulate epilogue (the plan never asks)
+    switch (p.kernel) {
+      GEMM_CASE(GNX_GEMM_KERNEL_WS, true, (k_gemm_ws<BT, EPI>), w, 160 * 1024);
+      GEMM_CASE(GNX_GEMM_KERNEL_WS3, true, (k_gemm_ws3<BT, EPI, false, 8>), w, 160 * 1024);
+      GEMM_CASE(GNX_GEMM_KERNEL_WS3_FAST8, no_rmw, (k_gemm_ws3<BT, EPI, true, 8>), w, 160 * 1024);
+      GEMM_CASE(GNX_GEMM_KERNEL_WS3_FAST4, no_rmw, (k_gemm_ws3<BT, EPI, true, 4>), w, 64 * 1024);
+      GEMM_CASE(GNX_GEMM_KERNEL_MID, true, (k_gemm_mid<BT, EPI>), g, 0);
+      GEMM_CASE(GNX_GEMM_KERNEL_AS3, true, (k_gemm_as3<EPI>), g, (int)AS_LDS);
+      GEMM_CASE(GNX_GEMM_KERNEL_GEMM3P_96, true, (k_gemm3p<EPI, 3>), g, 0);
+      GEMM_CASE(GNX_GEMM_KERNEL_GEMM3P_128, true, (k_gemm3p<EPI, 4>), g, 0);
+      GEMM_CASE(GNX_GEMM_KERNEL_GEMM3, true, (k_gemm3<EPI>), g, 0);
+      GEMM_CASE(GNX_GEMM_KERNEL_TILED_VEC, true, (k_gemm<BT, EPI, true>), g, 0);
+      GEMM_CASE(GNX_GEMM_KERNEL_TILED_GENERIC, true, (k_gemm<BT, EPI, false>), g, 0);
+      default: {  // GNX_GEMM_KERNEL_SMALL: a batch of one
+        small_batch_args b;
+        for (int i = 0; i < GNX_SMALL_BATCH; ++i)
+          b.p[i] = {w.A, w.lda, w.B, w.ldb, bias, C, ldc, (int32_t)M, N, w.K,
+                    (p.bt ? GNX_SB_B_TRANS : 0) | (relu ? GNX_SB_RELU : 0) | ((flags & GNX_GEMM_ACCUMULATE) ? GNX_SB_ACCUMULATE : 0)};
+        b.n = 1;
+        hipLaunchKernelGGL(k_gemm_small_batched, grid, block, 0, h->stream, b);
+        return hipSuccess;
+      }
     }
-    for (int q = nseg; q <= MAX_SEGS; ++q) sa.koff[q] = kp;
-    sa.nseg = nseg;
-    sa.N = N;
-    sa.Npad = (int)gnx_cdiv((int64_t)N, BN) * BN;
-    sa.Kpad = kp;
-    sa.D = num_classes > 0 ? num_classes : 1;
-    pipe = pipe && kp / BK >= G3P_MIN_KTILES;
-    if (pipe) {  // tile height of the pipelined kernel: the caller's (grouped: what its tile table was built with) or ours
-      const int rows = tile_info ? (tile_rows ? tile_rows : BM) : (tile_rows ? tile_rows : gemm_pipe_tile_rows(h, M, N));
-      mi3 = rows == 96;
-      if (!tile_info) grid3 = dim3(persistent_grid((unsigned)gnx_cdiv(M, (int64_t)rows)));
-    }
-    as3 = h->opt[GNX_OPT_GEMM_AS] != 0 && nseg == 1 && kp == 4 * BK && N >= 2 * BN && N % BN == 0 &&
-          (double)M * (double)(ldc > ldmask ? ldc : ldmask) + (double)N < 1073741824.0 && aligned16(C) && ldc % 4 == 0 &&
-          (mask == nullptr || (aligned16(mask) && ldmask % 4 == 0)) && (bias == nullptr || aligned16(bias));
-    sa.frag = (pipe || as3) ? 1 : 0;
-    sa.out = reinterpret_cast<__bf16*>(ws);
-    const int64_t items = (int64_t)sa.D * sa.Npad * (sa.Kpad / 8);
-    if (flags & GNX_GEMM_PRESPLIT) {
-      // the caller ran this very split before (GNX_GEMM_SPLIT_ONLY, same arguments)
-    } else if (bt)
-      hipLaunchKernelGGL(k_split_weights<true>, dim3((unsigned)gnx_cdiv(items, 256)), dim3(256), 0, h->stream, sa);
-    else
-      hipLaunchKernelGGL(k_split_weights<false>, dim3((unsigned)gnx_cdiv(items, 256)), dim3(256), 0, h->stream, sa);
-    if (split_only) {
-      GNX_LAUNCH_CHECK();
-      return GNX_OK;
-    }
-    g.bsplit = sa.out;
-    g.Npad = sa.Npad;
-    g.Kpad = sa.Kpad;
-    for (int q = 0; q < MAX_SEGS; ++q) g.koff[q] = sa.koff[q];
-    g.steps = sa.Kpad / BK;
-  }
-  if (split_only) return GNX_OK;  // (this call takes a kernel that needs no images)
-  const hipError_t lds_limit = epi_dispatch(bt, epi, [&](auto BT, auto EPI) {
-    if (split && as3) {
-      const hipError_t e = gnx_raise_lds_limit<&k_gemm_as3<EPI>>((int)AS_LDS);
-      if (e != hipSuccess) return e;
-      const unsigned ga = tile_info ? (unsigned)(2 * max_tiles) : (unsigned)gnx_cdiv(M, AS_BM);
-      hipLaunchKernelGGL((k_gemm_as3<EPI>), dim3(ga), dim3(256), AS_LDS, h->stream, g);
-    } else if (split && pipe && mi3) {
-      hipLaunchKernelGGL((k_gemm3p<EPI, 3>), grid3, dim3(256), G3P_LDS(3), h->stream, g);
-    } else if (split && pipe) {
-      hipLaunchKernelGGL((k_gemm3p<EPI, 4>), grid3, dim3(256), G3P_LDS(4), h->stream, g);
-    } else if (split) {
-      hipLaunchKernelGGL((k_gemm3<EPI>), grid3, dim3(256), 0, h->stream, g);
-    } else if (vec) {
-      hipLaunchKernelGGL((k_gemm<BT, EPI, true>), grid, dim3(256), 0, h->stream, g);
-    } else {
-      hipLaunchKernelGGL((k_gemm<BT, EPI, false>), grid, dim3(256), 0, h->stream, g);
-    }
-    return hipSuccess;
   });
+#undef GEMM_CASE
   GNX_HIP(lds_limit);
   GNX_LAUNCH_CHECK();
   return GNX_OK;
@@ -2263,7 +2076,34 @@ extern "C" int32_t gnx_gemm(gnx_handle* h, int32_t nseg, const gnx_gemm_seg* seg
 extern "C" size_t gnx_gemm_workspace_bytes(gnx_handle* h, int32_t nseg, const gnx_gemm_seg* segs,
                                            const int64_t* cls_strides, int32_t num_classes, int64_t M, int32_t N,
                                            const float* mask, int32_t flags, int32_t grouped) {
-  return gemm_split_bytes(h, nseg, segs, cls_strides, num_classes, M, N, mask, flags, grouped != 0);
+  if (h == nullptr || segs == nullptr || nseg < 1 || nseg > MAX_SEGS || M < 0 || N <= 0) return 0;
+  static const int32_t a_table = 0;  // (only its NULL-ness is looked at)
+  return gemm_plan_of(nseg, segs, cls_strides, num_classes, M, N, nullptr, mask, N, nullptr, N, flags, grouped ? &a_table : nullptr,
+                      1, nullptr, 0, h->opt, h->num_cus)
+      .image_bytes;
+}
+
+extern "C" int32_t gnx_gemm_tile_rows(gnx_handle* h, int64_t M, int32_t N) {
+  if (h == nullptr || M <= 0 || N <= 0) return 128;
+  return gemm_plan_tile_rows(M, N, h->opt[GNX_OPT_GEMM_TILE_ROWS], h->num_cus > 0 ? h->num_cus : 256);
+}
+
+extern "C" int32_t gnx_gemm_plan(gnx_handle* h, int32_t nseg, const gnx_gemm_seg* segs, const int64_t* cls_strides,
+                                 int32_t num_classes, int64_t M, int32_t N, const float* bias, const float* mask, int64_t ldmask,
+                                 float* C, int64_t ldc, int32_t flags, const int32_t* row_index, const int32_t* tile_info,
+                                 const int32_t* ntiles, int64_t max_tiles, void* ws, size_t ws_bytes, int32_t tile_rows,
+                                 gnx_gemm_plan_info* out) {
+  GNX_CHECK_ARG(out, "gnx_gemm_plan: NULL argument");
+  const bool grouped = cls_strides || row_index || tile_info || ntiles;
+  GNX_CHECK_ARG(!grouped || (cls_strides && row_index && tile_info && ntiles && max_tiles > 0 && num_classes >= 1 && num_classes <= 4096),
+                "gnx_gemm_plan: grouped call with a NULL array, max_tiles <= 0 or num_classes not in [1,4096]");
+  const int32_t st = gemm_check(h, nseg, segs, M, N, mask, ldmask, C, ldc, flags, tile_rows);
+  if (st != GNX_OK) return st;
+  (void)ws_bytes;
+  const gemm_plan p = gemm_plan_of(nseg, segs, cls_strides, grouped ? num_classes : 1, M, N, bias, mask, ldmask, C, ldc, flags,
+                                   tile_info, max_tiles, ws, tile_rows, h->opt, h->num_cus);
+  *out = gnx_gemm_plan_info{p.kernel, p.tile_rows, p.grid_x, p.grid_y, p.block, p.run_split ? 1 : 0, p.image_bytes};
+  return GNX_OK;
 }
 
 extern "C" int32_t gnx_gemm_grouped(gnx_handle* h, int32_t nseg, const gnx_gemm_seg* segs, const int64_t* cls_strides,
@@ -2288,4 +2128,3 @@ extern "C" int32_t gnx_gemm_grouped_rows(gnx_handle* h, int32_t nseg, const gnx_
   return gemm_launch(h, nseg, segs, cls_strides, num_classes, M, N, bias, mask, ldmask, C, ldc, flags, row_index,
                      tile_info, ntiles, max_tiles, ws, ws_bytes, tile_rows);
 }
-

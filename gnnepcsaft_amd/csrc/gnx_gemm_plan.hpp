@@ -1,0 +1,199 @@
+// Which kernel a gnx_gemm / gnx_gemm_grouped / gnx_gemm_grouped_rows call takes, decided ONCE, on the host, without HIP:
+// gemm_plan_of() turns a call's arguments into a gemm_plan, gemm_launch (gnx_gemm.hip) checks the arguments, asks for the
+// plan and launches from it, and gnx_gemm_workspace_bytes / gnx_gemm_tile_rows / gnx_gemm_plan return its fields.  Plain
+// C++17 so that tests/gemm_plan_probe.cpp can pin the decision table on a machine without a GPU.  Pointers are looked at
+// for NULL-ness and 16-byte alignment only.  No heap use: this runs once per product, > 100 times per step.
+//
+// The decision table, in the order gemm_plan_of takes it, is in DESIGN.md section 4 ("Which product kernel a call takes").
+#pragma once
+#include <cstddef>
+#include <cstdint>
+
+#include "gnx.h"
+
+// Tile geometry the decision depends on; gnx_gemm.hip asserts every value against the kernels' own constants.
+constexpr int PLAN_MAX_SEGS = 4;
+constexpr int PLAN_BM = 128, PLAN_BN = 128, PLAN_BK = 32;  // tiled kernels
+constexpr int PLAN_WS_BM = 64;                             // k_gemm_ws, k_gemm_ws3 with 8 waves (4 waves: half of it)
+constexpr size_t PLAN_WS_LDS = 4 * (128 * 132 + 2 * 64 * 132);  // k_gemm_ws: the weight image and two A tiles, row stride 132
+constexpr size_t PLAN_WS3_LDS8 = 2 * 3 * 64 * 272;         // k_gemm_ws3, 8 waves: two stages of three bf16 images of a tile
+constexpr size_t PLAN_WS3_LDS4 = 64 * 1024;                // 4 waves: at least what the NN weight staging image needs
+constexpr int PLAN_G3P_MIN_KTILES = 8;
+constexpr size_t plan_g3p_lds(int mi) { return (size_t)(2 * 3 * 32 * mi * 80 + 2 * 32 * mi * 4); }
+constexpr int PLAN_AS_BM = 64;
+constexpr size_t PLAN_AS_LDS = 3 * 64 * 272 + 2 * 64 * 4;
+constexpr int PLAN_PATCH = 16;           // k_gemm_mid and k_gemm_small_batched: 16 x 16 outputs per workgroup
+constexpr int PLAN_WGS_PER_CU = 2;       // persistent workgroups of k_gemm3 / k_gemm3p
+constexpr int64_t PLAN_SPLIT_MIN_ROWS = 4096, PLAN_WS_MIN_ROWS = 8192;
+
+enum { PLAN_EPI_PLAIN = 0, PLAN_EPI_ACCUM = 1, PLAN_EPI_MASK = 2 };
+
+struct gemm_plan {
+  int kernel = GNX_GEMM_KERNEL_NONE;  // GNX_GEMM_KERNEL_*: with stop_after_split, the kernel the images are for
+  bool bt = false;
+  int epi = PLAN_EPI_PLAIN;
+  unsigned grid_x = 0, grid_y = 1, block = 256;
+  size_t lds = 0;          // dynamic LDS bytes
+  int tile_rows = 0;       // rows per workgroup tile
+  int row_tiles = 0;       // ws_args.ntiles (weights-stationary kernels)
+  int ny = 1;              // column tiles of 128
+  size_t image_bytes = 0;  // what gnx_gemm_workspace_bytes answers (whether or not this call brought a workspace)
+  bool images = false;     // the kernel reads split weight images: image_bytes > 0 and a workspace
+  int Npad = 0, Kpad = 0, koff[PLAN_MAX_SEGS + 1] = {0, 0, 0, 0, 0}, frag = 0, classes = 1;
+  bool run_split = false;         // launch k_split_weights first (images, and not GNX_GEMM_PRESPLIT)
+  bool stop_after_split = false;  // GNX_GEMM_SPLIT_ONLY
+  int prof_id = GNX_K_NONE;
+  double bytes = 0.0, flops = 0.0, mfma = 0.0;
+};
+
+static inline int64_t plan_cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
+static inline bool plan_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+static inline bool plan_vec_a(const gnx_gemm_seg& s) { return plan_aligned16(s.a) && s.lda % 4 == 0; }
+static inline bool plan_vec_b(const gnx_gemm_seg& s, int64_t cls_stride) {
+  return plan_aligned16(s.b) && s.ldb % 4 == 0 && cls_stride % 4 == 0;
+}
+static inline int plan_kpad(int64_t k) { return (int)(plan_cdiv(k, PLAN_BK) * PLAN_BK); }
+
+// Bytes of the split weight images of `classes` weight sets with N columns and kpad = sum of plan_kpad(k) over the
+// segments: N padded to 128, three bf16 pieces.
+static inline size_t gemm_plan_image_bytes(int64_t classes, int64_t N, int64_t kpad) {
+  return (size_t)((classes > 0 ? classes : 1) * 3 * (plan_cdiv(N, PLAN_BN) * PLAN_BN) * kpad) * 2;
+}
+
+// Row-tile height of the pipelined tiled product for M rows x N columns: 96 where that shortens the longest workgroup's
+// walk (rounds x tile height; persistent workgroups, PLAN_WGS_PER_CU per CU), else 128 (ties keep 128, the most measured
+// shape).  forced = GNX_OPT_GEMM_TILE_ROWS.
+static inline int gemm_plan_tile_rows(int64_t M, int32_t N, int forced, int cus) {
+  if (forced == 96 || forced == 128) return forced;
+  const int64_t ny = plan_cdiv(N, PLAN_BN), slots = (int64_t)PLAN_WGS_PER_CU * cus;
+  const int64_t c128 = plan_cdiv(plan_cdiv(M, 128) * ny, slots) * 128, c96 = plan_cdiv(plan_cdiv(M, 96) * ny, slots) * 96;
+  return c96 < c128 ? 96 : 128;
+}
+
+// Workgroups of k_gemm3 / k_gemm3p for row_tiles x ny tiles: PLAN_WGS_PER_CU per CU at the most, a multiple of 8 * ny
+// (the XCD-aware tile walk needs it).
+static inline unsigned gemm_plan_persistent_grid(int64_t row_tiles, unsigned ny, int cus) {
+  const unsigned unit = 8u * ny, all = (unsigned)(plan_cdiv(row_tiles, 8) * unit);
+  unsigned slots = (unsigned)(PLAN_WGS_PER_CU * cus) / unit * unit;
+  if (slots < unit) slots = unit;
+  return all > slots ? slots : all;
+}
+
+// Arguments as gemm_launch's (tile_info == NULL: an ungrouped call; ws is the caller's workspace or NULL); opt =
+// gnx_handle::opt, num_cus <= 0 counts as 256.  The arguments have passed gemm_launch's checks.
+static inline gemm_plan gemm_plan_of(int32_t nseg, const gnx_gemm_seg* segs, const int64_t* cls_strides, int32_t num_classes,
+                                     int64_t M, int32_t N, const float* bias, const float* mask, int64_t ldmask, const float* C,
+                                     int64_t ldc, int32_t flags, const int32_t* tile_info, int64_t max_tiles, const void* ws,
+                                     int32_t tile_rows, const int* opt, int num_cus) {
+  gemm_plan p;
+  p.bt = (flags & GNX_GEMM_B_TRANS) != 0;
+  const bool accumulate = (flags & GNX_GEMM_ACCUMULATE) != 0;
+  p.epi = mask ? PLAN_EPI_MASK : (accumulate ? PLAN_EPI_ACCUM : PLAN_EPI_PLAIN);
+  if (M == 0) return p;
+  const int cus = num_cus > 0 ? num_cus : 256;
+  const bool grouped = tile_info != nullptr, split_only = (flags & GNX_GEMM_SPLIT_ONLY) != 0;
+  const bool out_aligned = plan_aligned16(C) && ldc % 4 == 0 && (mask == nullptr || (plan_aligned16(mask) && ldmask % 4 == 0));
+  double ktot = 0.0;
+  for (int s = 0; s < nseg; ++s) ktot += segs[s].k;
+  p.flops = 2.0 * (double)M * N * ktot;
+  const double io = 4.0 * M * (ktot + N), rmw = (mask || accumulate) ? 4.0 * M * N : 0.0;
+
+  // The weights-stationary shape: one segment with M >= 8192, 32 <= K, N <= 128 (multiples of 4), aligned operands, no row
+  // scale and not mask + accumulate (ungrouped calls only).
+  const gnx_gemm_seg& s0 = segs[0];
+  if (!grouped && nseg == 1 && M >= PLAN_WS_MIN_ROWS && s0.rowscale == nullptr && s0.k >= 32 && s0.k <= 128 && N >= 32 &&
+      N <= 128 && s0.k % 4 == 0 && N % 4 == 0 && plan_vec_a(s0) && plan_vec_b(s0, 0) && !(mask != nullptr && accumulate)) {
+    if (split_only) return p;  // (the weights live in registers or LDS there: no images)
+    const bool split = opt[GNX_OPT_GEMM_SPLIT] != 0;
+    const int fast = (split && p.epi != PLAN_EPI_ACCUM && N == 128 && out_aligned) ? opt[GNX_OPT_GEMM_WS_FAST] : 0;
+    p.kernel = !split ? GNX_GEMM_KERNEL_WS : fast == 2 ? GNX_GEMM_KERNEL_WS3_FAST4 : fast ? GNX_GEMM_KERNEL_WS3_FAST8 : GNX_GEMM_KERNEL_WS3;
+    const int waves = fast == 2 ? 4 : 8;
+    p.tile_rows = PLAN_WS_BM * waves / 8;
+    p.row_tiles = (int)plan_cdiv(M, p.tile_rows);
+    const int wgs = cus * (8 / waves);
+    p.grid_x = (unsigned)(p.row_tiles < wgs ? p.row_tiles : wgs);
+    p.block = 64u * waves;
+    p.lds = !split ? PLAN_WS_LDS : waves == 4 ? PLAN_WS3_LDS4 : PLAN_WS3_LDS8;
+    p.prof_id = GNX_K_GEMM_WS;
+    p.bytes = io + rmw + 4.0 * N * ktot;
+    p.mfma = split ? 6.0 * p.flops : 0.0;
+    return p;
+  }
+  if (split_only && M < PLAN_SPLIT_MIN_ROWS) return p;  // (no split path below 4096 rows)
+  if (!grouped && nseg == 1 && M <= 256 && mask == nullptr && segs[0].rowscale == nullptr && opt[GNX_OPT_GEMM_MID] == 0) {
+    // (k_gemm_mid computes the same k-ordered chain with 16-byte staging loads and the next chunk prefetched: 3-4 us
+    // instead of 7-10 us for a 20-row product)
+    p.kernel = GNX_GEMM_KERNEL_SMALL;
+    p.tile_rows = PLAN_PATCH;
+    p.grid_x = (unsigned)(plan_cdiv(M, PLAN_PATCH) * plan_cdiv(N, PLAN_PATCH));
+    p.prof_id = GNX_K_GEMM_SMALL;
+    p.bytes = 4.0 * ((double)M * (segs[0].k + N) + (double)N * segs[0].k);
+    return p;
+  }
+  p.ny = (int)plan_cdiv(N, PLAN_BN);
+  if (opt[GNX_OPT_GEMM_MID] != 0 && M < PLAN_SPLIT_MIN_ROWS && plan_cdiv(M, PLAN_BM) * p.ny <= 48) {
+    // few 128 x 128 tiles: 16 x 16 patches on many workgroups instead (a grouped call's max_tiles is an upper bound with
+    // one partial tile per class, so the row count decides; every 128-row tile of its table is 8 patches high)
+    p.kernel = GNX_GEMM_KERNEL_MID;
+    p.tile_rows = PLAN_PATCH;
+    p.grid_x = (unsigned)(grouped ? max_tiles * (PLAN_BM / PLAN_PATCH) : plan_cdiv(M, PLAN_PATCH));
+    p.grid_y = (unsigned)plan_cdiv(N, PLAN_PATCH);
+    p.prof_id = GNX_K_GEMM_SMALL;
+    p.bytes = io + 4.0 * N * ktot;
+    return p;
+  }
+
+  // Tiled kernels.  The split-operand ones (M >= 4096, >= 2 K-tiles, no row scale, aligned operands) read split weight
+  // images from the caller's workspace; row-scaled segments (the 4-segment post-layer 0 of hub-heavy batches), odd shapes
+  // and a call without a workspace stay on the exact-fp32 MFMA kernel.
+  p.classes = num_classes > 0 ? num_classes : 1;
+  bool vec = true, can_split = opt[GNX_OPT_GEMM_SPLIT] != 0 && M >= PLAN_SPLIT_MIN_ROWS;
+  for (int s = 0; s < nseg; ++s) {
+    const gnx_gemm_seg& in = segs[s];
+    const bool aligned = plan_vec_a(in) && plan_vec_b(in, cls_strides ? cls_strides[s] : 0) && in.k % 4 == 0 && (p.bt || N % 4 == 0);
+    vec = vec && aligned;
+    can_split = can_split && aligned && in.rowscale == nullptr && in.k > 0;
+    p.koff[s] = p.Kpad;
+    p.Kpad += plan_kpad(in.k);
+  }
+  for (int s = nseg; s <= PLAN_MAX_SEGS; ++s) p.koff[s] = p.Kpad;
+  p.Npad = p.ny * PLAN_BN;
+  const int ktiles = p.Kpad / PLAN_BK;
+  if (can_split && ktiles >= 2) p.image_bytes = gemm_plan_image_bytes(p.classes, N, p.Kpad);
+  p.images = p.image_bytes > 0 && ws != nullptr;
+  p.prof_id = GNX_K_GEMM_TILED;
+  p.bytes = io + rmw + 4.0 * N * ktot * p.classes;
+  p.mfma = p.images ? 6.0 * p.flops : 0.0;
+  const int64_t row_tiles = grouped ? max_tiles : plan_cdiv(M, PLAN_BM);
+  if (!p.images) {
+    if (split_only) return p;  // (this call takes a kernel that needs no images)
+    p.kernel = vec ? GNX_GEMM_KERNEL_TILED_VEC : GNX_GEMM_KERNEL_TILED_GENERIC;
+    p.tile_rows = PLAN_BM;
+    p.grid_x = (unsigned)row_tiles;
+    p.grid_y = (unsigned)p.ny;
+    return p;
+  }
+  p.run_split = (flags & GNX_GEMM_PRESPLIT) == 0;  // (else the caller ran this very split before: SPLIT_ONLY, same arguments)
+  p.stop_after_split = split_only;
+  const bool as3 = opt[GNX_OPT_GEMM_AS] != 0 && nseg == 1 && p.Kpad == 4 * PLAN_BK && N >= 2 * PLAN_BN && N % PLAN_BN == 0 &&
+                   (double)M * (double)(ldc > ldmask ? ldc : ldmask) + (double)N < 1073741824.0 && out_aligned &&
+                   (bias == nullptr || plan_aligned16(bias));
+  const bool pipe = opt[GNX_OPT_GEMM_PIPE] != 0 && ktiles >= PLAN_G3P_MIN_KTILES;
+  p.frag = (pipe || as3) ? 1 : 0;
+  if (as3) {  // one 64-row tile per workgroup, all column tiles
+    p.kernel = GNX_GEMM_KERNEL_AS3;
+    p.tile_rows = PLAN_AS_BM;
+    p.grid_x = (unsigned)(grouped ? max_tiles * (PLAN_BM / PLAN_AS_BM) : plan_cdiv(M, PLAN_AS_BM));
+    p.lds = PLAN_AS_LDS;
+  } else if (pipe) {  // tile height: a grouped call's is what its tile table was built with (the caller's, or 128)
+    p.tile_rows = tile_rows ? tile_rows : grouped ? PLAN_BM : gemm_plan_tile_rows(M, N, opt[GNX_OPT_GEMM_TILE_ROWS], cus);
+    p.kernel = p.tile_rows == 96 ? GNX_GEMM_KERNEL_GEMM3P_96 : GNX_GEMM_KERNEL_GEMM3P_128;
+    p.grid_x = gemm_plan_persistent_grid(grouped ? row_tiles : plan_cdiv(M, p.tile_rows), (unsigned)p.ny, cus);
+    p.lds = plan_g3p_lds(p.tile_rows / 32);
+  } else {
+    p.kernel = GNX_GEMM_KERNEL_GEMM3;
+    p.tile_rows = PLAN_BM;
+    p.grid_x = gemm_plan_persistent_grid(row_tiles, (unsigned)p.ny, cus);
+  }
+  return p;
+}

@@ -7,6 +7,7 @@
 // /root/reference/gnnepcsaft/train/models.py:445-457 (restructured as DESIGN.md §4 describes: node-level P/Q products +
 // 60-row bond table for pre-layer 0, per-degree-class effective weights for post-layer 0, lin o last post layer merged).
 #include "gnx_common.hpp"
+#include "gnx_gemm_plan.hpp"
 
 #include <algorithm>
 #include <vector>
@@ -84,12 +85,12 @@ int32_t on_side(gnx_handle* h, int which, bool enabled, F body) {
 // gnx_pna_conv_fwd): forward: post-layer 0; backward: dA and dx.
 static size_t align256(size_t v) { return (v + 255) / 256 * 256; }
 static void pna_ws_sizes(int32_t T, int32_t F, int32_t D, size_t& scratch, size_t& post0, size_t& grouped, size_t& dx) {
-  auto pad = [](int64_t v, int64_t m) { return (v + m - 1) / m * m; };
-  grouped = align256((size_t)(D > 0 ? D : 1) * 3 * pad(4 * (int64_t)F, 128) * pad(F, 32) * 2);
-  dx = align256((size_t)3 * pad(F, 128) * (3 * pad(F, 32)) * 2);
-  const size_t lin = (size_t)3 * pad((int64_t)T * F, 128) * pad((int64_t)T * F, 32) * 2;  // lin / merged product, H x H
+  const int64_t H = (int64_t)T * F;
+  grouped = align256(gemm_plan_image_bytes(D, 4 * (int64_t)F, plan_kpad(F)));
+  dx = align256(gemm_plan_image_bytes(1, F, 3 * plan_kpad(F)));
+  const size_t lin = gemm_plan_image_bytes(1, H, plan_kpad(H));  // lin / merged product, H x H
   // forward: post-layer 0 by degree class, z = x W0^T + A Weff(d)^T  (N = F, K = F + 4F)
-  post0 = align256((size_t)(D > 0 ? D : 1) * 3 * pad(F, 128) * (pad(F, 32) + pad(4 * (int64_t)F, 32)) * 2);
+  post0 = align256(gemm_plan_image_bytes(D, F, plan_kpad(F) + plan_kpad(4 * (int64_t)F)));
   scratch = align256(std::max(std::max(grouped, post0), std::max(dx, lin)) + 256);
 }
 

@@ -404,25 +404,31 @@ class _SegArrays(threading.local):
 _SEG_ARRAYS = _SegArrays()
 
 
-def gemm(segs: Sequence[Seg], out: torch.Tensor, *, bias: Optional[torch.Tensor] = None,
-         mask: Optional[torch.Tensor] = None, relu: bool = False, accumulate: bool = False,
-         b_trans: bool = True) -> torch.Tensor:
-    """out[M,N] (+)= act(sum_s (rs_s * A_s) @ B_s(^T) + bias), optionally * (mask > 0).  See gnx_gemm in gnx.h.
+GSeg = Tuple[torch.Tensor, Optional[torch.Tensor], torch.Tensor, int]  # (A view, rowscale|None, B of class 0, stride)
 
-    b_trans=True: B_s is a [N,k] weight view (forward Linear); False: B_s is a [k,N] view (input gradient).
-    """
+
+def _gemm_args(segs, out, dc, bias, mask, relu, accumulate, b_trans, forward_tiles):
+    """Marshals a gemm() (``dc`` None, Seg tuples) or gemm_grouped() (GSeg tuples) call: the arguments of
+    gnx_gemm_grouped_rows / gnx_gemm_plan from the handle to tile_rows (NULL grouping arrays: ungrouped; tile_rows 0: the
+    128-row table), and the workspace tensor they point into (None: the call needs no split weight images)."""
     M, N = out.shape
-    if M == 0:
-        return out
     cptr, ldc = _mat(out, "out")
-    arr = _SEG_ARRAYS.by_len[len(segs)]  # reused: the library copies the descriptors during the call
-    for i, (a, rs, b) in enumerate(segs):
+    n = len(segs)
+    if dc is None:
+        arr, strides = _SEG_ARRAYS.by_len[n], None  # reused: the library copies the descriptors during the call
+    else:
+        arr, strides = (GemmSeg * n)(), (C.c_int64 * n)()
+    for i, sg in enumerate(segs):
+        a, rs, b = sg[0], sg[1], sg[2]
         ap, lda = _mat(a, "A")
         bp, ldb = _mat(b, "B")
-        (am, k), (b0, b1) = a.shape, b.shape
-        if am != M or (b_trans and (b0 != N or b1 != k)) or (not b_trans and (b0 != k or b1 != N)):
-            raise _lib.GnxError(_lib.GNX_E_INVALID, f"gemm segment {i}: A {tuple(a.shape)} B {tuple(b.shape)} "
-                                                    f"out {tuple(out.shape)} b_trans={b_trans}")
+        k = a.size(1)
+        if dc is None:
+            if a.size(0) != M or tuple(b.shape) != ((N, k) if b_trans else (k, N)):
+                raise _lib.GnxError(_lib.GNX_E_INVALID, f"gemm segment {i}: A {tuple(a.shape)} B {tuple(b.shape)} "
+                                                        f"out {tuple(out.shape)} b_trans={b_trans}")
+        else:
+            strides[i] = sg[3]
         e = arr[i]
         e.a, e.lda, e.rowscale = ap, lda, (None if rs is None else rs.data_ptr())
         e.b, e.ldb, e.k = bp, ldb, k
@@ -432,13 +438,31 @@ def gemm(segs: Sequence[Seg], out: torch.Tensor, *, bias: Optional[torch.Tensor]
     lib, h = _lib.load(), handle(out.device)
     # split weight images of the tiled split-operand kernel live in caller-owned scratch (0 bytes for most calls; the
     # split path needs >= 4096 rows, so small products skip the query: host time matters in tiny-kernel phases)
-    nbytes = lib.gnx_gemm_workspace_bytes(h, len(segs), arr, None, 1, M, N, mp, flags, 0) if M >= 4096 else 0
+    D = 1 if dc is None else dc.D
+    nbytes = lib.gnx_gemm_workspace_bytes(h, n, arr, strides, D, M, N, mp, flags, int(dc is not None)) if M >= 4096 else 0
     ws = torch.empty(nbytes, dtype=torch.uint8, device=out.device) if nbytes else None
-    check(lib.gnx_gemm(h, len(segs), arr, M, N, _ptr(bias), mp, ldm, cptr, ldc, flags, _ptr(ws), nbytes))
+    if dc is None:
+        table = (None, None, None, 0)
+    elif forward_tiles:
+        table = (dc.dperm.data_ptr(), dc.tiles_p.data_ptr(), dc.ntiles_p.data_ptr(), dc.max_tiles_p)
+    else:
+        table = (dc.dperm.data_ptr(), dc.tiles.data_ptr(), dc.ntiles.data_ptr(), dc.max_tiles)
+    tile_rows = dc.tile_rows_p if dc is not None and forward_tiles else 0
+    return (h, n, arr, strides, D, M, N, _ptr(bias), mp, ldm, cptr, ldc, flags, *table, _ptr(ws), nbytes, tile_rows), ws
+
+
+def gemm(segs: Sequence[Seg], out: torch.Tensor, *, bias: Optional[torch.Tensor] = None,
+         mask: Optional[torch.Tensor] = None, relu: bool = False, accumulate: bool = False,
+         b_trans: bool = True) -> torch.Tensor:
+    """out[M,N] (+)= act(sum_s (rs_s * A_s) @ B_s(^T) + bias), optionally * (mask > 0).  See gnx_gemm in gnx.h.
+
+    b_trans=True: B_s is a [N,k] weight view (forward Linear); False: B_s is a [k,N] view (input gradient).
+    """
+    if out.size(0) == 0:
+        return out
+    a, _ws = _gemm_args(segs, out, None, bias, mask, relu, accumulate, b_trans, False)
+    check(_lib.load().gnx_gemm(*a[0:3], *a[5:13], *a[17:19]))
     return out
-
-
-GSeg = Tuple[torch.Tensor, Optional[torch.Tensor], torch.Tensor, int]  # (A view, rowscale|None, B of class 0, stride)
 
 
 def gemm_grouped(segs: Sequence[GSeg], out: torch.Tensor, dc: DegreeClasses, *, bias: Optional[torch.Tensor] = None,
@@ -448,32 +472,23 @@ def gemm_grouped(segs: Sequence[GSeg], out: torch.Tensor, dc: DegreeClasses, *, 
     s reads its weight at ``B_s + class * stride_s`` elements (stride 0 = the same weight for every class).
     ``forward_tiles``: walk ``dc.tiles_p`` (the 96- or 128-row table of the pipelined forward product) instead of the
     128-row table."""
-    M, N = out.shape
-    if M == 0:
+    if out.size(0) == 0:
         return out
-    cptr, ldc = _mat(out, "out")
-    arr = (GemmSeg * len(segs))()
-    strides = (C.c_int64 * len(segs))()
-    for i, (a, rs, b, stride) in enumerate(segs):
-        ap, lda = _mat(a, f"A[{i}]")
-        bp, ldb = _mat(b, f"B[{i}]")
-        arr[i].a, arr[i].lda, arr[i].rowscale = ap, lda, _ptr(rs)
-        arr[i].b, arr[i].ldb, arr[i].k = bp, ldb, a.size(1)
-        strides[i] = stride
-    flags = (_lib.GEMM_RELU if relu else 0) | (_lib.GEMM_B_TRANS if b_trans else 0)
-    mp, ldm = (None, 0) if mask is None else _mat(mask, "mask")
-    lib, h = _lib.load(), handle(out.device)
-    nbytes = lib.gnx_gemm_workspace_bytes(h, len(segs), arr, strides, dc.D, M, N, mp, flags, 1)
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=out.device) if nbytes else None
-    if forward_tiles:
-        check(lib.gnx_gemm_grouped_rows(h, len(segs), arr, strides, dc.D, M, N, _ptr(bias), mp, ldm, cptr, ldc, flags,
-                                        dc.dperm.data_ptr(), dc.tiles_p.data_ptr(), dc.ntiles_p.data_ptr(), dc.max_tiles_p,
-                                        _ptr(ws), nbytes, dc.tile_rows_p))
-        return out
-    check(lib.gnx_gemm_grouped(h, len(segs), arr, strides, dc.D, M, N, _ptr(bias), mp, ldm, cptr, ldc, flags,
-                               dc.dperm.data_ptr(), dc.tiles.data_ptr(), dc.ntiles.data_ptr(), dc.max_tiles, _ptr(ws),
-                               nbytes))
+    a, _ws = _gemm_args(segs, out, dc, bias, mask, relu, False, b_trans, forward_tiles)
+    lib = _lib.load()
+    check(lib.gnx_gemm_grouped_rows(*a) if forward_tiles else lib.gnx_gemm_grouped(*a[:19]))
     return out
+
+
+def gemm_plan(segs, out: torch.Tensor, *, bias: Optional[torch.Tensor] = None, mask: Optional[torch.Tensor] = None,
+              relu: bool = False, accumulate: bool = False, b_trans: bool = True, dc: Optional[DegreeClasses] = None,
+              forward_tiles: bool = False) -> Tuple[str, "_lib.GemmPlanInfo"]:
+    """Which kernel gemm() (``dc`` None) or gemm_grouped() takes for these arguments, marshalled as they marshal them:
+    (its name, one of _lib.GEMM_KERNEL_NAMES, and the gnx_gemm_plan_info).  Launches nothing."""
+    a, _ws = _gemm_args(segs, out, dc, bias, mask, relu, accumulate, b_trans, forward_tiles)
+    info = _lib.GemmPlanInfo()
+    check(_lib.load().gnx_gemm_plan(*a, C.byref(info)))
+    return _lib.GEMM_KERNEL_NAMES[info.kernel], info
 
 
 def gemm_wgrad_grouped(dC: torch.Tensor, A: torch.Tensor, dW_cls: torch.Tensor, dc: DegreeClasses) -> None:

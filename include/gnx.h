@@ -291,6 +291,38 @@ int32_t gnx_gemm_grouped_rows(gnx_handle* h, int32_t nseg, const gnx_gemm_seg* s
                               int64_t ldmask, float* C, int64_t ldc, int32_t flags, const int32_t* row_index,
                               const int32_t* tile_info, const int32_t* ntiles, int64_t max_tiles, void* ws,
                               size_t ws_bytes, int32_t tile_rows);
+/* Which kernel such a call takes, without launching anything or touching device memory: the arguments of
+ * gnx_gemm_grouped_rows (row_index = tile_info = ntiles = NULL: an ungrouped call, as gnx_gemm's; tile_rows = 0: 128-row
+ * table, as gnx_gemm_grouped's).  With GNX_GEMM_SPLIT_ONLY `kernel` is the kernel the images are written for, or
+ * GNX_GEMM_KERNEL_NONE where the call does nothing. */
+enum {
+  GNX_GEMM_KERNEL_NONE = 0,          /* nothing is launched (M = 0, or GNX_GEMM_SPLIT_ONLY without images) */
+  GNX_GEMM_KERNEL_TILED_VEC = 1,     /* k_gemm, 16-byte loads */
+  GNX_GEMM_KERNEL_TILED_GENERIC = 2, /* k_gemm, element-wise loads */
+  GNX_GEMM_KERNEL_WS = 3,            /* k_gemm_ws */
+  GNX_GEMM_KERNEL_WS3 = 4,           /* k_gemm_ws3, predicated, 8 waves */
+  GNX_GEMM_KERNEL_WS3_FAST8 = 5,     /* k_gemm_ws3, predicate-free, 8 waves on 64-row tiles */
+  GNX_GEMM_KERNEL_WS3_FAST4 = 6,     /* k_gemm_ws3, predicate-free, 4 waves on 32-row tiles */
+  GNX_GEMM_KERNEL_GEMM3 = 7,         /* k_gemm3 */
+  GNX_GEMM_KERNEL_GEMM3P_96 = 8,     /* k_gemm3p, 96-row tiles */
+  GNX_GEMM_KERNEL_GEMM3P_128 = 9,    /* k_gemm3p, 128-row tiles */
+  GNX_GEMM_KERNEL_AS3 = 10,          /* k_gemm_as3 */
+  GNX_GEMM_KERNEL_MID = 11,          /* k_gemm_mid */
+  GNX_GEMM_KERNEL_SMALL = 12,        /* k_gemm_small_batched */
+  GNX_GEMM_KERNEL_COUNT = 13
+};
+typedef struct {
+  int32_t kernel;                  /* GNX_GEMM_KERNEL_* */
+  int32_t tile_rows;               /* rows per workgroup tile */
+  uint32_t grid_x, grid_y, block;  /* launch dimensions */
+  int32_t runs_split;              /* 1: the call launches k_split_weights first */
+  size_t image_bytes;              /* = gnx_gemm_workspace_bytes */
+} gnx_gemm_plan_info;
+int32_t gnx_gemm_plan(gnx_handle* h, int32_t nseg, const gnx_gemm_seg* segs, const int64_t* cls_strides,
+                      int32_t num_classes, int64_t M, int32_t N, const float* bias, const float* mask, int64_t ldmask,
+                      float* C, int64_t ldc, int32_t flags, const int32_t* row_index, const int32_t* tile_info,
+                      const int32_t* ntiles, int64_t max_tiles, void* ws, size_t ws_bytes, int32_t tile_rows,
+                      gnx_gemm_plan_info* out);
 /* per-class weight gradient: dW_cls[c] (stride dw_cls_stride) += sum over the rows of class c of dC[row]^T A[row]. */
 int32_t gnx_gemm_wgrad_grouped(gnx_handle* h, const float* dC, int64_t lddc, const float* A, int64_t lda, int64_t M,
                                int32_t N, int32_t K, float* dW_cls, int64_t lddw, int64_t dw_cls_stride,

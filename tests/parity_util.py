@@ -38,6 +38,18 @@ def rel_err(a: torch.Tensor, ref: torch.Tensor, floor: float = 0.0) -> float:
     return num / den
 
 
+def gemm_named(segs, out, dc=None, **kw) -> str:
+    """ops.gemm (or, with ``dc``, ops.gemm_grouped) into ``out``; returns the kernel that ops.gemm_plan names for the same
+    arguments under the options in force, so a test can show WHICH kernel produced the values it checks."""
+    from gnnepcsaft_amd import ops
+    name, _ = ops.gemm_plan(segs, out, dc=dc, **kw)
+    if dc is None:
+        ops.gemm(segs, out, **kw)
+    else:
+        ops.gemm_grouped(segs, out, dc, **kw)
+    return name
+
+
 class capture_intermediates:
     """Forward hooks on either model (oracle or native): embed, conv{l}, act{l} (= relu(BatchNorm(conv)), which the
     native BatchNorm kernel produces fused), pool, so that a parity failure localises to a layer.  The hooked tensors

@@ -1,5 +1,5 @@
-"""GPU parity of the tiled split-operand GEMM (k_split_weights + k_gemm3: multi-segment / grouped / wide products with
-M >= 4096) against fp64 torch: both weight layouts, ragged M / K / N, several column tiles, persistent tile walk over
+"""GPU parity of the tiled split-operand GEMM (k_split_weights + k_gemm3 / k_gemm3p / k_gemm_as3: multi-segment / grouped /
+wide products with M >= 4096) against fp64 torch; every case also asks ops.gemm_plan which kernel its call takes: both weight layouts, ragged M / K / N, several column tiles, persistent tile walk over
 more tiles than workgroups, degree-class grouping, all epilogues, strided views; and against the exact-fp32 MFMA
 kernel (GNX_GEMM_SPLIT=0)."""
 import os
@@ -9,7 +9,7 @@ import pytest
 import torch
 
 from gnnepcsaft_amd import _lib
-from tests.parity_util import rel_err
+from tests.parity_util import gemm_named, rel_err
 from tests.test_ops_gpu import _graph, _pack
 
 pytestmark = pytest.mark.gpu
@@ -31,7 +31,8 @@ def wgrad_kernel(request, gpu_device):
 
 @pytest.mark.parametrize("M", [4096, 20037, 70000])
 def test_two_segments_nt_bias_relu(gpu_device, M):
-    """post-layer-0 shape: [x | A] (K = 128 + 512) against W[:, :640], bias + ReLU."""
+    """post-layer-0 shape: [x | A] (K = 128 + 512: 20 K-tiles, the pipelined kernel; one round of workgroups either way, so
+    96-row tiles) against W[:, :640], bias + ReLU."""
     from gnnepcsaft_amd import ops
     torch.manual_seed(M)
     F = 128
@@ -40,14 +41,17 @@ def test_two_segments_nt_bias_relu(gpu_device, M):
     ref = (torch.cat([x, A], 1).double() @ W[:, :5 * F].double().T + b.double()).relu()
     out = torch.full((M, F), float("nan"), device=gpu_device)
     Wd = W.to(gpu_device)
-    ops.gemm([(x.to(gpu_device), None, Wd[:, :F]), (A.to(gpu_device), None, Wd[:, F:5 * F])], out,
-             bias=b.to(gpu_device), relu=True)
+    name = gemm_named([(x.to(gpu_device), None, Wd[:, :F]), (A.to(gpu_device), None, Wd[:, F:5 * F])], out,
+                      bias=b.to(gpu_device), relu=True)
+    assert name == "k_gemm3p<96>"
     assert rel_err(out, ref) <= TOL
 
 
 @pytest.mark.parametrize("M,N,K", [(8200, 512, 128), (4100, 132, 100), (33000, 256, 256)])
 def test_nn_wide_mask_and_accumulate(gpu_device, M, N, K):
-    """dA shape (several column tiles share the A rows), NN weights, ReLU-mask and accumulate epilogues."""
+    """dA shape (several column tiles share the A rows), NN weights, ReLU-mask and accumulate epilogues: K = 128 with N a
+    multiple of 128 on k_gemm_as3, N = 132 on k_gemm3, K = 256 (8 K-tiles) on k_gemm3p."""
+    kernel = {512: "k_gemm_as3", 132: "k_gemm3", 256: "k_gemm3p<96>"}[N]
     from gnnepcsaft_amd import ops
     torch.manual_seed(M + N)
     a, w = torch.randn(M, K), torch.randn(K, N) / 4
@@ -55,13 +59,13 @@ def test_nn_wide_mask_and_accumulate(gpu_device, M, N, K):
     ad, wd = a.to(gpu_device), w.to(gpu_device)
     prod = a.double() @ w.double()
     out = torch.full((M, N), float("nan"), device=gpu_device)
-    ops.gemm([(ad, None, wd)], out, b_trans=False)
+    assert gemm_named([(ad, None, wd)], out, b_trans=False) == kernel
     assert rel_err(out, prod) <= TOL
     out = torch.full((M, N), float("nan"), device=gpu_device)
-    ops.gemm([(ad, None, wd)], out, b_trans=False, mask=mask.to(gpu_device))
+    assert gemm_named([(ad, None, wd)], out, b_trans=False, mask=mask.to(gpu_device)) == kernel
     assert rel_err(out, prod * (mask > 0)) <= TOL
     out = c0.clone().to(gpu_device)
-    ops.gemm([(ad, None, wd)], out, b_trans=False, accumulate=True)
+    assert gemm_named([(ad, None, wd)], out, b_trans=False, accumulate=True) == kernel
     assert rel_err(out, c0.double() + prod) <= TOL
 
 
@@ -80,7 +84,7 @@ def test_three_segments_nn_ragged_k_strided_views(gpu_device):
         segs.append((gd[:, 128 * i:128 * i + k], None, wd[i, :k, :]))
         ref = ref + G3[:, 128 * i:128 * i + k].double() @ W[i, :k, :].double()
     out = torch.zeros(M, 512, device=gpu_device)
-    ops.gemm(segs, out[:, 128:260], b_trans=False)
+    assert gemm_named(segs, out[:, 128:260], b_trans=False) == "k_gemm3p<96>"  # 4 + 2 + 4 K-tiles
     assert rel_err(out[:, 128:260], ref) <= TOL
     assert float(out[:, :128].abs().max()) == 0.0 and float(out[:, 260:].abs().max()) == 0.0
 
@@ -105,27 +109,38 @@ def test_grouped_by_degree_class(gpu_device):
     ref = (cat @ W.double().T + b.double()).relu()
     weff = ops.pna_weff(Wd, F, dc.D, avg)
     z = torch.full((N, F), float("nan"), device=gpu_device)
-    ops.gemm_grouped([(xd, None, Wd[:, 0:F], 0), (Ad, None, weff[0], 4 * F * F)], z, dc, bias=bd, relu=True)
+    name = gemm_named([(xd, None, Wd[:, 0:F], 0), (Ad, None, weff[0], 4 * F * F)], z, dc, bias=bd, relu=True)
+    assert name == "k_gemm3p<128>"  # 2 + 8 K-tiles over the 128-row table
     assert rel_err(z, ref) <= TOL
     gr = torch.randn(N, F)
     ref_dA = gr.double() @ W[:, F:5 * F].double() + (gr * amp.cpu()[:, None]).double() @ W[:, 5 * F:9 * F].double() + \
         (gr * att.cpu()[:, None]).double() @ W[:, 9 * F:].double()
     dA = torch.full((N, 4 * F), float("nan"), device=gpu_device)
-    ops.gemm_grouped([(gr.to(gpu_device), None, weff[0], 4 * F * F)], dA, dc, b_trans=False)
+    assert gemm_named([(gr.to(gpu_device), None, weff[0], 4 * F * F)], dA, dc, b_trans=False) == "k_gemm3"  # K = 64
     assert rel_err(dA, ref_dA) <= TOL
 
 
-def _both_tiled_kernels(fn):
-    """fn() through the software-pipelined kernel (default for >= 8 K-tiles) and through the two-barrier kernel."""
+def _under_option(opt, values, default, fn, kernels):
+    """fn() -> (output, kernel name) under every value of A/B option ``opt``; the runs must have taken ``kernels``, which
+    differ from each other.  Returns the outputs."""
     from gnnepcsaft_amd import ops
-    outs = []
-    for pipe in (1, 0):
-        ops.set_option(torch.device("cuda:0"), _lib.OPT_GEMM_PIPE, pipe)
+    assert len(set(kernels)) == len(values)
+    outs, names = [], []
+    for v in values:
+        ops.set_option(torch.device("cuda:0"), opt, v)
         try:
-            outs.append(fn())
+            out, name = fn()
+            outs.append(out)
+            names.append(name)
         finally:
-            ops.set_option(torch.device("cuda:0"), _lib.OPT_GEMM_PIPE, 1)
+            ops.set_option(torch.device("cuda:0"), opt, default)
+    assert tuple(names) == tuple(kernels)
     return outs
+
+
+def _both_tiled_kernels(fn, pipelined="k_gemm3p<96>"):
+    """fn() through the software-pipelined kernel (default for >= 8 K-tiles) and through the two-barrier kernel."""
+    return _under_option(_lib.OPT_GEMM_PIPE, (1, 0), 1, fn, (pipelined, "k_gemm3"))
 
 
 def test_pipelined_and_two_barrier_tiled_kernels_are_bit_identical(gpu_device):
@@ -144,8 +159,7 @@ def test_pipelined_and_two_barrier_tiled_kernels_are_bit_identical(gpu_device):
 
     def post0():
         out = torch.full((M, F), float("nan"), device=gpu_device)
-        ops.gemm([(xd, None, Wd[:, :F]), (Ad, None, Wd[:, F:])], out, bias=bd, relu=True)
-        return out
+        return out, gemm_named([(xd, None, Wd[:, :F]), (Ad, None, Wd[:, F:])], out, bias=bd, relu=True)
     p, q = _both_tiled_kernels(post0)
     assert torch.equal(p, q)
     assert rel_err(p, (torch.cat([x, A], 1).double() @ W.double().T + b.double()).relu()) <= TOL
@@ -159,9 +173,8 @@ def test_pipelined_and_two_barrier_tiled_kernels_are_bit_identical(gpu_device):
 
     def three():
         outw = c0.clone().to(gpu_device)
-        ops.gemm([(bigd[:, 160 * i:160 * i + k], None, wsd[i]) for i, k in enumerate(ks)], outw[:, 8:104], b_trans=False,
-                 accumulate=True)
-        return outw
+        return outw, gemm_named([(bigd[:, 160 * i:160 * i + k], None, wsd[i]) for i, k in enumerate(ks)], outw[:, 8:104],
+                                b_trans=False, accumulate=True)
     p, q = _both_tiled_kernels(three)
     assert torch.equal(p, q)
     ref = c0.double().clone()
@@ -174,8 +187,7 @@ def test_pipelined_and_two_barrier_tiled_kernels_are_bit_identical(gpu_device):
 
     def wide():
         out = torch.full((M3, N3), float("nan"), device=gpu_device)
-        ops.gemm([(ad, None, wd)], out, b_trans=False, mask=md)
-        return out
+        return out, gemm_named([(ad, None, wd)], out, b_trans=False, mask=md)
     p, q = _both_tiled_kernels(wide)
     assert torch.equal(p, q)
     assert rel_err(p, (a.double() @ w.double()) * (mask > 0)) <= TOL
@@ -191,9 +203,8 @@ def test_pipelined_and_two_barrier_tiled_kernels_are_bit_identical(gpu_device):
 
     def grouped():
         z = torch.full((N, F), float("nan"), device=gpu_device)
-        ops.gemm_grouped([(xg, None, Wp[:, 0:F], 0), (Ag, None, weff[0], 4 * F * F)], z, dc, bias=bd, relu=True)
-        return z
-    p, q = _both_tiled_kernels(grouped)
+        return z, gemm_named([(xg, None, Wp[:, 0:F], 0), (Ag, None, weff[0], 4 * F * F)], z, dc, bias=bd, relu=True)
+    p, q = _both_tiled_kernels(grouped, pipelined="k_gemm3p<128>")  # (the 128-row table)
     assert torch.equal(p, q)
     assert not torch.isnan(p).any()
 
@@ -207,14 +218,7 @@ def test_activation_stationary_and_two_barrier_kernels_are_bit_identical(gpu_dev
     dev = torch.device("cuda:0")
 
     def both(fn):
-        outs = []
-        for on in (1, 0):
-            ops.set_option(dev, _lib.OPT_GEMM_AS, on)
-            try:
-                outs.append(fn())
-            finally:
-                ops.set_option(dev, _lib.OPT_GEMM_AS, 1)
-        return outs
+        return _under_option(_lib.OPT_GEMM_AS, (1, 0), 1, fn, ("k_gemm_as3", "k_gemm3"))
 
     torch.manual_seed(77)
     for M, N, K in [(8200, 512, 128), (4099, 256, 100), (70001, 384, 128)]:
@@ -225,30 +229,26 @@ def test_activation_stationary_and_two_barrier_kernels_are_bit_identical(gpu_dev
 
         def plain():
             out = torch.full((M, N + 24), float("nan"), device=gpu_device)
-            ops.gemm([(ad, None, wd)], out[:, 8:8 + N], b_trans=False)
-            return out
+            return out, gemm_named([(ad, None, wd)], out[:, 8:8 + N], b_trans=False)
         p, q = both(plain)
         assert torch.equal(p[:, 8:8 + N], q[:, 8:8 + N]) and rel_err(p[:, 8:8 + N], prod) <= TOL
         assert torch.isnan(p[:, :8]).all() and torch.isnan(p[:, 8 + N:]).all()
 
         def masked():
             out = torch.full((M, N), float("nan"), device=gpu_device)
-            ops.gemm([(ad, None, wd)], out, b_trans=False, mask=md)
-            return out
+            return out, gemm_named([(ad, None, wd)], out, b_trans=False, mask=md)
         p, q = both(masked)
         assert torch.equal(p, q) and rel_err(p, prod * (mask > 0)) <= TOL
 
         def accum():
             out = c0.clone().to(gpu_device)
-            ops.gemm([(ad, None, wd)], out, b_trans=False, accumulate=True)
-            return out
+            return out, gemm_named([(ad, None, wd)], out, b_trans=False, accumulate=True)
         p, q = both(accum)
         assert torch.equal(p, q) and rel_err(p, c0.double() + prod) <= TOL
 
         def bias_relu():
             out = torch.full((M, N), float("nan"), device=gpu_device)
-            ops.gemm([(ad, None, wd.T.contiguous())], out, bias=bd, relu=True)
-            return out
+            return out, gemm_named([(ad, None, wd.T.contiguous())], out, bias=bd, relu=True)
         p, q = both(bias_relu)
         assert torch.equal(p, q) and rel_err(p, (prod + b.double()).relu()) <= TOL
     # grouped dA: rows gathered per in-degree class, per-class weights, K = 128 -> N = 512
@@ -263,8 +263,7 @@ def test_activation_stationary_and_two_barrier_kernels_are_bit_identical(gpu_dev
 
     def grouped():
         dA = torch.full((Nn, 4 * F), float("nan"), device=gpu_device)
-        ops.gemm_grouped([(gr, None, weff[0], 4 * F * F)], dA, dc, b_trans=False)
-        return dA
+        return dA, gemm_named([(gr, None, weff[0], 4 * F * F)], dA, dc, b_trans=False)
     p, q = both(grouped)
     assert torch.equal(p, q) and not torch.isnan(p).any()
 
@@ -284,15 +283,10 @@ def test_96_and_128_row_tiles_of_the_pipelined_kernel_are_bit_identical(gpu_devi
     for M in (81920, 20037):
         x, A = torch.randn(M, F, device=gpu_device), torch.randn(M, 4 * F, device=gpu_device)
         W, b = torch.randn(F, 5 * F, device=gpu_device) / 8, torch.randn(F, device=gpu_device)
-        outs = []
-        for rows in (96, 128):
-            ops.set_option(dev, _lib.OPT_GEMM_TILE_ROWS, rows)
-            try:
-                out = torch.full((M, F), float("nan"), device=gpu_device)
-                ops.gemm([(x, None, W[:, :F]), (A, None, W[:, F:])], out, bias=b, relu=True)
-                outs.append(out)
-            finally:
-                ops.set_option(dev, _lib.OPT_GEMM_TILE_ROWS, 0)
+        def post0():
+            out = torch.full((M, F), float("nan"), device=gpu_device)
+            return out, gemm_named([(x, None, W[:, :F]), (A, None, W[:, F:])], out, bias=b, relu=True)
+        outs = _under_option(_lib.OPT_GEMM_TILE_ROWS, (96, 128), 0, post0, ("k_gemm3p<96>", "k_gemm3p<128>"))
         assert torch.equal(outs[0], outs[1]) and not torch.isnan(outs[0]).any()
         ref = (torch.cat([x, A], 1).double() @ W.double().T + b.double()).relu()
         assert rel_err(outs[0], ref) <= TOL
@@ -307,9 +301,10 @@ def test_96_and_128_row_tiles_of_the_pipelined_kernel_are_bit_identical(gpu_devi
     bd = torch.randn(F, device=gpu_device)
     weff = ops.pna_weff(Wp, F, dc.D, 1.2)
     zs = []
-    for fwd in (True, False):
+    for fwd, kernel in ((True, "k_gemm3p<96>"), (False, "k_gemm3p<128>")):
         z = torch.full((N, F), float("nan"), device=gpu_device)
-        ops.gemm_grouped([(xg, None, Wp[:, 0:F], 0), (Ag, None, weff[0], 4 * F * F)], z, dc, bias=bd, relu=True, forward_tiles=fwd)
+        assert gemm_named([(xg, None, Wp[:, 0:F], 0), (Ag, None, weff[0], 4 * F * F)], z, dc, bias=bd, relu=True,
+                          forward_tiles=fwd) == kernel
         zs.append(z)
     assert torch.equal(zs[0], zs[1]) and not torch.isnan(zs[0]).any()
 
@@ -324,18 +319,60 @@ def test_split_and_exact_kernels_agree(gpu_device):
     W = torch.randn(F, 5 * F) / 8
     xd, Ad, Wd = x.to(gpu_device), A.to(gpu_device), W.to(gpu_device)
     ref = torch.cat([x, A], 1).double() @ W.double().T
-    outs = {}
-    for mode in ("1", "0"):
-        ops.set_option(torch.device("cuda:0"), _lib.OPT_GEMM_SPLIT, int(mode))
-        try:
-            out = torch.empty(M, F, device=gpu_device)
-            ops.gemm([(xd, None, Wd[:, :F]), (Ad, None, Wd[:, F:])], out)
-            outs[mode] = out.double().cpu()
-        finally:
-            ops.set_option(torch.device("cuda:0"), _lib.OPT_GEMM_SPLIT, 1)
+    def post0():
+        out = torch.empty(M, F, device=gpu_device)
+        return out, gemm_named([(xd, None, Wd[:, :F]), (Ad, None, Wd[:, F:])], out)
+    outs = dict(zip("10", (o.double().cpu() for o in _under_option(_lib.OPT_GEMM_SPLIT, (1, 0), 1, post0,
+                                                                      ("k_gemm3p<96>", "k_gemm<vec>")))))
     assert rel_err(outs["1"], ref) <= TOL and rel_err(outs["0"], ref) <= TOL
     assert rel_err(outs["1"], outs["0"]) <= 2e-6
     assert rel_err(outs["1"], ref) <= rel_err(outs["0"], ref) * 1.5 + 1e-8
+
+
+#  kernel                 M     N    ks          options (A/B switches off their defaults)      row scale
+KERNEL_WALK = [
+    ("k_gemm_ws3<fast,4>", 8200, 128, (128,), {}, False),
+    ("k_gemm_ws3<fast,8>", 8200, 128, (128,), {_lib.OPT_GEMM_WS_FAST: (1, 2)}, False),
+    ("k_gemm_ws3", 8200, 96, (128,), {}, False),
+    ("k_gemm_ws", 8200, 128, (128,), {_lib.OPT_GEMM_SPLIT: (0, 1)}, False),
+    ("k_gemm_small_batched", 200, 128, (128,), {_lib.OPT_GEMM_MID: (0, 1)}, False),
+    ("k_gemm_mid", 650, 128, (128,), {}, False),
+    ("k_gemm<vec>", 5000, 128, (128,), {}, True),
+    ("k_gemm<generic>", 5000, 128, (30,), {}, True),
+    ("k_gemm3", 4100, 128, (64, 64), {}, False),
+    ("k_gemm3p<96>", 4100, 128, (256,), {}, False),  # 43 tiles of 96 rows in one round beat 33 of 128
+    ("k_gemm3p<128>", 4100, 128, (256,), {_lib.OPT_GEMM_TILE_ROWS: (128, 0)}, False),
+    ("k_gemm_as3", 4100, 256, (128,), {}, False),
+]
+
+
+@pytest.mark.parametrize("kernel,M,N,ks,options,rowscale", KERNEL_WALK, ids=[c[0] for c in KERNEL_WALK])
+def test_every_kernel_kind_at_its_smallest_shape(gpu_device, kernel, M, N, ks, options, rowscale):
+    """Every kernel behind gnx_gemm at the smallest shape that reaches it, ragged M (the last tile is partial): the plan
+    names it, gnx_gemm_workspace_bytes equals the plan's image bytes, and the product is within TOL of fp64."""
+    from gnnepcsaft_amd import ops
+    torch.manual_seed(M + N + len(ks))
+    a = [torch.randn(M, k) for k in ks]
+    w = [torch.randn(N, k) / 4 for k in ks]
+    rs = torch.rand(M) + 0.5 if rowscale else None
+    ref = sum((x * rs[:, None] if i == 0 and rowscale else x).double() @ y.double().T for i, (x, y) in enumerate(zip(a, w)))
+    segs = [(x.to(gpu_device), rs.to(gpu_device) if i == 0 and rowscale else None, y.to(gpu_device))
+            for i, (x, y) in enumerate(zip(a, w))]
+    out = torch.full((M, N), float("nan"), device=gpu_device)
+    for opt, (value, _) in options.items():
+        ops.set_option(gpu_device, opt, value)
+    try:
+        name, info = ops.gemm_plan(segs, out)
+        g, _ws = ops._gemm_args(segs, out, None, None, None, False, False, True, False)
+        asked = _lib.load().gnx_gemm_workspace_bytes(g[0], g[1], g[2], g[3], g[4], g[5], g[6], g[8], g[12], 0)
+        ops.gemm(segs, out)
+    finally:
+        for opt, (_, default) in options.items():
+            ops.set_option(gpu_device, opt, default)
+    assert name == kernel
+    assert asked == info.image_bytes and (asked > 0) == kernel.startswith(("k_gemm3", "k_gemm_as3"))
+    assert info.runs_split == int(asked > 0)
+    assert rel_err(out, ref) <= TOL
 
 
 @pytest.mark.parametrize("M,N,K", [(20001, 128, 128), (8192, 36, 100), (5000, 130, 260)])
@@ -444,15 +481,13 @@ def test_split_product_is_fp32_faithful_at_layer_widths(gpu_device, K, nseg, kin
     norm = (a.double().abs() @ w.double().abs().T).clamp_min(1.1754943508222875e-38)
     step = K // nseg
     segs = [(ad[:, i * step:(i + 1) * step], None, wd[:, i * step:(i + 1) * step]) for i in range(nseg)]
-    errs = {}
-    for mode in (1, 0):
-        ops.set_option(gpu_device, _lib.OPT_GEMM_SPLIT, mode)
-        try:
-            out = torch.empty(M, N, device=gpu_device)
-            ops.gemm(segs, out)
-            errs[mode] = float(((out.double().cpu() - ref).abs() / norm).max())
-        finally:
-            ops.set_option(gpu_device, _lib.OPT_GEMM_SPLIT, 1)
+    def product():
+        out = torch.empty(M, N, device=gpu_device)
+        return out, gemm_named(segs, out)
+    # (K = 128 in one segment is the weights-stationary shape; the wider ones take the pipelined tiled kernel)
+    kernels = ("k_gemm_ws3<fast,4>", "k_gemm_ws") if nseg == 1 else ("k_gemm3p<96>", "k_gemm<vec>")
+    outs = _under_option(_lib.OPT_GEMM_SPLIT, (1, 0), 1, product, kernels)
+    errs = {mode: float(((out.double().cpu() - ref).abs() / norm).max()) for mode, out in zip((1, 0), outs)}
     eps32 = 2.0 ** -24
     print(K, kind, {k: v / eps32 for k, v in errs.items()})
     # the exact-fp32 MFMA chain: error grows ~ sqrt(K) roundings; the split product sums 16 exact products per rounding

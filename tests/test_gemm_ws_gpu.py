@@ -1,12 +1,13 @@
-"""GPU parity of the weights-stationary persistent GEMM (k_gemm_ws: one segment, K,N <= 128, M >= 8192) against fp64
-torch, all epilogue variants, both weight layouts, ragged M / K / N."""
+"""GPU parity of the weights-stationary persistent GEMM (k_gemm_ws3, and k_gemm_ws with GNX_OPT_GEMM_SPLIT = 0: one
+segment, K,N <= 128, M >= 8192) against fp64 torch, all epilogue variants, both weight layouts, ragged M / K / N; every
+case also asks ops.gemm_plan which kernel its call takes."""
 import os
 
 import pytest
 import torch
 
 from gnnepcsaft_amd import _lib
-from tests.parity_util import rel_err
+from tests.parity_util import gemm_named, rel_err
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-5
@@ -16,7 +17,8 @@ TOL = 1e-5
                                    (163840, 128, 128), (10000, 128, 100)])
 @pytest.mark.parametrize("b_trans", [True, False])
 def test_gemm_ws_variants(gpu_device, M, N, K, b_trans):
-    from gnnepcsaft_amd import ops
+    """k_gemm_ws3: predicate-free on 4 waves where N = 128 and the epilogue is not accumulate, else predicated."""
+    fast = "k_gemm_ws3<fast,4>" if N == 128 else "k_gemm_ws3"
     torch.manual_seed(M + N + K)
     a = torch.randn(M, K)
     w = torch.randn(N, K) if b_trans else torch.randn(K, N)
@@ -26,13 +28,13 @@ def test_gemm_ws_variants(gpu_device, M, N, K, b_trans):
     ad, wd, bd = a.to(gpu_device), w.to(gpu_device), b.to(gpu_device)
     prod = a.double() @ (w.double().T if b_trans else w.double())
     out = torch.full((M, N), float("nan"), device=gpu_device)
-    ops.gemm([(ad, None, wd)], out, bias=bd, relu=True, b_trans=b_trans)
+    assert gemm_named([(ad, None, wd)], out, bias=bd, relu=True, b_trans=b_trans) == fast
     assert rel_err(out, (prod + b.double()).relu()) <= TOL
     out = torch.full((M, N), float("nan"), device=gpu_device)
-    ops.gemm([(ad, None, wd)], out, b_trans=b_trans, mask=mask.to(gpu_device))
+    assert gemm_named([(ad, None, wd)], out, b_trans=b_trans, mask=mask.to(gpu_device)) == fast
     assert rel_err(out, prod * (mask > 0)) <= TOL
     out = c0.clone().to(gpu_device)
-    ops.gemm([(ad, None, wd)], out, b_trans=b_trans, accumulate=True, bias=bd)
+    assert gemm_named([(ad, None, wd)], out, b_trans=b_trans, accumulate=True, bias=bd) == "k_gemm_ws3"
     assert rel_err(out, c0.double() + prod + b.double()) <= TOL
 
 
@@ -51,35 +53,35 @@ def test_predicate_free_and_predicated_ws3_are_bit_identical(gpu_device, M, K, b
     b, mask = torch.randn(N, device=gpu_device), torch.randn(M, N, device=gpu_device)
 
     def both(fn):
-        outs = []
+        outs, names = [], []
         for on in (1, 0, 2):  # 2: the 4-wave form (32-row tiles, two workgroups per CU)
             ops.set_option(dev, _lib.OPT_GEMM_WS_FAST, on)
             try:
-                outs.append(fn())
+                out, name = fn()
+                outs.append(out)
+                names.append(name)
             finally:
                 ops.set_option(dev, _lib.OPT_GEMM_WS_FAST, 2)
+        assert names == ["k_gemm_ws3<fast,8>", "k_gemm_ws3", "k_gemm_ws3<fast,4>"]
         assert torch.equal(torch.nan_to_num(outs[2], nan=-7.0), torch.nan_to_num(outs[0], nan=-7.0))  # (NaN guard frame)
         return outs[:2]
 
     def bias_relu():
         out = torch.full((M + 3, N + 8), float("nan"), device=gpu_device)
-        ops.gemm([(a, None, w)], out[:M, 4:4 + N], bias=b, relu=True, b_trans=b_trans)
-        return out
+        return out, gemm_named([(a, None, w)], out[:M, 4:4 + N], bias=b, relu=True, b_trans=b_trans)
     p, q = both(bias_relu)
     assert torch.equal(p[:M, 4:4 + N], q[:M, 4:4 + N]) and not torch.isnan(p[:M, 4:4 + N]).any()
     assert torch.isnan(p[M:]).all() and torch.isnan(p[:, :4]).all() and torch.isnan(p[:, 4 + N:]).all()
 
     def plain():
         out = torch.full((M, N), float("nan"), device=gpu_device)
-        ops.gemm([(a, None, w)], out, b_trans=b_trans)
-        return out
+        return out, gemm_named([(a, None, w)], out, b_trans=b_trans)
     p, q = both(plain)
     assert torch.equal(p, q)
 
     def masked():
         out = torch.full((M, N), float("nan"), device=gpu_device)
-        ops.gemm([(a, None, w)], out, b_trans=b_trans, mask=mask)
-        return out
+        return out, gemm_named([(a, None, w)], out, b_trans=b_trans, mask=mask)
     p, q = both(masked)
     assert torch.equal(p, q)
     prod = a.double() @ (w.double().T if b_trans else w.double())
@@ -95,7 +97,7 @@ def test_gemm_ws_strided_views_and_guard_rows(gpu_device):
     w = torch.randn(F, 3 * F)
     xd, wd = x.to(gpu_device), w.to(gpu_device)
     out = torch.zeros(M, H, device=gpu_device)
-    ops.gemm([(xd[:, F:2 * F], None, wd[:, F:2 * F])], out[:, 2 * F:3 * F])
+    assert gemm_named([(xd[:, F:2 * F], None, wd[:, F:2 * F])], out[:, 2 * F:3 * F]) == "k_gemm_ws3"  # (N = 64)
     ref = x[:, F:2 * F].double() @ w[:, F:2 * F].double().T
     assert rel_err(out[:, 2 * F:3 * F], ref) <= TOL
     assert float(out[:, :2 * F].abs().max()) == 0.0 and float(out[:, 3 * F:].abs().max()) == 0.0
@@ -153,11 +155,11 @@ def test_split_operand_product_is_fp32_faithful(gpu_device, b_trans, scale):
     ref = a.double() @ wm
     norm = a.double().abs() @ wm.abs()
     errs = {}
-    for mode in ("1", "0"):
+    for mode, kernel in (("1", "k_gemm_ws3<fast,4>"), ("0", "k_gemm_ws")):
         ops.set_option(torch.device("cuda:0"), _lib.OPT_GEMM_SPLIT, int(mode))
         try:
             out = torch.empty(M, N, device=gpu_device)
-            ops.gemm([(ad, None, wd)], out, b_trans=b_trans)
+            assert gemm_named([(ad, None, wd)], out, b_trans=b_trans) == kernel
             errs[mode] = float(((out.double().cpu() - ref).abs() / norm).max())
         finally:
             ops.set_option(torch.device("cuda:0"), _lib.OPT_GEMM_SPLIT, 1)

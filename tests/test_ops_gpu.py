@@ -12,7 +12,7 @@ import torch
 
 from oracle import pyg_restatement as O
 from gnnepcsaft_amd import _lib
-from tests.parity_util import rel_err
+from tests.parity_util import gemm_named, rel_err
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-5
@@ -216,14 +216,18 @@ def test_gemm_mid_size_kernel_against_the_tiled_kernel(gpu_device):
     from gnnepcsaft_amd import _lib, ops
     dev = torch.device("cuda:0")
 
-    def both(fn):
-        outs = []
+    def both(fn, other):
+        """fn() -> (output, kernel name) with GNX_OPT_GEMM_MID on and off: k_gemm_mid, then ``other``."""
+        outs, names = [], []
         for on in (1, 0):
             ops.set_option(dev, _lib.OPT_GEMM_MID, on)
             try:
-                outs.append(fn())
+                out, name = fn()
+                outs.append(out)
+                names.append(name)
             finally:
                 ops.set_option(dev, _lib.OPT_GEMM_MID, 1)
+        assert names == ["k_gemm_mid", other]
         return outs
 
     torch.manual_seed(19)
@@ -231,26 +235,25 @@ def test_gemm_mid_size_kernel_against_the_tiled_kernel(gpu_device):
                     (200, 36, 300)]:
         a, w, wt = torch.randn(M, K, device=gpu_device), torch.randn(K, N, device=gpu_device), torch.randn(N, K, device=gpu_device)
         b, mask, c0 = torch.randn(N, device=gpu_device), torch.randn(M, N, device=gpu_device), torch.randn(M, N, device=gpu_device)
+        small = "k_gemm_small_batched" if M <= 256 else None  # (unmasked products only)
+        nn_tiled = "k_gemm<vec>" if N % 4 == 0 else "k_gemm<generic>"  # ([k][n] weights: the row stride is N)
 
         def nt():
             out = torch.full((M, N), float("nan"), device=gpu_device)
-            ops.gemm([(a, None, wt)], out, bias=b, relu=True)
-            return out
-        p, q = both(nt)
+            return out, gemm_named([(a, None, wt)], out, bias=b, relu=True)
+        p, q = both(nt, small or "k_gemm<vec>")
         assert rel_err(p, q) <= 2e-6 and rel_err(p, (a.double() @ wt.double().T + b.double()).relu()) <= TOL
 
         def nn_mask():
             out = torch.full((M, N), float("nan"), device=gpu_device)
-            ops.gemm([(a, None, w)], out, b_trans=False, mask=mask)
-            return out
-        p, q = both(nn_mask)
+            return out, gemm_named([(a, None, w)], out, b_trans=False, mask=mask)
+        p, q = both(nn_mask, nn_tiled)
         assert rel_err(p, q) <= 2e-6 and rel_err(p, (a.double() @ w.double()) * (mask > 0)) <= TOL
 
         def nn_acc():
             out = c0.clone()
-            ops.gemm([(a, None, w)], out, b_trans=False, accumulate=True)
-            return out
-        p, q = both(nn_acc)
+            return out, gemm_named([(a, None, w)], out, b_trans=False, accumulate=True)
+        p, q = both(nn_acc, small or nn_tiled)
         assert rel_err(p, q) <= 2e-6 and rel_err(p, c0.double() + a.double() @ w.double()) <= TOL
     # three segments with a row scale on strided views (the dx product's shape at 640 rows)
     M, F = 640, 128
@@ -260,10 +263,9 @@ def test_gemm_mid_size_kernel_against_the_tiled_kernel(gpu_device):
 
     def three():
         out = torch.zeros(M, F + 8, device=gpu_device)
-        ops.gemm([(g3[:, 4:4 + F], None, ws[0]), (g3[:, 4 + F:4 + 2 * F], rs, ws[1]), (g3[:, 4 + 2 * F:4 + 3 * F], None, ws[2])],
-                 out[:, 4:4 + F], b_trans=False)
-        return out
-    p, q = both(three)
+        return out, gemm_named([(g3[:, 4:4 + F], None, ws[0]), (g3[:, 4 + F:4 + 2 * F], rs, ws[1]),
+                                (g3[:, 4 + 2 * F:4 + 3 * F], None, ws[2])], out[:, 4:4 + F], b_trans=False)
+    p, q = both(three, "k_gemm<vec>")
     ref = g3[:, 4:4 + F].double() @ ws[0].double() + (rs[:, None] * g3[:, 4 + F:4 + 2 * F]).double() @ ws[1].double() + \
         g3[:, 4 + 2 * F:4 + 3 * F].double() @ ws[2].double()
     assert rel_err(p[:, 4:4 + F], q[:, 4:4 + F]) <= 2e-6 and rel_err(p[:, 4:4 + F], ref) <= TOL
@@ -281,17 +283,15 @@ def test_gemm_mid_size_kernel_against_the_tiled_kernel(gpu_device):
 
     def grouped():
         z = torch.full((Nn, F), float("nan"), device=gpu_device)
-        ops.gemm_grouped([(x, None, W[:, 0:F], 0), (A, None, weff[0], 4 * F * F)], z, dc, bias=bd, relu=True)
-        return z
-    p, q = both(grouped)
+        return z, gemm_named([(x, None, W[:, 0:F], 0), (A, None, weff[0], 4 * F * F)], z, dc, bias=bd, relu=True)
+    p, q = both(grouped, "k_gemm<vec>")
     cat = torch.cat([x, A, A * amp[:, None], A * att[:, None]], 1).double()
     assert rel_err(p, q) <= 2e-6 and rel_err(p, (cat @ W.double().T + bd.double()).relu()) <= TOL
 
     def grouped_da():
         dA = torch.full((Nn, 4 * F), float("nan"), device=gpu_device)
-        ops.gemm_grouped([(x, None, weff[0], 4 * F * F)], dA, dc, b_trans=False)
-        return dA
-    p, q = both(grouped_da)
+        return dA, gemm_named([(x, None, weff[0], 4 * F * F)], dA, dc, b_trans=False)
+    p, q = both(grouped_da, "k_gemm<vec>")
     assert rel_err(p, q) <= 2e-6 and not torch.isnan(p).any()
 
 
