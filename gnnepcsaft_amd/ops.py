@@ -1076,13 +1076,15 @@ _PCSAFT_MIX = {"pcsaft_mix_state": ("gnx_pcsaft_mix_state", (0, 0, 0)),
                "pcsaft_mix_lnphi_state": ("gnx_pcsaft_mix_lnphi_state", (1, 0)),
                "pcsaft_mix_lnphi": ("gnx_pcsaft_mix_lnphi", (0, 1, 1)),
                "pcsaft_mix_bubble": ("gnx_pcsaft_mix_bubble", (0, 1, 0, 0)),
-               "pcsaft_mix_flash": ("gnx_pcsaft_mix_flash", (0, 1, 1, 0, 0))}
+               "pcsaft_mix_flash": ("gnx_pcsaft_mix_flash", (0, 1, 1, 0, 0)),
+               "pcsaft_mix_stability": ("gnx_pcsaft_mix_stability", (0, 1, 0, 0))}
 
 
-def _pcsaft_mix(params, comp, kij, eab, owner, T, second, x, name, out=None, last=True):
+def _pcsaft_mix(params, comp, kij, eab, owner, T, second, x, name, out=None, last=True, trial=None):
     """The mixture form ``name`` of ``_PCSAFT_MIX``: validate, take ``out`` or make the outputs, call.  ``second`` is the
     state beside T (rho or P), None for the bubble point, which has none.  ``last`` False leaves the last fp64 output
-    (lnphi_pure) out: None in the result, NULL for the entry."""
+    (lnphi_pure) out: None in the result, NULL for the entry.  ``trial``: the int64 column that the stability entry
+    takes beside ``owner``, and it alone."""
     entry, widths = _PCSAFT_MIX[name]
     params, owner, T = _pcsaft_args(params, owner, T, name)
     dev = params.device
@@ -1097,6 +1099,12 @@ def _pcsaft_mix(params, comp, kij, eab, owner, T, second, x, name, out=None, las
             if tuple(t.shape) != (M, nc, nc):
                 raise _lib.GnxError(_lib.GNX_E_INVALID, f"{name}: {label} must be [{M}, {nc}, {nc}], got {tuple(t.shape)}")
         mats.append(t)
+    rows = []
+    if trial is not None:
+        if trial.dtype != torch.int64 or trial.device != dev or trial.shape != owner.shape:
+            raise _lib.GnxError(_lib.GNX_E_INVALID, f"{name}: trial must be an int64 tensor on {dev} of the shape of "
+                                                    f"owner, {tuple(owner.shape)}")
+        rows.append(trial.contiguous())
     state = [] if second is None else [_f64_on(second, f"{name}: state", dev)]
     x = _f64_on(x, f"{name}: x", dev)
     n = T.numel()
@@ -1108,8 +1116,8 @@ def _pcsaft_mix(params, comp, kij, eab, owner, T, second, x, name, out=None, las
         specs[-2] = None
     out = _pcsaft_outs(out, specs, dev, name)
     check(getattr(_lib.load(), entry)(handle(dev), params.data_ptr(), params.size(0), comp.data_ptr(), _ptr(mats[0]),
-                                      _ptr(mats[1]), M, nc, owner.data_ptr(), T.data_ptr(),
-                                      *(t.data_ptr() for t in state), x.data_ptr(), n, *map(_ptr, out)))
+                                      _ptr(mats[1]), M, nc, owner.data_ptr(), *(t.data_ptr() for t in rows),
+                                      T.data_ptr(), *(t.data_ptr() for t in state), x.data_ptr(), n, *map(_ptr, out)))
     return out
 
 
@@ -1178,6 +1186,25 @@ def pcsaft_mix_flash(params: torch.Tensor, comp: torch.Tensor, kij: Optional[tor
     status [n] int32; 4 = no vapour-liquid split).  A used slot with z = 0 is dropped (x = y = 0.0), a -1 slot has NaN;
     where status != 0, beta and the densities are 0.0 and the x and y rows are NaN."""
     return _pcsaft_mix_flash(params, comp, kij, eab, owner, T, P, z)
+
+
+def _pcsaft_mix_stability(params, comp, kij, eab, owner, trial, T, P, z, out=None):
+    """``pcsaft_mix_stability`` writing into ``out`` = (tpd, w, rho_w, rho_z, status) where given; rho_w and rho_z may be
+    None there."""
+    return _pcsaft_mix(params, comp, kij, eab, owner, T, P, z, "pcsaft_mix_stability", out=out, trial=trial)
+
+
+def pcsaft_mix_stability(params: torch.Tensor, comp: torch.Tensor, kij: Optional[torch.Tensor],
+                         eab: Optional[torch.Tensor], owner: torch.Tensor, trial: torch.Tensor, T: torch.Tensor,
+                         P: torch.Tensor, z: torch.Tensor
+                         ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Mixture PC-SAFT tangent-plane stability test, one trial per row (gnx_pcsaft_mix_stability): arguments as
+    ``pcsaft_mix_flash`` with trial [n] int64 beside owner, 0 = vapour-like, 1 = liquid-like, 2 + s = rich in slot s ->
+    (tpd [n], w [n, nc], rho_w [n], rho_z [n] mol/m^3, status [n] int32).  tpd is 0.0 exactly where the trial fell onto
+    the feed (w = z), negative where it proves the feed unstable, else the distance at the stationary point it reached.
+    A used slot with z = 0 is dropped (w = 0.0), a -1 slot has NaN; where status != 0 (3 also for a trial outside
+    [0, nc + 2)), tpd is NaN, the densities are 0.0 and the w row is NaN."""
+    return _pcsaft_mix_stability(params, comp, kij, eab, owner, trial, T, P, z)
 
 
 _POOL = {"add": _lib.POOL_ADD, "sum": _lib.POOL_ADD, "mean": _lib.POOL_MEAN, "max": _lib.POOL_MAX}

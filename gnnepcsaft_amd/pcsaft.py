@@ -34,6 +34,12 @@ binary at every measured (T, P) over a list of trial feeds in one launch (pcsaft
 ``mixture_tp_flash`` on device tensors.  A feed without a vapour-liquid split at (T, P) reports ``STATUS_SINGLE_PHASE``;
 liquid-liquid splits are not looked for.
 
+Tangent-plane stability of a feed z at (T, P), the test the reference runs on every trial feed before it flashes it
+(csrc/gnx_pcsaft_mix_stab.hip): ``mix_is_stable`` for one point (the reference's ``is_stable_feos``),
+``mix_stability_batch`` for every point of every system in one launch, ``mixture_stability`` on device tensors.  Each
+point runs nc + 2 trial phases as rows of one launch; a negative tangent-plane distance comes back with the composition w
+that proves it, also where the split is liquid-liquid and the flash reports none.  No flash is started from w here.
+
 Parameter rows are ``[m, sigma (Å), epsilon/k (K), kappa_ab, epsilon_ab/k (K), mu (D), na, nb, mw]``; state rows are
 ``[T (K), P (Pa), phase, tp, value]`` (only T and P are read).  Densities are in mol/m³, pressures in Pa.
 """
@@ -265,13 +271,61 @@ def mixture_tp_flash(params: torch.Tensor, comp: torch.Tensor, z: torch.Tensor, 
     return ops.pcsaft_mix_flash(params, comp, kij, eab, _owner(owner, T), T, P, z)
 
 
+def _reduce_trials(tpd: torch.Tensor, w: torch.Tensor, status: torch.Tensor
+                   ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """The verdict of each point from its trials, tpd / status [n, nt] and w [n, nt, nc] of ``ops.pcsaft_mix_stability``
+    -> (stable [n] bool, tpd [n], w [n, nc], status [n] int32).  A trial with status 0 and tpd < 0 makes the point
+    unstable with status 0, whatever the other trials did: it gets the most negative tpd and its w.  Otherwise a trial
+    status != 0 is the point's (3 over 1): not stable, tpd and w NaN.  Otherwise the point is stable: the smallest
+    stationary tpd and its w, or 0.0 and the feed (trial 0) where every trial fell onto the feed (tpd = 0.0 exactly)."""
+    ok = status == STATUS_OK
+    unstable = (ok & (tpd < 0)).any(dim=1)
+    st = torch.where(unstable, torch.zeros_like(status[:, 0]), status.max(dim=1).values)
+    pick = torch.where(ok & (tpd != 0), tpd, torch.full_like(tpd, float("inf"))).argmin(dim=1)
+    point = torch.arange(tpd.size(0), device=tpd.device)
+    lost = (st != STATUS_OK)
+    nan = torch.full_like(tpd[:, 0], float("nan"))
+    return (~unstable & ~lost, torch.where(lost, nan, tpd[point, pick]),
+            torch.where(lost[:, None], nan[:, None], w[point, pick]), st)
+
+
+def mixture_stability(params: torch.Tensor, comp: torch.Tensor, z: torch.Tensor, T: torch.Tensor, P: torch.Tensor,
+                      owner: Optional[torch.Tensor] = None, kij: Optional[torch.Tensor] = None,
+                      eab: Optional[torch.Tensor] = None
+                      ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Tensor form on device tensors, arguments as ``mixture_tp_flash`` -> (stable [n] bool, tpd [n], w [n, nc], status [n]
+    int32): Michelsen's tangent-plane test of the feed z at (T, P).  Each point becomes nc + 2 rows of one launch of
+    ``ops.pcsaft_mix_stability`` (trial 0 vapour-like, 1 liquid-like, 2 + s rich in slot s), reduced on the device as
+    ``_reduce_trials`` says: unstable with the most negative tangent-plane distance tpd and the composition w that has
+    it; stable with the smallest stationary tpd (0.0 and w = z where every trial fell onto the feed); or, with status
+    != 0, neither: ``stable`` False, tpd and w NaN.  In w a used slot with z = 0 has 0.0, a -1 slot NaN.  Asynchronous, on
+    the current stream."""
+    n, nc = z.shape
+    nt = nc + 2
+    trial = torch.arange(nt, dtype=torch.int64, device=z.device).repeat(n)
+    tpd, w, _, _, status = ops.pcsaft_mix_stability(
+        params, comp, kij, eab, _owner(owner, T).repeat_interleave(nt), trial, T.repeat_interleave(nt),
+        P.repeat_interleave(nt), z.repeat_interleave(nt, dim=0))
+    return _reduce_trials(tpd.view(n, nt), w.view(n, nt, nc), status.view(n, nt))
+
+
 def _run_mix(kind: str, params: np.ndarray, comp: np.ndarray, kij: Optional[np.ndarray], eab: Optional[np.ndarray],
              owner: np.ndarray, states: np.ndarray) -> Tuple[List[Optional[np.ndarray]], np.ndarray]:
     """states [n, 2 + nc] -> (values, status [n] int32); values is [rho [n]] for kind "density", [rho, lnphi [n, nc],
     None] for "lnphi", [rho, lnphi, lnphi_pure [n, nc]] for "lnphi_pure" and [P [n], y [n, nc], rho_l [n], rho_v [n]]
     for "bubble", which does not read the P column, and [beta [n], x [n, nc], y [n, nc], rho_l [n], rho_v [n]] for "flash",
-    whose composition columns hold the feed."""
+    whose composition columns hold the feed, as do those of "stability": [tpd [n], w [n, nc]] of the points, their nc + 2
+    trials each expanded here into rows of the launch and reduced by ``_reduce_trials`` after the download."""
     n, nc = owner.shape[0], comp.shape[1]
+    if kind == "stability":
+        nt = nc + 2
+        rows = [np.repeat(a, nt, axis=0) for a in (owner, states[:, 0], states[:, 1], states[:, 2:])]
+        trial = np.tile(np.arange(nt, dtype=np.int64), n)
+        (tpd, w, _, _), status = _run(ops._pcsaft_mix_stability, [params, comp, kij, eab, rows[0], trial, *rows[1:]],
+                                      n * nt, [(n * nt,), (n * nt, nc), None, None])
+        _, tpd, w, status = _reduce_trials(torch.from_numpy(tpd).view(n, nt), torch.from_numpy(w).view(n, nt, nc),
+                                           torch.from_numpy(status).view(n, nt))
+        return [tpd.numpy(), w.numpy()], status.numpy()
     if kind == "flash":
         return _run(ops._pcsaft_mix_flash, [params, comp, kij, eab, owner, states[:, 0], states[:, 1], states[:, 2:]], n,
                     [(n,), (n, nc), (n, nc), (n,), (n,)])
@@ -548,3 +602,29 @@ def mix_flash_x1(parameters: Sequence[Sequence[float]], states: Any, feed_x1s: A
     ok = (status == STATUS_OK).reshape(n, F)
     first = np.argmax(ok, axis=1)
     return np.where(ok.any(axis=1), x[:, 0].reshape(n, F)[np.arange(n), first], np.nan)
+
+
+def mix_is_stable(parameters: Sequence[Sequence[float]], state: Sequence[float], kij_matrix: Optional[Any] = None,
+                  epsilon_ab: Optional[Any] = None, density_initialization: Optional[str] = None) -> bool:
+    """Is the feed ``state = [T (K), P (Pa), z1, z2, ...]`` of the components ``parameters`` one stable phase (reference
+    ``is_stable_feos``)?  False where one of the nc + 2 trial phases has a negative tangent-plane distance.  The state of
+    the feed is the one of its liquid and vapour roots with the lower Gibbs energy, feos's
+    ``density_initialization=None``, which is what the reference passes: any other value raises ``ValueError``.  Raises
+    ``RuntimeError`` where the test is inconclusive (a trial without a root or an end, and none that is negative)."""
+    if density_initialization is not None:
+        raise ValueError(f"mix_is_stable takes the feed's state of lower Gibbs energy (density_initialization=None), got "
+                         f"{density_initialization!r}")
+    (tpd, _), _ = _mix_point("stability", "stability", parameters, state, kij_matrix, epsilon_ab)
+    return bool(tpd[0] >= 0.0)
+
+
+def mix_stability_batch(mixtures: List[List[List[Any]]], states_batch: List[Any], kij: Optional[List[Any]] = None
+                        ) -> List[np.ndarray]:
+    """Stability tests of every state of every non-empty table in one launch, arguments as ``mix_rho_batch`` (the
+    composition columns hold the feed): one fp64 array [rows, 1 + nc_i] of rows ``[tpd, w1..w_nc]`` per non-empty table.
+    tpd < 0: unstable, w the trial composition with the most negative tangent-plane distance; tpd >= 0: stable, the
+    smallest stationary distance and its w (0.0 and the feed where every trial fell onto the feed); a row of NaN where
+    a point is inconclusive."""
+    parts = _mix_batch("stability", mixtures, states_batch, kij,
+                       lambda values: np.concatenate([values[0][:, None], values[1]], axis=1))
+    return [v[:, :1 + len(mixtures[i])].copy() for i, v in parts]

@@ -538,6 +538,23 @@ int32_t gnx_pcsaft_mix_flash(gnx_handle* h, const double* params, int64_t B, con
                              const double* mix_kij, const double* mix_eab, int64_t M, int32_t nc, const int64_t* owner,
                              const double* T, const double* P, const double* z, int64_t n, double* beta, double* x,
                              double* y, double* rho_l, double* rho_v, int32_t* status);
+/* Tangent-plane stability test (ref: pcsaft/pcsaft_feos.py is_stable_feos, called at pcsaft/kij.py:30 on every trial
+ * feed before it is flashed): row i is trial trial[i] of the feed z[i, :] (normalised by its sum) at T[i], P[i] (Pa).  A
+ * mixture of nc slots has the trials 0 (vapour-like, W = z K), 1 (liquid-like, W = z / K) and 2 + s (rich in slot s, W =
+ * 0.1 z + 0.9 e_s), K_i = f_i(z) kT / (z_i P); a caller that wants a verdict runs all nc + 2 as rows of one launch.  Each is
+ * successive substitution on the tangent-plane distance D(w) = sum_i w_i (ln f_i(w) - ln f_i(z)), ln f_i = mu_i^res/kT +
+ * ln(rho x_i), the state of z and of every w being the one of its liquid and its lowest vapour root at P with the lower
+ * sum_i x_i ln f_i.  tpd[i] is 0.0 exactly where the trial fell onto the feed (w[i, :] = z, rho_w = rho_z), the first
+ * D < -1e-8 it met (z is unstable, w[i, :] proves it) or D at the stationary point it converged to (residual < 1e-8);
+ * rho_w[i], rho_z[i] are the molar densities of w and z (either may be NULL).  A used slot with z = 0 is dropped (w =
+ * 0.0), a -1 slot has NaN in w; the trial rich in such a slot and every trial of a single component report the feed.
+ * status 1: no end within 400 steps, a non-finite value, or no root of w or z at P.  status 3 also covers a non-finite
+ * or non-positive P and a trial outside [0, nc + 2).  A row with status != 0 has tpd = NaN, NaN in its whole w row and
+ * densities 0.0.  The launch has no kernel id (GNX_K_NONE). */
+int32_t gnx_pcsaft_mix_stability(gnx_handle* h, const double* params, int64_t B, const int64_t* mix_comp,
+                                 const double* mix_kij, const double* mix_eab, int64_t M, int32_t nc, const int64_t* owner,
+                                 const int64_t* trial, const double* T, const double* P, const double* z, int64_t n,
+                                 double* tpd, double* w, double* rho_w, double* rho_z, int32_t* status);
 
 /* ---- contiguous segment reduce: global pool (ref: train/models.py:218-225, 587-595) ------------------------ */
 enum { GNX_POOL_ADD = 0, GNX_POOL_MEAN = 1, GNX_POOL_MAX = 2 };

@@ -16,7 +16,11 @@ With ``--flash`` it times the (T, P) flash kernel of csrc/gnx_pcsaft_mix_flash.h
 tests/pcsaft_mix_flash_ref.py (the six named bubble points at beta = 0.3, six fixture points at beta = 0.5), repeated, the
 bubble-point kernel on the liquids of the same tie lines for the ratio, and that module's oracle flash on a sample.
 
-Usage: python tools/pcsaft_bench.py [--mixture | --bubble | --flash] [--sizes 1000,100000,1000000] [--oracle-sample 20] [--out FILE.json]
+With ``--stability`` it times the tangent-plane stability test of csrc/gnx_pcsaft_mix_stab.hip through
+``pcsaft.mixture_stability`` (nc + 2 = 6 trial rows per point) on the 43 cases of tests/pcsaft_mix_stab_ref.py, repeated,
+the flash kernel on the 12 tie-line feeds among them in the same run, and that module's oracle on a sample.
+
+Usage: python tools/pcsaft_bench.py [--mixture | --bubble | --flash | --stability] [--reps 3] [--sizes 1000,100000,1000000] [--oracle-sample 20] [--out FILE.json]
 """
 import argparse
 import json
@@ -34,7 +38,11 @@ from gnnepcsaft_amd import pcsaft  # noqa: E402
 from tests import pcsaft_ref as R  # noqa: E402
 
 
-def _kernel_ms(fn, reps=3):
+REPS = 3
+
+
+def _kernel_ms(fn, reps=None):
+    reps = REPS if reps is None else reps
     fn()
     torch.cuda.synchronize()
     best = float("inf")
@@ -142,18 +150,57 @@ def _flash(args, dev):
     return res
 
 
+def _stability(args, dev):
+    from tests import pcsaft_mix_stab_ref as S
+    cases = S.cases()
+    params, comp, z = [], np.full((len(cases), 4), -1, dtype=np.int64), np.zeros((len(cases), 4))
+    for i, (_, _, rows, _, _, zi, _) in enumerate(cases):
+        comp[i, :len(rows)] = np.arange(len(params), len(params) + len(rows))
+        params.extend(np.asarray(rows, dtype=np.float64).tolist())
+        z[i, :len(rows)] = zi
+    T, P = np.array([c[3] for c in cases]), np.array([c[4] for c in cases])
+    expected = np.array([c[6] for c in cases])
+    tie = [i for i, c in enumerate(cases) if c[0] == "tie line"]
+    step = max(1, len(cases) // args.oracle_sample)
+    t0 = time.perf_counter()
+    sols = [S.stability(rows, zi, t, p) for _, _, rows, t, p, zi, _ in cases[::step]]
+    oracle = (time.perf_counter() - t0) / len(sols)
+    d_params, d_comp = torch.from_numpy(np.array(params)).to(dev), torch.from_numpy(comp).to(dev)
+    res = []
+    for n in [int(s) for s in args.sizes.split(",")]:
+        idx = np.arange(n) % len(cases)
+        o, t, pp, zz = (torch.from_numpy(np.ascontiguousarray(a)).to(dev) for a in (idx.astype(np.int64), T[idx], P[idx], z[idx]))
+        k = _kernel_ms(lambda: pcsaft.mixture_stability(d_params, d_comp, zz, t, pp, o))
+        stable, _, _, st = pcsaft.mixture_stability(d_params, d_comp, zz, t, pp, o)
+        wrong = int((stable.cpu().numpy() != expected[idx]).sum())
+        fidx = np.array(tie)[np.arange(n) % len(tie)]
+        fo, ft, fp, fz = (torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+                          for a in (fidx.astype(np.int64), T[fidx], P[fidx], z[fidx]))
+        kf = _kernel_ms(lambda: pcsaft.mixture_tp_flash(d_params, d_comp, fz, ft, fp, fo))
+        rec = dict(points=n, rows=6 * n, mix_stability_ms=k, mix_stability_points_per_s=n / k * 1e3,
+                   inconclusive_points=int((st != 0).sum().item()), wrong_verdicts=wrong,
+                   mix_flash_tie_line_feeds_kernel_ms=kf, stability_over_flash=k / kf, oracle_stability_ms_est=oracle * n * 1e3)
+        print(json.dumps(rec), flush=True)
+        res.append(rec)
+    return res
+
+
 def main():
+    global REPS
     ap = argparse.ArgumentParser()
     ap.add_argument("--sizes", default="1000,100000,1000000")
     ap.add_argument("--oracle-sample", type=int, default=20)
     ap.add_argument("--mixture", action="store_true")
     ap.add_argument("--bubble", action="store_true")
     ap.add_argument("--flash", action="store_true")
+    ap.add_argument("--stability", action="store_true")
+    ap.add_argument("--reps", type=int, default=REPS, help="timed repetitions per kernel, the best of which counts")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
-    if args.mixture or args.bubble or args.flash:
+    REPS = args.reps
+    if args.mixture or args.bubble or args.flash or args.stability:
         dev = torch.device("cuda", torch.cuda.current_device())
-        res = (_flash if args.flash else _bubble if args.bubble else _mixture)(args, dev)
+        res = (_stability if args.stability else _flash if args.flash else _bubble if args.bubble else _mixture)(args, dev)
         if args.out:
             with open(args.out, "w") as fh:
                 json.dump(dict(device=torch.cuda.get_device_name(dev), oracle_sample=args.oracle_sample, results=res), fh,
