@@ -96,6 +96,19 @@ class PnaBwdArgs(C.Structure):
                 ("acc_buf", _vp), ("dx", _vp), ("flags", _i32), ("etile_w", _i32), ("etile_info", _vp)]
 
 
+class GemmImage(C.Structure):
+    """gnx_gemm_image of include/gnx.h: what a product's plan says about its split weight images."""
+    _fields_ = [("image_bytes", C.c_uint64), ("classes", _i32), ("Npad", _i32), ("Kpad", _i32), ("koff", _i32 * 5),
+                ("frag", _i32), ("bt", _i32)]
+
+
+class PnaLayerImages(C.Structure):
+    """gnx_pna_layer_images of include/gnx.h: one layer's image pointers and records (gnx_pna_split_all)."""
+    _fields_ = [("post0", _vp * PNA_MAX_TOWERS), ("dA", _vp * PNA_MAX_TOWERS), ("dx", _vp * PNA_MAX_TOWERS),
+                ("post0_rec", GemmImage * PNA_MAX_TOWERS), ("dA_rec", GemmImage * PNA_MAX_TOWERS),
+                ("dx_rec", GemmImage * PNA_MAX_TOWERS)]
+
+
 class PnaFinishArgs(C.Structure):
     """gnx_pna_finish_args of include/gnx.h (same field order)."""
     _fields_ = [("L", _i32), ("T", _i32), ("F", _i32), ("pre_layers", _i32), ("post_layers", _i32), ("R", _i32), ("D", _i32),
@@ -209,6 +222,12 @@ SIGNATURES = {
     "gnx_pna_weight_only": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _f32, C.POINTER(_vp), _i32, _vp, _vp,
                                    C.POINTER(_vp), _vp, _vp]),
     "gnx_pna_conv_fwd": (_i32, [_vp, C.POINTER(PnaFwdArgs)]),
+    "gnx_pna_split_all_bytes": (_sz, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _i64, _i32]),
+    "gnx_pna_split_all": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _i64, _i32, C.POINTER(_vp), C.POINTER(_vp), _vp, _sz,
+                                 C.POINTER(PnaLayerImages)]),
+    "gnx_gemm_split_counts": (_i32, [_vp, C.POINTER(_i64), C.POINTER(_i64)]),
+    "gnx_pna_conv_fwd_images": (_i32, [_vp, C.POINTER(PnaFwdArgs), C.POINTER(PnaLayerImages)]),
+    "gnx_pna_conv_bwd_images": (_i32, [_vp, C.POINTER(PnaBwdArgs), C.POINTER(PnaLayerImages)]),
     "gnx_pna_weight_only_all": (_i32, [_vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _i32, C.POINTER(_f32), C.POINTER(_vp),
                                        _i32, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp)]),
     "gnx_pna_stack_finish": (_i32, [_vp, C.POINTER(PnaFinishArgs)]),

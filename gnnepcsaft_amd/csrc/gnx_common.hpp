@@ -19,13 +19,15 @@ struct gnx_handle {
   float* d_scratch = nullptr;  // 4 KiB
   float* d_zero = nullptr;     // 256 zero bytes, never written: what a masked-out vector load reads
   // side streams (gnx_side_begin/end/join): created on first use; `stream` is swapped to one between begin and end
-  static constexpr int kSideStreams = 3;  // 0: weight gradients, 1: bond-table chain, 2: weight-image splits ahead of their products
+  static constexpr int kSideStreams = 3;  // 0: weight gradients, 1: bond-table chain, 2: the caller's (no library call forks onto it)
   hipStream_t side[kSideStreams] = {nullptr, nullptr, nullptr};
   hipStream_t main_saved = nullptr;
   hipEvent_t side_fork[kSideStreams] = {nullptr, nullptr, nullptr}, side_done[kSideStreams] = {nullptr, nullptr, nullptr};
   bool on_side = false;
   // A/B switches (gnx_set_option); initialised ONCE from the GNX_* environment variables in gnx_create
   int opt[GNX_OPT_COUNT] = {};
+  // launches of k_split_weights (one product's images, in front of it) and of k_split_weights_batched since gnx_create
+  int64_t split_launches = 0, split_batched_launches = 0;
   // profiling: bit k of prof_mask = record an event pair around every launch group of kernel id k
   unsigned prof_mask = 0;
   std::vector<hipEvent_t> ev;
@@ -137,6 +139,10 @@ static inline hipError_t gnx_raise_lds_limit(int bytes) {
   }
   return hipSuccess;
 }
+
+// the split weight images of n products in one launch per 32 problems (gnx_gemm.hip; gemm_split_problem: gnx_gemm_plan.hpp)
+struct gemm_split_problem;
+int32_t gnx_split_weights_batched(gnx_handle* h, int32_t n, const gemm_split_problem* probs);
 
 // reads + clears the sticky range flag (synchronises the stream)
 int32_t gnx_read_flag(gnx_handle* h, int* value);

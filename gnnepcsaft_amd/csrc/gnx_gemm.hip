@@ -809,42 +809,55 @@ struct split_args {
   __bf16* out;
 };
 
-template <bool B_TRANS>
-__global__ void __launch_bounds__(256) k_split_weights(split_args g) {
-  const int kgroups = g.Kpad >> 3;
-  const int64_t total = (int64_t)g.D * g.Npad * kgroups;
-  const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+// One item of a split: thread `idx` of D * Npad * Kpad / 8 converts 8 consecutive k of one (class, column) and stores its three
+// pieces.  seg_of(si) names segment si's weights as a split_src; koff[q] (q <= nseg) are the padded k offsets.  Shared by
+// the per-call kernel and the batched one, so both write the same bytes.
+struct split_src {
+  const float* b;
+  int64_t ldb, cls_stride;
+  int k;
+};
+
+template <bool B_TRANS, typename SegOf>
+__device__ __forceinline__ void split_weights_item(int64_t idx, int nseg, const int* koff, SegOf seg_of, int N, int Npad,
+                                                   int Kpad, int D, int frag, __bf16* out) {
+  const int kgroups = Kpad >> 3;
+  const int64_t total = (int64_t)D * Npad * kgroups;
   if (idx >= total) return;
   int c, n, kg;
   if (B_TRANS) {  // W[n][k]: k fastest
     kg = (int)(idx % kgroups);
-    n = (int)((idx / kgroups) % g.Npad);
-    c = (int)(idx / ((int64_t)kgroups * g.Npad));
+    n = (int)((idx / kgroups) % Npad);
+    c = (int)(idx / ((int64_t)kgroups * Npad));
   } else {  // W[k][n]: n fastest
-    n = (int)(idx % g.Npad);
-    kg = (int)((idx / g.Npad) % kgroups);
-    c = (int)(idx / ((int64_t)kgroups * g.Npad));
+    n = (int)(idx % Npad);
+    kg = (int)((idx / Npad) % kgroups);
+    c = (int)(idx / ((int64_t)kgroups * Npad));
   }
   const int kk = kg * 8;
-  int si = 0;
+  int si = 0, kbase = 0;  // the segment kk falls into and its padded offset (the offsets grow with q)
 #pragma unroll
-  for (int q = 1; q < MAX_SEGS; ++q) si += (q < g.nseg && kk >= g.koff[q]) ? 1 : 0;
-  const seg_dev& sg = g.seg[si];
-  const int kl = kk - g.koff[si];
+  for (int q = 1; q < MAX_SEGS; ++q)
+    if (q < nseg && kk >= koff[q]) {
+      si = q;
+      kbase = koff[q];
+    }
+  const split_src sg = seg_of(si);
+  const int kl = kk - kbase;
   const float* sb = sg.b + (int64_t)c * sg.cls_stride;
   float x[8];
 #pragma unroll
   for (int j = 0; j < 8; ++j) {
-    const bool ok = n < g.N && kl + j < sg.k;
+    const bool ok = n < N && kl + j < sg.k;
     const int64_t off = B_TRANS ? (int64_t)n * sg.ldb + kl + j : (int64_t)(kl + j) * sg.ldb + n;
     x[j] = ok ? sb[ok ? off : 0] : 0.f;
   }
   bf16x8 p1, p2, p3;
   split3(x, p1, p2, p3);
   // tile-major: [class][n tile][k tile][piece][128 n][32 k] -> the 24 KB of one (n tile, k tile) are contiguous
-  const int NT = g.Npad / BN, KT = g.Kpad / BK;
-  __bf16* blk = g.out + ((((int64_t)c * NT + n / BN) * KT + kk / BK) * 3) * (BN * BK);
-  if (g.frag) {
+  const int NT = Npad / BN, KT = Kpad / BK;
+  __bf16* blk = out + ((((int64_t)c * NT + n / BN) * KT + kk / BK) * 3) * (BN * BK);
+  if (frag) {
     // MFMA B operand of column n, k = 16 slab + 8 half .. +7: lane = 32 half + n % 32 of the (slab, piece, n / 32) fragment
     const int nl = n % BN, kl2 = kk % BK;
     const int64_t lane_off = ((int64_t)(nl >> 5) * 64 + ((kl2 >> 3) & 1) * 32 + (nl & 31)) * 8;
@@ -858,6 +871,59 @@ __global__ void __launch_bounds__(256) k_split_weights(split_args g) {
   *reinterpret_cast<bf16x8*>(o) = p1;
   *reinterpret_cast<bf16x8*>(o + BN * BK) = p2;
   *reinterpret_cast<bf16x8*>(o + 2 * BN * BK) = p3;
+}
+
+template <bool B_TRANS>
+__global__ void __launch_bounds__(256) k_split_weights(split_args g) {
+  split_weights_item<B_TRANS>((int64_t)blockIdx.x * 256 + threadIdx.x, g.nseg, g.koff,
+                              [&](int si) {
+                                const seg_dev& s = g.seg[si];
+                                return split_src{s.b, s.ldb, s.cls_stride, s.k};
+                              },
+                              g.N, g.Npad, g.Kpad, g.D, g.frag, g.out);
+}
+
+// The splits of many products in ONE launch (gnx_split_weights_batched: every PNA layer's images, once per step):
+// blockIdx.y = problem, blockIdx.x covers that problem's D * Npad * Kpad / 8 items (the grid is as wide as the largest
+// problem; blocks past a problem's end return).  A problem is what a split needs of a call -- per segment b, ldb, the class
+// stride and k; N, the class count, the layout and the image address -- 120 bytes, so 32 of them travel in the
+// kernel-argument block (4 KB): no descriptor buffer on the device, no copy.  Npad, Kpad and the k offsets follow from
+// N and k as in gemm_plan_of.
+#define SPLIT_MAX_BATCH 32
+struct split_batch_seg {
+  const float* b;
+  int64_t cls_stride;
+  int32_t ldb, k;
+};
+struct split_batch_prob {
+  split_batch_seg seg[MAX_SEGS];
+  __bf16* out;
+  int32_t N, D;
+  int32_t nseg;
+  int32_t layout;  // bit 0: B_TRANS, bit 1: fragment-major
+};
+struct split_batch_args {
+  split_batch_prob p[SPLIT_MAX_BATCH];
+  int32_t n;
+};
+static_assert(sizeof(split_batch_prob) == 120 && sizeof(split_batch_args) <= 4096, "split_batch_args: kernel-argument limit");
+
+__global__ void __launch_bounds__(256) k_split_weights_batched(split_batch_args b) {
+  const split_batch_prob& p = b.p[blockIdx.y];
+  int koff[MAX_SEGS + 1];
+  koff[0] = 0;
+#pragma unroll
+  for (int s = 0; s < MAX_SEGS; ++s) koff[s + 1] = koff[s] + (s < p.nseg ? (p.seg[s].k + BK - 1) / BK * BK : 0);
+  const int Npad = (p.N + BN - 1) / BN * BN, Kpad = koff[MAX_SEGS];
+  const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  auto seg_of = [&](int si) {
+    const split_batch_seg& s = p.seg[si];
+    return split_src{s.b, (int64_t)s.ldb, s.cls_stride, s.k};
+  };
+  if (p.layout & 1)
+    split_weights_item<true>(idx, p.nseg, koff, seg_of, p.N, Npad, Kpad, p.D, (p.layout >> 1) & 1, p.out);
+  else
+    split_weights_item<false>(idx, p.nseg, koff, seg_of, p.N, Npad, Kpad, p.D, (p.layout >> 1) & 1, p.out);
 }
 
 // Persistent workgroups (two per CU): workgroup w walks the virtual tile ids w, w + G, w + 2G, ...  A virtual id v maps
@@ -2020,6 +2086,7 @@ static int32_t gemm_launch(gnx_handle* h, int32_t nseg, const gnx_gemm_seg* segs
       hipLaunchKernelGGL(k_split_weights<true>, gs, dim3(256), 0, h->stream, sa);
     else
       hipLaunchKernelGGL(k_split_weights<false>, gs, dim3(256), 0, h->stream, sa);
+    ++h->split_launches;
   }
   if (p.stop_after_split || p.kernel == GNX_GEMM_KERNEL_NONE) {
     GNX_LAUNCH_CHECK();
@@ -2066,6 +2133,49 @@ static int32_t gemm_launch(gnx_handle* h, int32_t nseg, const gnx_gemm_seg* segs
   return GNX_OK;
 }
 
+// The splits of `n` products in ceil(n / SPLIT_MAX_BATCH) launches of k_split_weights_batched on the bound stream (declared
+// in gnx_common.hpp; gnx_pna_split_all is the caller).  Every image is written whole by its own problem's workgroups.
+int32_t gnx_split_weights_batched(gnx_handle* h, int32_t n, const gemm_split_problem* probs) {
+  GNX_CHECK_ARG(h && (n == 0 || probs) && n >= 0, "gnx_split_weights_batched: bad argument");
+  double bytes = 0.0;
+  for (int i = 0; i < n; ++i) {
+    const gemm_split_problem& q = probs[i];
+    GNX_CHECK_ARG(q.nseg >= 1 && q.nseg <= MAX_SEGS && q.N > 0 && q.classes >= 1 && q.out && aligned16(q.out),
+                  "gnx_split_weights_batched: problem %d: bad shape or image address", i);
+    for (int s = 0; s < q.nseg; ++s)
+      GNX_CHECK_ARG(q.b[s] && q.k[s] > 0 && q.ldb[s] > 0 && q.ldb[s] <= INT32_MAX,
+                    "gnx_split_weights_batched: problem %d, segment %d: NULL weights, k <= 0 or ldb out of range", i, s);
+  }
+  for (int i0 = 0; i0 < n; i0 += SPLIT_MAX_BATCH) {
+    split_batch_args b = {};
+    b.n = n - i0 < SPLIT_MAX_BATCH ? n - i0 : SPLIT_MAX_BATCH;
+    int64_t widest = 0;
+    for (int i = 0; i < b.n; ++i) {
+      const gemm_split_problem& q = probs[i0 + i];
+      split_batch_prob& d = b.p[i];
+      int64_t kpad = 0;
+      for (int s = 0; s < q.nseg; ++s) {
+        d.seg[s] = split_batch_seg{q.b[s], q.cls_stride[s], (int32_t)q.ldb[s], q.k[s]};
+        kpad += plan_kpad(q.k[s]);
+      }
+      d.out = reinterpret_cast<__bf16*>(q.out);
+      d.N = q.N;
+      d.D = q.classes;
+      d.nseg = q.nseg;
+      d.layout = (q.bt ? 1 : 0) | (q.frag ? 2 : 0);
+      const int64_t items = (int64_t)q.classes * (gnx_cdiv(q.N, BN) * BN) * (kpad / 8);
+      widest = items > widest ? items : widest;
+      bytes += 6.0 * items * 8 + 4.0 * q.classes * q.N * kpad;
+    }
+    gnx_prof_scope prof(h, GNX_K_GEMM_TILED, bytes, 0.0, 0.0);
+    hipLaunchKernelGGL(k_split_weights_batched, dim3((unsigned)gnx_cdiv(widest, 256), (unsigned)b.n), dim3(256), 0, h->stream, b);
+    ++h->split_batched_launches;
+    bytes = 0.0;
+  }
+  GNX_LAUNCH_CHECK();
+  return GNX_OK;
+}
+
 extern "C" int32_t gnx_gemm(gnx_handle* h, int32_t nseg, const gnx_gemm_seg* segs, int64_t M, int32_t N,
                             const float* bias, const float* mask, int64_t ldmask, float* C, int64_t ldc, int32_t flags,
                             void* ws, size_t ws_bytes) {
@@ -2081,6 +2191,13 @@ extern "C" size_t gnx_gemm_workspace_bytes(gnx_handle* h, int32_t nseg, const gn
   return gemm_plan_of(nseg, segs, cls_strides, num_classes, M, N, nullptr, mask, N, nullptr, N, flags, grouped ? &a_table : nullptr,
                       1, nullptr, 0, h->opt, h->num_cus)
       .image_bytes;
+}
+
+extern "C" int32_t gnx_gemm_split_counts(gnx_handle* h, int64_t* per_call, int64_t* batched) {
+  GNX_CHECK_ARG(h && per_call && batched, "gnx_gemm_split_counts: NULL argument");
+  *per_call = h->split_launches;
+  *batched = h->split_batched_launches;
+  return GNX_OK;
 }
 
 extern "C" int32_t gnx_gemm_tile_rows(gnx_handle* h, int64_t M, int32_t N) {

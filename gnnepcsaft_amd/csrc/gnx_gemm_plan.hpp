@@ -197,3 +197,185 @@ static inline gemm_plan gemm_plan_of(int32_t nseg, const gnx_gemm_seg* segs, con
   }
   return p;
 }
+
+// ---------------------------------------------------------------------------------------------------------------
+// Split weight images as data: what a plan says about the images it reads, and what a split needs of the call.
+// ---------------------------------------------------------------------------------------------------------------
+
+// The record of a plan's images (gnx_gemm_image, gnx.h: it crosses the C ABI next to the image pointer).  Two calls whose
+// records are equal read images of the same size and layout; image_bytes == 0: the call reads none.
+static inline gnx_gemm_image gemm_image_of(const gemm_plan& p) {
+  gnx_gemm_image r = {};
+  if (p.image_bytes == 0) return r;
+  r.image_bytes = p.image_bytes;
+  r.classes = p.classes;
+  r.Npad = p.Npad;
+  r.Kpad = p.Kpad;
+  for (int s = 0; s <= PLAN_MAX_SEGS; ++s) r.koff[s] = p.koff[s];
+  r.frag = p.frag;
+  r.bt = p.bt ? 1 : 0;
+  return r;
+}
+static inline bool gemm_image_equal(const gnx_gemm_image& a, const gnx_gemm_image& b) {
+  bool eq = a.image_bytes == b.image_bytes && a.classes == b.classes && a.Npad == b.Npad && a.Kpad == b.Kpad && a.frag == b.frag &&
+            a.bt == b.bt;
+  for (int s = 0; s <= PLAN_MAX_SEGS; ++s) eq = eq && a.koff[s] == b.koff[s];
+  return eq;
+}
+
+// One problem of gnx_split_weights_batched (gnx_gemm.hip): the weights of a call whose plan has images, and where they go.
+struct gemm_split_problem {
+  const float* b[PLAN_MAX_SEGS];
+  int64_t ldb[PLAN_MAX_SEGS], cls_stride[PLAN_MAX_SEGS];
+  int32_t k[PLAN_MAX_SEGS];
+  int32_t nseg, N, classes, frag, bt;
+  void* out;
+};
+static inline gemm_split_problem gemm_split_problem_of(const gemm_plan& p, int32_t nseg, const gnx_gemm_seg* segs,
+                                                       const int64_t* cls_strides, int32_t N, void* out) {
+  gemm_split_problem q = {};
+  for (int s = 0; s < nseg; ++s) {
+    q.b[s] = segs[s].b;
+    q.ldb[s] = segs[s].ldb;
+    q.cls_stride[s] = cls_strides ? cls_strides[s] : 0;
+    q.k[s] = segs[s].k;
+  }
+  q.nseg = nseg;
+  q.N = N;
+  q.classes = p.classes;
+  q.frag = p.frag;
+  q.bt = p.bt ? 1 : 0;
+  q.out = out;
+  return q;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// The three products of a PNAConv layer that read split weight images, as argument lists.  gnx_pna_conv_fwd / _bwd run
+// them, gnx_pna_split_all plans them: both build them HERE, so they cannot disagree about what a product's weights are.
+//   post-layer 0   z = x W0^T + A Weff(d)^T   grouped by degree class, [n][k] weights, N = F, K = F + 4F
+//   dA             dA = g Weff(d)             grouped by degree class, [k][n] weights, N = 4F, K = F
+//   dx             dx = g Wx + dP Wi + dQ Wj  three segments,          [k][n] weights, N = F, K = 3F
+// P = the layer's parameter pointers (gnx_pna_bwd_args' order), t = the tower; operand / output pointers are the caller's.
+// At split time only their alignment is looked at (pna_stand_in).
+// ---------------------------------------------------------------------------------------------------------------
+struct pna_product {
+  int32_t nseg = 0;
+  gnx_gemm_seg seg[3] = {};
+  int64_t stride[3] = {0, 0, 0};
+  bool grouped = false;
+  int32_t classes = 1, N = 0, flags = 0, tile_rows = 0;  // tile_rows != 0: gnx_gemm_grouped_rows
+  const float* bias = nullptr;
+  float* C = nullptr;
+  int64_t ldc = 0;
+};
+
+static inline gnx_gemm_seg pna_seg(const float* a, int64_t lda, const float* b, int64_t ldb, int32_t k) {
+  gnx_gemm_seg s;
+  s.a = a;
+  s.lda = lda;
+  s.rowscale = nullptr;
+  s.b = b;
+  s.ldb = ldb;
+  s.k = k;
+  s._pad = 0;
+  return s;
+}
+
+// a 256-byte aligned address that is never dereferenced: stands in for an activation when only the weights are known
+static inline float* pna_stand_in() { return reinterpret_cast<float*>(static_cast<uintptr_t>(1) << 20); }
+
+static inline pna_product pna_post0_product(const float* const* P, const float* weff_t, int T, int F, int pre, int post, int D,
+                                            int t, const float* x, const float* A, float* z0, int tile_rows) {
+  const int H = T * F, k = 4 + t * 2 * (pre + post) + 2 * pre;
+  pna_product q;
+  q.nseg = 2;
+  q.seg[0] = pna_seg(x + t * F, H, P[k], 13 * F, F);
+  q.seg[1] = pna_seg(A + (int64_t)t * 4 * F, (int64_t)T * 4 * F, weff_t, 4 * F, 4 * F);
+  q.stride[1] = (int64_t)4 * F * F;
+  q.grouped = true;
+  q.classes = D;
+  q.N = F;
+  q.flags = GNX_GEMM_B_TRANS | (post > 1 ? GNX_GEMM_RELU : 0);
+  q.tile_rows = tile_rows == 96 ? 96 : 128;
+  q.bias = P[k + 1];
+  q.C = z0 + t * F;
+  q.ldc = H;
+  return q;
+}
+
+static inline pna_product pna_dA_product(const float* weff_t, int T, int F, int D, int t, const float* g, float* dA) {
+  pna_product q;
+  q.nseg = 1;
+  q.seg[0] = pna_seg(g + t * F, (int64_t)T * F, weff_t, 4 * F, F);
+  q.stride[0] = (int64_t)4 * F * F;
+  q.grouped = true;
+  q.classes = D;
+  q.N = 4 * F;
+  q.C = dA + (int64_t)t * 4 * F;
+  q.ldc = (int64_t)T * 4 * F;
+  return q;
+}
+
+static inline pna_product pna_dx_product(const float* const* P, int T, int F, int pre, int post, int t, const float* g_post0,
+                                         const float* dP, const float* dQ, float* dx) {
+  const int H = T * F, k0 = 4 + t * 2 * (pre + post), kp = k0 + 2 * pre;
+  pna_product q;
+  q.nseg = 3;
+  q.seg[0] = pna_seg(g_post0 + t * F, H, P[kp], 13 * F, F);
+  q.seg[1] = pna_seg(dP + t * F, H, P[k0], 3 * F, F);
+  q.seg[2] = pna_seg(dQ + t * F, H, P[k0] + F, 3 * F, F);
+  q.N = F;
+  q.C = dx + t * F;
+  q.ldc = H;
+  return q;
+}
+
+// The plan of such a product over M rows: what gemm_launch computes for pna_product's call (a grouped call's table is
+// looked at for NULL-ness and max_tiles only, and max_tiles moves grid sizes alone).
+static inline gemm_plan pna_product_plan(const pna_product& q, int64_t M, int32_t extra_flags, const void* ws, int64_t max_tiles,
+                                         const int* opt, int num_cus) {
+  static const int32_t a_table = 0;
+  return gemm_plan_of(q.nseg, q.seg, q.grouped ? q.stride : nullptr, q.grouped ? q.classes : 1, M, q.N, q.bias, nullptr, 0, q.C,
+                      q.ldc, q.flags | extra_flags, q.grouped ? &a_table : nullptr, max_tiles, ws, q.grouped ? q.tile_rows : 0, opt,
+                      num_cus);
+}
+
+// Where the images of L layers x T towers lie in one slab: per (layer, tower) post-layer 0, dA, dx back to back, each
+// region as long as its plan's image_bytes (a multiple of 24 KB, so every region stays 256-byte aligned); a product
+// without images takes no room.  Returns the slab's size; fills out[l] when out != NULL (pointers relative to slab;
+// slab == NULL: offsets from 0, for the size query).  params: L x (4 + T 2 (pre + post)) pointers, weff: L x T.
+static inline size_t pna_images_layout(int L, int T, int F, int pre, int post, int D, int64_t N, int tile_rows,
+                                       const float* const* params, const float* const* weff, const int* opt, int num_cus,
+                                       void* slab, gnx_pna_layer_images* out, gemm_split_problem* probs, int* nprobs) {
+  const int np = 4 + T * 2 * (pre + post);
+  const uintptr_t base = reinterpret_cast<uintptr_t>(slab);
+  float* const act = pna_stand_in();
+  size_t off = 0;
+  int n = 0;
+  for (int l = 0; l < L; ++l) {
+    const float* const* P = params + (size_t)l * np;
+    gnx_pna_layer_images li = {};
+    for (int t = 0; t < T; ++t) {
+      const float* w = weff[(size_t)l * T + t];
+      const pna_product prod[3] = {pna_post0_product(P, w, T, F, pre, post, D, t, act, act, act, tile_rows),
+                                   pna_dA_product(w, T, F, D, t, act, act), pna_dx_product(P, T, F, pre, post, t, act, act, act, act)};
+      void** const ptr[3] = {&li.post0[t], &li.dA[t], &li.dx[t]};
+      gnx_gemm_image* const rec[3] = {&li.post0_rec[t], &li.dA_rec[t], &li.dx_rec[t]};
+      for (int i = 0; i < 3; ++i) {
+        const pna_product& q = prod[i];
+        // (any non-NULL workspace: its alignment is checked where the images are written, not in the plan)
+        const gemm_plan p = pna_product_plan(q, N, GNX_GEMM_SPLIT_ONLY, act, 1, opt, num_cus);
+        if (!p.images || !p.run_split) continue;
+        *rec[i] = gemm_image_of(p);
+        void* const image = reinterpret_cast<void*>(base + off);
+        *ptr[i] = image;
+        if (probs) probs[n] = gemm_split_problem_of(p, q.nseg, q.seg, q.grouped ? q.stride : nullptr, q.N, image);
+        ++n;
+        off += p.image_bytes;
+      }
+    }
+    if (out) out[l] = li;
+  }
+  if (nprobs) *nprobs = n;
+  return off;
+}

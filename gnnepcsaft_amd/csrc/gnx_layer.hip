@@ -14,17 +14,7 @@
 
 namespace {
 
-inline gnx_gemm_seg seg(const float* a, int64_t lda, const float* b, int64_t ldb, int32_t k) {
-  gnx_gemm_seg s;
-  s.a = a;
-  s.lda = lda;
-  s.rowscale = nullptr;
-  s.b = b;
-  s.ldb = ldb;
-  s.k = k;
-  s._pad = 0;
-  return s;
-}
+inline gnx_gemm_seg seg(const float* a, int64_t lda, const float* b, int64_t ldb, int32_t k) { return pna_seg(a, lda, b, ldb, k); }
 
 inline bool a16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
@@ -76,31 +66,56 @@ int32_t on_side(gnx_handle* h, int which, bool enabled, F body) {
   return st;
 }
 
+// the degree-class table a grouped product runs over
+struct class_tiles {
+  const int32_t *dperm, *tiles, *ntiles;
+  int64_t max_tiles;
+};
+
+int32_t run_product(gnx_handle* h, const pna_product& q, int64_t M, const class_tiles& ct, int32_t extra_flags, void* ws,
+                    size_t ws_bytes) {
+  if (!q.grouped) return gnx_gemm(h, q.nseg, q.seg, M, q.N, q.bias, nullptr, 0, q.C, q.ldc, q.flags | extra_flags, ws, ws_bytes);
+  if (q.tile_rows)
+    return gnx_gemm_grouped_rows(h, q.nseg, q.seg, q.stride, q.classes, M, q.N, q.bias, nullptr, 0, q.C, q.ldc, q.flags | extra_flags,
+                                 ct.dperm, ct.tiles, ct.ntiles, ct.max_tiles, ws, ws_bytes, q.tile_rows);
+  return gnx_gemm_grouped(h, q.nseg, q.seg, q.stride, q.classes, M, q.N, q.bias, nullptr, 0, q.C, q.ldc, q.flags | extra_flags, ct.dperm,
+                          ct.tiles, ct.ntiles, ct.max_tiles, ws, ws_bytes);
+}
+
+// One of the layer's three image-reading products.  `image` / `rec` (gnx_pna_split_all) are used only if the plan of THIS call
+// gives the very record the images were written under; any difference -- another row count, a changed option, an operand
+// that is not aligned after all -- and the product splits in place into the scratch, as it does without images.
+int32_t run_with_image(gnx_handle* h, const pna_product& q, int64_t M, const class_tiles& ct, void* image,
+                       const gnx_gemm_image* rec, void* scratch, size_t scratch_bytes) {
+  if (image != nullptr && rec != nullptr && rec->image_bytes > 0) {
+    const gemm_plan p = pna_product_plan(q, M, GNX_GEMM_PRESPLIT, image, ct.max_tiles, h->opt, h->num_cus);
+    if (p.images && gemm_image_equal(gemm_image_of(p), *rec))
+      return run_product(h, q, M, ct, GNX_GEMM_PRESPLIT, image, (size_t)rec->image_bytes);
+  }
+  return run_product(h, q, M, ct, 0, scratch, scratch_bytes);
+}
+
 }  // namespace
 
 // upper bound of the split-weight images any product of the layer's forward or backward needs (gnx_gemm_workspace_bytes): the
 // degree-class product dA = g Weff(d) (D classes, N = 4F, K = F) and the 3-segment dx product (N = F, K = 3F)
-// Layout of the workspace: [0, scratch) is reused by every product of the layer in turn; behind it one region per tower and
-// per tiled product whose weight images are split AHEAD on side stream 2 (layers with two or more towers, see
-// gnx_pna_conv_fwd): forward: post-layer 0; backward: dA and dx.
+// The workspace is one scratch that every product of the layer splits into in turn (a product whose images came from
+// gnx_pna_split_all does not touch it).
 static size_t align256(size_t v) { return (v + 255) / 256 * 256; }
-static void pna_ws_sizes(int32_t T, int32_t F, int32_t D, size_t& scratch, size_t& post0, size_t& grouped, size_t& dx) {
-  const int64_t H = (int64_t)T * F;
-  grouped = align256(gemm_plan_image_bytes(D, 4 * (int64_t)F, plan_kpad(F)));
-  dx = align256(gemm_plan_image_bytes(1, F, 3 * plan_kpad(F)));
-  const size_t lin = gemm_plan_image_bytes(1, H, plan_kpad(H));  // lin / merged product, H x H
-  // forward: post-layer 0 by degree class, z = x W0^T + A Weff(d)^T  (N = F, K = F + 4F)
-  post0 = align256(gemm_plan_image_bytes(D, F, plan_kpad(F) + plan_kpad(4 * (int64_t)F)));
-  scratch = align256(std::max(std::max(grouped, post0), std::max(dx, lin)) + 256);
-}
 
 extern "C" size_t gnx_pna_conv_bwd_workspace_bytes(int32_t T, int32_t F, int32_t D) {
-  size_t scratch, post0, grouped, dx;
-  pna_ws_sizes(T, F, D, scratch, post0, grouped, dx);
-  return scratch + (size_t)(T > 0 ? T : 1) * std::max(post0, grouped + dx);
+  const int64_t H = (int64_t)T * F;
+  const size_t grouped = gemm_plan_image_bytes(D, 4 * (int64_t)F, plan_kpad(F));
+  const size_t dx = gemm_plan_image_bytes(1, F, 3 * plan_kpad(F));
+  const size_t lin = gemm_plan_image_bytes(1, H, plan_kpad(H));  // lin / merged product, H x H
+  // forward: post-layer 0 by degree class, z = x W0^T + A Weff(d)^T  (N = F, K = F + 4F)
+  const size_t post0 = gemm_plan_image_bytes(D, F, plan_kpad(F) + plan_kpad(4 * (int64_t)F));
+  return align256(std::max(std::max(grouped, post0), std::max(dx, lin)) + 256);
 }
 
-extern "C" int32_t gnx_pna_conv_bwd(gnx_handle* h, const gnx_pna_bwd_args* a) {
+extern "C" int32_t gnx_pna_conv_bwd(gnx_handle* h, const gnx_pna_bwd_args* a) { return gnx_pna_conv_bwd_images(h, a, nullptr); }
+
+extern "C" int32_t gnx_pna_conv_bwd_images(gnx_handle* h, const gnx_pna_bwd_args* a, const gnx_pna_layer_images* im) {
   GNX_CHECK_ARG(h && a, "gnx_pna_conv_bwd: NULL argument");
   const int T = a->T, F = a->F, pre = a->pre_layers, post = a->post_layers, R = a->R, D = a->D;
   const int64_t N = a->N, E = a->E;
@@ -117,41 +132,9 @@ extern "C" int32_t gnx_pna_conv_bwd(gnx_handle* h, const gnx_pna_bwd_args* a) {
   const float* lin_w = P[2];
   WgradQueue wq;
 
-  // the weight images of the two tiled products of this backward (dA per degree class, the 3-segment dx) are split on side
-  // stream 2 while the lin / hidden input-gradient products run; the products take them as they are (GNX_GEMM_PRESPLIT)
-  size_t scratch = a->ws_bytes, r_post0 = 0, r_dA = 0, r_dx = 0;
-  // (for layers with two or more towers only: the measurement is at the same choice in gnx_pna_conv_fwd)
-  bool ahead = T >= 2 && side && !h->on_side && N >= 4096 && a->ws != nullptr;
-  if (ahead) {
-    pna_ws_sizes(T, F, D, scratch, r_post0, r_dA, r_dx);
-    ahead = scratch + (size_t)T * (r_dA + r_dx) <= a->ws_bytes;
-    if (!ahead) scratch = a->ws_bytes;
-  }
-  unsigned char* const ahead_base = reinterpret_cast<unsigned char*>(a->ws) + scratch;
-  auto dA_call = [&](int t, const float* gt, int extra_flags, void* ws, size_t ws_bytes) -> int32_t {
-    gnx_gemm_seg s = seg(gt, H, a->weff[t], 4 * F, F);
-    const int64_t stride = (int64_t)4 * F * F;
-    return gnx_gemm_grouped(h, 1, &s, &stride, D, N, 4 * F, nullptr, nullptr, 0, a->dA + (int64_t)t * 4 * F, (int64_t)T * 4 * F,
-                            extra_flags, a->dperm, a->tiles, a->ntiles, a->max_tiles, ws, ws_bytes);
-  };
-  auto dx_call = [&](int t, const float* g_post0, int extra_flags, void* ws, size_t ws_bytes) -> int32_t {
-    const int k0 = pidx(t, true, 0), kp = pidx(t, false, 0);
-    const float* W0 = P[k0];
-    gnx_gemm_seg s3[3] = {seg(g_post0 + t * F, H, P[kp], 13 * F, F), seg(a->dP + t * F, H, W0, 3 * F, F),
-                          seg(a->dQ + t * F, H, W0 + F, 3 * F, F)};
-    return gnx_gemm(h, 3, s3, N, F, nullptr, nullptr, 0, a->dx + t * F, H, extra_flags, ws, ws_bytes);
-  };
-  if (ahead) {
-    GNX_TRY(gnx_side_begin_n(h, 2));
-    int32_t st = GNX_OK;
-    for (int t = 0; t < T && st == GNX_OK; ++t) {  // (gbuf[0] stands in for the gradient operand: only its alignment matters)
-      unsigned char* reg = ahead_base + (size_t)t * (r_dA + r_dx);
-      st = dA_call(t, a->gbuf[0] + t * F, GNX_GEMM_SPLIT_ONLY, reg, r_dA);
-      if (st == GNX_OK) st = dx_call(t, a->gbuf[0], GNX_GEMM_SPLIT_ONLY, reg + r_dA, r_dx);
-    }
-    (void)gnx_side_end(h);
-    GNX_TRY(st);
-  }
+  // the two tiled products of this backward that read split weight images (dA per degree class, the 3-segment dx) take them
+  // from `im` where gnx_pna_split_all wrote them for this very shape, and split in place otherwise
+  const class_tiles ct = {a->dperm, a->tiles, a->ntiles, a->max_tiles};
 
   // ---- lin (or lin o last post layer): dgrad into gbuf[0]
   // every gradient buffer of the chain is distinct: the queued weight-gradient problems read them at flush time
@@ -210,12 +193,8 @@ extern "C" int32_t gnx_pna_conv_bwd(gnx_handle* h, const gnx_pna_bwd_args* a) {
       class_wgrads.push_back(class_wgrad);
     else
       GNX_TRY(class_wgrad());
-    if (ahead) {
-      if (t == 0) GNX_TRY(gnx_side_join_n(h, 2));
-      GNX_TRY(dA_call(t, gt, GNX_GEMM_PRESPLIT, ahead_base + (size_t)t * (r_dA + r_dx), r_dA));
-    } else {
-      GNX_TRY(dA_call(t, gt, 0, a->ws, scratch));
-    }
+    GNX_TRY(run_with_image(h, pna_dA_product(a->weff[t], T, F, D, t, g, a->dA), N, ct, im ? im->dA[t] : nullptr,
+                           im ? &im->dA_rec[t] : nullptr, a->ws, a->ws_bytes));
   }
   const float* g_post0 = g;  // gradient w.r.t. post-layer 0's output: also an operand of dx below
   // (the last layer of the pass keeps the weight gradients queued so far for the end of the layer as well: launched HERE,
@@ -274,12 +253,9 @@ extern "C" int32_t gnx_pna_conv_bwd(gnx_handle* h, const gnx_pna_bwd_args* a) {
   };
   const bool flush_before_dx = side && !tail;
   if (flush_before_dx) GNX_TRY(on_side(h, 0, side, flush_batched));
-  for (int t = 0; t < T; ++t) {
-    if (ahead)
-      GNX_TRY(dx_call(t, g_post0, GNX_GEMM_PRESPLIT, ahead_base + (size_t)t * (r_dA + r_dx) + r_dA, r_dx));
-    else
-      GNX_TRY(dx_call(t, g_post0, 0, a->ws, scratch));
-  }
+  for (int t = 0; t < T; ++t)
+    GNX_TRY(run_with_image(h, pna_dx_product(P, T, F, pre, post, t, g_post0, a->dP, a->dQ, a->dx), N, ct, im ? im->dx[t] : nullptr,
+                           im ? &im->dx_rec[t] : nullptr, a->ws, a->ws_bytes));
   // ---- bond-table gradient chain on side stream 1 (feeds parameter gradients and the shared accumulator only)
   GNX_TRY(on_side(h, 1, side, [&]() -> int32_t {
     if (!fused_bwd) {
@@ -362,7 +338,9 @@ extern "C" int32_t gnx_pna_weight_only(gnx_handle* h, const float* BE, int32_t R
 // products, message assembly, remaining pre layers, scatter-aggregate, post-layer 0 by degree class, hidden post
 // layers, lin (or the merged product).  Every activation the backward needs is written into caller-owned buffers.
 // ---------------------------------------------------------------------------------------------------------------
-extern "C" int32_t gnx_pna_conv_fwd(gnx_handle* h, const gnx_pna_fwd_args* a) {
+extern "C" int32_t gnx_pna_conv_fwd(gnx_handle* h, const gnx_pna_fwd_args* a) { return gnx_pna_conv_fwd_images(h, a, nullptr); }
+
+extern "C" int32_t gnx_pna_conv_fwd_images(gnx_handle* h, const gnx_pna_fwd_args* a, const gnx_pna_layer_images* im) {
   GNX_CHECK_ARG(h && a, "gnx_pna_conv_fwd: NULL argument");
   const int T = a->T, F = a->F, pre = a->pre_layers, post = a->post_layers, D = a->D;
   const int64_t N = a->N, E = a->E;
@@ -372,40 +350,14 @@ extern "C" int32_t gnx_pna_conv_fwd(gnx_handle* h, const gnx_pna_fwd_args* a) {
   GNX_CHECK_ARG(a->params && a->x && a->Te && a->P && a->Q && a->A && a->out, "gnx_pna_conv_fwd: NULL array");
   const int per = 2 * (pre + post);
   const float* const* W = a->params;
-  // post-layer 0's weight images (x part + Weff(d), per tower) are split on side stream 2 while the node products and the
-  // edge pipeline run; the product then takes them as they are (GNX_GEMM_PRESPLIT)
-  const int post0_flags = GNX_GEMM_B_TRANS | (post > 1 ? GNX_GEMM_RELU : 0);
-  const int post0_rows = a->tile_rows == 96 ? 96 : 128;
-  size_t scratch = a->ws_bytes, r_post0 = 0, r_grouped = 0, r_dx = 0;
-  // (measured: cfg-5, four towers = twelve splits per layer: 56.79 -> 56.35 ms per step; cfg-2, one tower: 6.608 -> 6.630 ms --
-  // the fork / join events cost what the three 7-us splits saved -- so: ahead with two or more towers, in place with one)
-  bool ahead = T >= 2 && !h->on_side && N >= 4096 && a->ws != nullptr;
-  if (ahead) {
-    pna_ws_sizes(T, F, D, scratch, r_post0, r_grouped, r_dx);
-    ahead = scratch + (size_t)T * r_post0 <= a->ws_bytes;
-    if (!ahead) scratch = a->ws_bytes;
-  }
-  unsigned char* const ahead_base = reinterpret_cast<unsigned char*>(a->ws) + scratch;
-  auto post0_call = [&](int t, int extra_flags, void* ws, size_t ws_bytes) -> int32_t {
-    const int k = 4 + t * per + 2 * pre;
-    gnx_gemm_seg s2[2] = {seg(a->x + t * F, H, W[k], 13 * F, F),
-                          seg(a->A + (int64_t)t * 4 * F, (int64_t)T * 4 * F, a->weff[t], 4 * F, 4 * F)};
-    const int64_t strides[2] = {0, (int64_t)4 * F * F};
-    return gnx_gemm_grouped_rows(h, 2, s2, strides, D, N, F, W[k + 1], nullptr, 0, a->zs[0] + t * F, H, post0_flags | extra_flags,
-                                 a->dperm, a->tiles, a->ntiles, a->max_tiles, ws, ws_bytes, post0_rows);
-  };
-  if (ahead) {
-    GNX_TRY(gnx_side_begin_n(h, 2));
-    int32_t st = GNX_OK;
-    for (int t = 0; t < T && st == GNX_OK; ++t) st = post0_call(t, GNX_GEMM_SPLIT_ONLY, ahead_base + (size_t)t * r_post0, r_post0);
-    (void)gnx_side_end(h);
-    GNX_TRY(st);
-  }
+  // post-layer 0's weight images (x part + Weff(d), per tower) come from `im` where gnx_pna_split_all wrote them for this very
+  // shape; otherwise the product splits in place
+  const class_tiles ct = {a->dperm, a->tiles, a->ntiles, a->max_tiles};
   for (int t = 0; t < T; ++t) {
     const float* W0 = W[4 + t * per];
     gnx_gemm_seg sp = seg(a->x + t * F, H, W0, 3 * F, F), sq = seg(a->x + t * F, H, W0 + F, 3 * F, F);
-    GNX_TRY(gnx_gemm(h, 1, &sp, N, F, nullptr, nullptr, 0, a->P + t * F, H, GNX_GEMM_B_TRANS, a->ws, scratch));
-    GNX_TRY(gnx_gemm(h, 1, &sq, N, F, nullptr, nullptr, 0, a->Q + t * F, H, GNX_GEMM_B_TRANS, a->ws, scratch));
+    GNX_TRY(gnx_gemm(h, 1, &sp, N, F, nullptr, nullptr, 0, a->P + t * F, H, GNX_GEMM_B_TRANS, a->ws, a->ws_bytes));
+    GNX_TRY(gnx_gemm(h, 1, &sq, N, F, nullptr, nullptr, 0, a->Q + t * F, H, GNX_GEMM_B_TRANS, a->ws, a->ws_bytes));
   }
   // edge pipeline: message assembly -> pre layers 1.. -> scatter-aggregate.  With two pre layers (the reference's default)
   // it is ONE launch (gnx_pna_edge_fwd: h1 and the messages are written once and never read back, bit-identical results)
@@ -428,17 +380,13 @@ extern "C" int32_t gnx_pna_conv_fwd(gnx_handle* h, const gnx_pna_fwd_args* a) {
         const int k = 4 + t * per + 2 * i;
         gnx_gemm_seg s = seg(a->hs[i - 1] + t * F, H, W[k], F, F);
         GNX_TRY(gnx_gemm(h, 1, &s, E, F, W[k + 1], nullptr, 0, a->hs[i] + t * F, H,
-                         GNX_GEMM_B_TRANS | (i < pre - 1 ? GNX_GEMM_RELU : 0), a->ws, scratch));
+                         GNX_GEMM_B_TRANS | (i < pre - 1 ? GNX_GEMM_RELU : 0), a->ws, a->ws_bytes));
       }
     GNX_TRY(gnx_pna_aggregate_fwd(h, a->hs[pre - 1], a->rowptr, N, E, T, F, a->A));
   }
-  if (ahead) GNX_TRY(gnx_side_join_n(h, 2));
-  for (int t = 0; t < T; ++t) {
-    if (ahead)
-      GNX_TRY(post0_call(t, GNX_GEMM_PRESPLIT, ahead_base + (size_t)t * r_post0, r_post0));
-    else
-      GNX_TRY(post0_call(t, 0, a->ws, scratch));
-  }
+  for (int t = 0; t < T; ++t)
+    GNX_TRY(run_with_image(h, pna_post0_product(W, a->weff[t], T, F, pre, post, D, t, a->x, a->A, a->zs[0], a->tile_rows), N, ct,
+                           im ? im->post0[t] : nullptr, im ? &im->post0_rec[t] : nullptr, a->ws, a->ws_bytes));
   const int hidden_end = a->merged ? post - 1 : post;  // hidden layers 1 .. hidden_end-1 are evaluated one by one
   int zi = 0;
   for (int i = 1; i < hidden_end; ++i, ++zi)
@@ -450,6 +398,43 @@ extern "C" int32_t gnx_pna_conv_fwd(gnx_handle* h, const gnx_pna_fwd_args* a) {
     }
   gnx_gemm_seg sl = a->merged ? seg(a->zs[zi], H, a->Wm, H, H) : seg(a->zs[zi], H, W[2], H, H);
   return gnx_gemm(h, 1, &sl, N, H, a->merged ? a->bm : W[3], nullptr, 0, a->out, H, GNX_GEMM_B_TRANS, a->ws, a->ws_bytes);
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// The split weight images of every layer's three tiled products, once per step (behind gnx_pna_weight_only_all: they read
+// Weff): planned and laid out by pna_images_layout (gnx_gemm_plan.hpp), written by k_split_weights_batched.
+// ---------------------------------------------------------------------------------------------------------------
+extern "C" size_t gnx_pna_split_all_bytes(gnx_handle* h, int32_t L, int32_t T, int32_t F, int32_t pre_layers, int32_t post_layers,
+                                          int32_t D, int64_t N, int32_t tile_rows) {
+  if (h == nullptr || L < 1 || T < 1 || T > GNX_PNA_MAX_TOWERS || F < 1 || pre_layers < 1 || post_layers < 1 || D < 1 || N <= 0) return 0;
+  // (only the alignment of a weight enters a plan: every pointer is the aligned stand-in, F % 4 decides the rest)
+  const std::vector<const float*> params((size_t)L * (4 + T * 2 * (pre_layers + post_layers)), pna_stand_in());
+  const std::vector<const float*> weff((size_t)L * T, pna_stand_in());
+  return pna_images_layout(L, T, F, pre_layers, post_layers, D, N, tile_rows, params.data(), weff.data(), h->opt, h->num_cus, nullptr,
+                           nullptr, nullptr, nullptr);
+}
+
+extern "C" int32_t gnx_pna_split_all(gnx_handle* h, int32_t L, int32_t T, int32_t F, int32_t pre_layers, int32_t post_layers,
+                                     int32_t D, int64_t N, int32_t tile_rows, const float* const* params, const float* const* weff,
+                                     void* slab, size_t slab_bytes, gnx_pna_layer_images* out) {
+  GNX_CHECK_ARG(h && params && weff && out && L >= 1 && T >= 1 && T <= GNX_PNA_MAX_TOWERS && F >= 1 && pre_layers >= 1 &&
+                    post_layers >= 1 && D >= 1 && N >= 0, "gnx_pna_split_all: bad argument");
+  const size_t np = 4 + (size_t)T * 2 * (pre_layers + post_layers);
+  for (size_t i = 0; i < (size_t)L * np; ++i) GNX_CHECK_ARG(params[i], "gnx_pna_split_all: params[%zu] is NULL", i);
+  for (size_t i = 0; i < (size_t)L * T; ++i) GNX_CHECK_ARG(weff[i], "gnx_pna_split_all: weff[%zu] is NULL", i);
+  std::vector<gemm_split_problem> probs((size_t)3 * L * T);
+  int n = 0;
+  // first pass without the slab: how much the images of THESE weights need
+  const size_t need = pna_images_layout(L, T, F, pre_layers, post_layers, D, N, tile_rows, params, weff, h->opt, h->num_cus, nullptr,
+                                        out, nullptr, &n);
+  if (n == 0) return GNX_OK;  // (out[] holds no image)
+  GNX_CHECK_ARG(slab && (reinterpret_cast<uintptr_t>(slab) & 255) == 0, "gnx_pna_split_all: the slab must be 256-byte aligned");
+  if (slab_bytes < need) {
+    gnx_set_error("gnx_pna_split_all: slab of %zu bytes, the images need %zu", slab_bytes, need);
+    return GNX_E_WORKSPACE;
+  }
+  pna_images_layout(L, T, F, pre_layers, post_layers, D, N, tile_rows, params, weff, h->opt, h->num_cus, slab, out, probs.data(), &n);
+  return gnx_split_weights_batched(h, n, probs.data());
 }
 
 // ---------------------------------------------------------------------------------------------------------------

@@ -20,6 +20,7 @@ _USE_DEGREE_CLASSES = True  # bench.py, tests: off = the 4-segment post-layer 0,
 _NATIVE_LAYER_BWD = True    # tests: off = PNAConv launch by launch from Python, the reference of the native calls
 _FUSED_EDGE = True          # tests: off = the three-launch edge pipeline, the reference of the fused edge kernels
 _BATCH_WEIGHT_ONLY = True   # tests: off = per-layer weight-only work (WeightOnlyAhead), the reference of the batched form
+_SPLIT_ALL = True           # tests: off = every layer splits its weight images in place, the reference of gnx_pna_split_all
 
 
 def set_grad_in_place(enabled: bool) -> None:
@@ -70,6 +71,18 @@ def set_batch_weight_only(enabled: bool) -> None:
 
 def batch_weight_only_enabled() -> bool:
     return _BATCH_WEIGHT_ONLY
+
+
+def set_split_all(enabled: bool) -> None:
+    """A/B switch: with the batched weight-only work (``WeightOnlyAll``), the split weight images of every PNA layer's three
+    tiled products are written once per step in one launch (gnx_pna_split_all) and handed to the layers (default on); off =
+    every layer splits in place, in front of each product.  Bit-identical activations and input gradients."""
+    global _SPLIT_ALL
+    _SPLIT_ALL = bool(enabled)
+
+
+def split_all_enabled() -> bool:
+    return _SPLIT_ALL
 
 
 def grad_sinks(params: Sequence[torch.Tensor]) -> tuple:
@@ -405,10 +418,15 @@ class WeightOnlyAhead:
 class WeightOnlyAll:
     """``_pna_weight_only`` of ALL PNA layers of a model in three launches (gnx_pna_weight_only_all: batched 60-row products
     + batched Weff), issued on the library's side stream when enabled; ``get(l)`` orders the caller's stream behind them
-    (once) and returns layer l's (EE, Te, weffs, Wm, bm).  ``layers``: per layer (avg_deg_log, params) with identical
-    T / F / pre_layers / post_layers."""
+    (once) and returns layer l's (EE, Te, weffs, Wm, bm, images).  ``layers``: per layer (avg_deg_log, params) with identical
+    T / F / pre_layers / post_layers.
 
-    def __init__(self, BE, T, F, pre_layers, post_layers, layers, D):
+    With ``n_rows`` (the batch's node count) and ``tile_rows`` (the height of the forward's degree-class table) it also
+    owns the slab of split weight images of every layer's post-layer 0 / dA / dx products, written by gnx_pna_split_all
+    directly behind the weight-only launches (the images need Weff); ``images`` of ``get(l)`` is then layer l's
+    ``(PnaLayerImages, slab)``, else None.  The plans need both numbers: a product below 4096 rows reads no images."""
+
+    def __init__(self, BE, T, F, pre_layers, post_layers, layers, D, n_rows: int = 0, tile_rows: int = 0):
         import ctypes as C
         from . import _lib
         self.device = BE.device
@@ -428,17 +446,28 @@ class WeightOnlyAll:
         a_EE, a_Te, a_Wm, a_bm = ptrs(EE, L), ptrs(Te, L), ptrs(Wm, L), ptrs(bm, L)
         a_weff = (vp * (L * T))(*[weff[l, t].data_ptr() for l in range(L) for t in range(T)]) if weff is not None else None
         cast = lambda arr: None if arr is None else C.cast(arr, C.POINTER(vp))  # noqa: E731
+        lib = _lib.load()
+        slab, images = None, None
+        if _SPLIT_ALL and weff is not None and n_rows > 0:
+            need = lib.gnx_pna_split_all_bytes(_lib.handle(BE.device), L, T, F, pre_layers, post_layers, D, n_rows, tile_rows)
+            if need > 0:
+                slab = torch.empty(need, dtype=torch.uint8, device=BE.device)
+                images = (_lib.PnaLayerImages * L)()
 
         def launch():
             ops.check(_lib.load().gnx_pna_weight_only_all(
                 _lib.handle(BE.device), L, BE.data_ptr(), R, T, F, pre_layers, post_layers, D,
                 C.cast(avg, C.POINTER(C.c_float)), cast(params), int(merged), cast(a_EE), cast(a_Te), cast(a_weff),
                 cast(a_Wm), cast(a_bm)))
+            if slab is not None:
+                ops.check(lib.gnx_pna_split_all(_lib.handle(BE.device), L, T, F, pre_layers, post_layers, D, n_rows, tile_rows,
+                                                cast(params), cast(a_weff), slab.data_ptr(), slab.numel(), images))
 
-        keep = [BE, EE, Te, weff, Wm, bm] + [p for _, ps in layers for p in ps]
+        keep = [BE, EE, Te, weff, Wm, bm, slab] + [p for _, ps in layers for p in ps]
         ops.run_after_wgrads(BE, keep, launch)
         self.values = [(EE[l], Te[l], [weff[l, t] for t in range(T)] if weff is not None else [],
-                        Wm[l] if merged else None, bm[l] if merged else None) for l in range(L)]
+                        Wm[l] if merged else None, bm[l] if merged else None,
+                        (images[l], slab) if slab is not None else None) for l in range(L)]
         self._joined = False
 
     def get(self, l: int):
@@ -479,7 +508,8 @@ def _pna_forward_native(ctx, x, BE, pack, cfg, params, dc, prep):
     import ctypes as C
     from . import _lib
     T, F, pre_layers, post_layers, avg_deg_log = cfg[:5]
-    EE, Te, weffs, Wm, bm = prep
+    EE, Te, weffs, Wm, bm = prep[:5]
+    images = prep[5] if len(prep) > 5 else None  # (PnaLayerImages, slab) of WeightOnlyAll, kept for the backward
     N, H = x.shape
     E, D = pack.E, dc.D
     dev = x.device
@@ -518,12 +548,16 @@ def _pna_forward_native(ctx, x, BE, pack, cfg, params, dc, prep):
     # hint trips the range flag); the library falls back to the three-launch sequence when it is not eligible
     etiles = pack.edge_tiles(D - 1) if (_FUSED_EDGE and pre_layers == 2) else None
     a.etile_info, a.etile_w = (etiles[0].data_ptr(), etiles[1]) if etiles is not None else (None, 0)
-    ops.check(lib.gnx_pna_conv_fwd(_lib.handle(dev), C.byref(a)))
+    if images is None:
+        ops.check(lib.gnx_pna_conv_fwd(_lib.handle(dev), C.byref(a)))
+    else:
+        ops.check(lib.gnx_pna_conv_fwd_images(_lib.handle(dev), C.byref(a), C.byref(images[0])))
     amp, att = pack.degree_scalers(avg_deg_log)
     ctx.pack, ctx.cfg = pack, cfg[:5]
     ctx.n_h, ctx.n_z = len(hs), len(zs)
     ctx.sinks = grad_sinks(params)
     ctx.dc, ctx.weffs, ctx.Wm = dc, weffs, Wm
+    ctx.images = images
     ctx.save_for_backward(x, BE, EE, A, amp, att, *hs, *zs, *params)
     return out
 
@@ -606,7 +640,8 @@ def _pna_backward_native(ctx, dout, x, BE, EE, A, hs, zs, params, sinks, code_po
     a.ws, a.ws_bytes, a.acc_buf, a.dx = ws.data_ptr(), ws_bytes, acc.buf.data_ptr(), dx.data_ptr()
     etiles = pack.edge_tiles(D - 1) if (_FUSED_EDGE and pre_layers == 2) else None  # (the forward's table, cached on the pack)
     a.etile_info, a.etile_w = (etiles[0].data_ptr(), etiles[1]) if etiles is not None else (None, 0)
-    ops.pna_conv_bwd(a, dev)
+    images = getattr(ctx, "images", None)
+    ops.pna_conv_bwd(a, dev, images[0] if images is not None else None)
     # everything the side-stream launches touch stays alive until the join at the end of backward
     ops.keep_until_join(dev, [dout, x, BE, EE, A, *hs, *zs, *ctx.weffs, ctx.Wm, gbuf, gebuf, dA, pq, small, ws, acc.buf,
                               acc.slab, *params, *sinks])
@@ -650,7 +685,7 @@ class PNAConvFn(torch.autograd.Function):
         # from ``prep`` when the caller evaluated it ahead of time on the side stream (pna_weight_only_async)
         if prep is None:
             prep = _pna_weight_only(BE, T, F, pre_layers, post_layers, avg_deg_log, params, dc.D if dc is not None else 0)
-        EE, Te, weffs, Wm, bm = prep
+        EE, Te, weffs, Wm, bm = prep[:5]
         if _NATIVE_LAYER_BWD and dc is not None and x.is_cuda and pre_layers <= 8 and post_layers <= 8 and T <= 8:
             return _pna_forward_native(ctx, x, BE, pack, cfg, params, dc, prep)
         P, Q = _empty(N, H, x), _empty(N, H, x)

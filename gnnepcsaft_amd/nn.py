@@ -229,7 +229,8 @@ class PNAConv(Module):
         dc = edge_index.degree_classes(edge_index.max_degree_hint) if Fn.degree_classes_enabled() else None
         layers = [(c.aggr_module.avg_log(), c._params()) for c in convs]
         return Fn.WeightOnlyAll(edge_attr, c0.towers, c0.F_in, c0.pre_layers, c0.post_layers, layers,
-                                dc.D if dc is not None else 0)
+                                dc.D if dc is not None else 0, n_rows=edge_index.N if dc is not None else 0,
+                                tile_rows=dc.tile_rows_p if dc is not None else 0)
 
     def forward(self, x: torch.Tensor, edge_index: GraphPack, edge_attr: torch.Tensor, prepared=None, bond_acc=None,
                 layer_index: int = 0) -> torch.Tensor:

@@ -652,7 +652,7 @@ typedef struct {
   float *dTe, *dEE;                           /* [R,H], [R,F] */
   float *dWm, *dbm;                           /* [H,H], [H] (merged = 1) */
   float* dWeff;                               /* [T,D,F,4F] */
-  void* ws;                                   /* split weight images: >= gnx_pna_conv_bwd_workspace_bytes */
+  void* ws;                                   /* scratch of the products that split in place: >= gnx_pna_conv_bwd_workspace_bytes */
   size_t ws_bytes;
   float* acc_buf;                             /* [R,H] bond-embedding gradient accumulator shared by the model's layers */
   float* dx;                                  /* [N,H] out: gradient w.r.t. the layer input */
@@ -721,6 +721,45 @@ typedef struct {
 } gnx_pna_fwd_args;
 int32_t gnx_pna_conv_fwd(gnx_handle* h, const gnx_pna_fwd_args* args);
 
+/* ---- every PNA layer's split weight images, once per step, in one launch ------------------------------------- */
+/* The three tiled products of a PNAConv layer that read split weight images (post-layer 0 by degree class, dA = g Weff(d),
+ * the three-segment dx) depend on the parameters and on Weff(d) only, so their images can be written once, behind
+ * gnx_pna_weight_only_all, for all L layers and T towers: gnx_pna_split_all plans the three products per (layer, tower)
+ * for N rows exactly as the layers will (GNX_GEMM_SPLIT_ONLY), lays the images out in `slab` and writes them with
+ * ceil(problems / 32) launches on the bound stream.  A product whose plan reads no images (N < 4096, a single K-tile,
+ * GNX_OPT_GEMM_SPLIT = 0, an unaligned weight) takes no room and no part in the launch.  out[l] receives layer l's image
+ * pointers (NULL: none) and, per image, the record of what the plan said about it; gnx_pna_conv_fwd_images / _bwd_images
+ * take it next to the unchanged argument block.  A layer uses an image only if its own plan of that product now gives an
+ * equal record (then GNX_GEMM_PRESPLIT); otherwise it splits in place, as gnx_pna_conv_fwd / _bwd (images = NULL) always
+ * do.  The slab stays alive and unchanged until the last layer's backward has run. */
+typedef struct {
+  uint64_t image_bytes;   /* 0: the product reads no images */
+  int32_t classes, Npad, Kpad;
+  int32_t koff[5];        /* padded k offset of every segment; koff[nseg..4] = Kpad */
+  int32_t frag;           /* 1: fragment-major blocks, 0: tile-major */
+  int32_t bt;             /* 1: the weights are [n][k] (GNX_GEMM_B_TRANS) */
+} gnx_gemm_image;
+typedef struct {
+  void* post0[GNX_PNA_MAX_TOWERS];
+  void* dA[GNX_PNA_MAX_TOWERS];
+  void* dx[GNX_PNA_MAX_TOWERS];
+  gnx_gemm_image post0_rec[GNX_PNA_MAX_TOWERS], dA_rec[GNX_PNA_MAX_TOWERS], dx_rec[GNX_PNA_MAX_TOWERS];
+} gnx_pna_layer_images;
+/* bytes of the slab for L layers (every weight taken as 16-byte aligned: an upper bound); 0: nothing to split.  tile_rows:
+ * the height of the forward's degree-class table (gnx_pna_fwd_args.tile_rows). */
+size_t gnx_pna_split_all_bytes(gnx_handle* h, int32_t L, int32_t T, int32_t F, int32_t pre_layers, int32_t post_layers,
+                               int32_t D, int64_t N, int32_t tile_rows);
+/* params HOST [L * np], weff HOST [L * T] (as gnx_pna_weight_only_all's, whose weff this reads: same stream, behind it);
+ * out HOST [L]. */
+int32_t gnx_pna_split_all(gnx_handle* h, int32_t L, int32_t T, int32_t F, int32_t pre_layers, int32_t post_layers, int32_t D,
+                          int64_t N, int32_t tile_rows, const float* const* params, const float* const* weff, void* slab,
+                          size_t slab_bytes, gnx_pna_layer_images* out);
+/* how many split launches the handle has issued since gnx_create: per_call = k_split_weights (one product's images, directly in
+ * front of it: gnx_gemm* without GNX_GEMM_PRESPLIT), batched = k_split_weights_batched (gnx_pna_split_all).  Host counters. */
+int32_t gnx_gemm_split_counts(gnx_handle* h, int64_t* per_call, int64_t* batched);
+int32_t gnx_pna_conv_fwd_images(gnx_handle* h, const gnx_pna_fwd_args* args, const gnx_pna_layer_images* images);
+int32_t gnx_pna_conv_bwd_images(gnx_handle* h, const gnx_pna_bwd_args* args, const gnx_pna_layer_images* images);
+
 /* ---- small elementwise helpers used by the host module ----------------------------------------------------- */
 int32_t gnx_fill(gnx_handle* h, float* p, int64_t n, float v);
 /* p[i] *= v : the 1/world factor of the gradient average after the all-reduce (sum) of the flat gradient buffer
@@ -741,7 +780,7 @@ int32_t gnx_side_begin(gnx_handle* h);
 int32_t gnx_side_stream(gnx_handle* h, void** hip_stream);
 int32_t gnx_side_end(gnx_handle* h);
 int32_t gnx_side_join(gnx_handle* h);
-/* the same with an explicit side-stream index (0, 1 or 2 -- 2 is used by gnx_pna_conv_fwd / _bwd themselves; gnx_side_begin / gnx_side_join are index 0).  Stream 1 carries
+/* the same with an explicit side-stream index (0, 1 or 2 -- no library call forks onto 2; gnx_side_begin / gnx_side_join are index 0).  Stream 1 carries
  * the bond-table gradient chain of a conv layer's backward (by-code segment sum -> 60-row products), which feeds only
  * parameter gradients and the bond-embedding gradient consumed at the very end of backward. */
 int32_t gnx_side_stream_n(gnx_handle* h, int32_t which, void** hip_stream);
