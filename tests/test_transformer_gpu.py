@@ -2,7 +2,8 @@
 single layer forward and every gradient on identical inputs (1e-5 norm-wise relative; the layer has no ReLU / min / max
 events, so no row is excluded), attention dropout replayed from the kernel's own keep mask, bitwise-deterministic
 d(q|k|v), the whole model against the swapped fp64 reference model, trainer save / resume, a captured training step,
-and the InferenceEngine's refusal."""
+and the InferenceEngine's refusal.
+The attention kernels on their own, entry by entry at every thread and head layout: tests/test_attn_ops_gpu.py."""
 import copy
 import math
 import os
