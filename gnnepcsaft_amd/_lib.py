@@ -96,6 +96,22 @@ class PnaBwdArgs(C.Structure):
                 ("acc_buf", _vp), ("dx", _vp), ("flags", _i32), ("etile_w", _i32), ("etile_info", _vp)]
 
 
+PACK_MAX_AVG = 4
+PACK_CLASSES, PACK_CODE_INDEX, PACK_EDGE_TILES, PACK_TILED_SCAN = 1, 2, 4, 256
+
+
+class PackBatchArgs(C.Structure):
+    """gnx_pack_batch_args of include/gnx.h (same field order)."""
+    _fields_ = [("edge_index", _vp), ("edge_attr", _vp), ("batch", _vp), ("N", _i64), ("E", _i64), ("B", _i64),
+                ("K", _i32), ("bond_dims", _i32 * 16), ("max_degree", _i32), ("R", _i32), ("n_avg", _i32),
+                ("avg_deg_log", _f32 * PACK_MAX_AVG), ("tile_rows", _i32 * 3), ("edge_tile_w", _i32),
+                ("parts", C.c_uint32), ("_pad", _i32),
+                ("rowptr", _vp), ("perm", _vp), ("src", _vp), ("dst", _vp), ("colptr", _vp), ("cpos", _vp),
+                ("code", _vp), ("graph_ptr", _vp), ("amp", _vp * PACK_MAX_AVG), ("att", _vp * PACK_MAX_AVG),
+                ("dperm", _vp), ("cls_ptr", _vp), ("tiles", _vp * 3), ("ntiles", _vp * 3), ("code_pos", _vp),
+                ("code_ptr", _vp), ("edge_tiles", _vp), ("ws", _vp), ("ws_bytes", _sz)]
+
+
 class GemmImage(C.Structure):
     """gnx_gemm_image of include/gnx.h: what a product's plan says about its split weight images."""
     _fields_ = [("image_bytes", C.c_uint64), ("classes", _i32), ("Npad", _i32), ("Kpad", _i32), ("koff", _i32 * 5),
@@ -180,6 +196,10 @@ SIGNATURES = {
     "gnx_pna_aggregate_bwd": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _vp]),
     "gnx_edge_tiles_count": (_i32, [_i64, _i32]),
     "gnx_edge_tiles": (_i32, [_vp, _vp, _i64, _i64, _i32, _vp]),
+    "gnx_pack_batch_workspace_bytes": (_sz, [_i64, _i64, _i32, _i32]),
+    "gnx_pack_batch": (_i32, [_vp, C.POINTER(PackBatchArgs)]),
+    "gnx_pack_batch_scan_chunk": (_i64, []),
+    "gnx_pack_batch_scan_bound": (_i64, []),
     "gnx_pna_edge_fwd": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _i64, _i32, _i32, C.POINTER(_vp),
                                 C.POINTER(_vp), _vp, _vp, _vp]),
     "gnx_pna_edge_bwd": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _i64, _i32, _i32, _i32, C.POINTER(_vp), _vp, _vp,

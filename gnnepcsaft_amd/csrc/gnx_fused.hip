@@ -31,6 +31,7 @@
 // <= maxdeg and W = 65 - maxdeg a tile never exceeds 64 message rows.  A violated bound (a degree above the hint) sets
 // sticky range-flag bit 6 and the overflowing rows are dropped (no out-of-bounds access).
 #include "gnx_common.hpp"
+#include "gnx_pack_dev.hpp"
 #include "gnx_split.hpp"
 
 #include <cmath>
@@ -85,21 +86,7 @@ struct edge_fwd_args {
 __global__ void k_edge_tiles(const int* __restrict__ rowptr, int64_t N, int64_t E, int W, int ntiles,
                              int* __restrict__ info) {
   const int j = blockIdx.x * blockDim.x + threadIdx.x;
-  if (j > ntiles) return;
-  if (j == ntiles) {
-    info[2 * j] = (int)N;
-    info[2 * j + 1] = (int)E;
-    return;
-  }
-  const int64_t target = (int64_t)W * j;  // <= E by the choice of ntiles
-  int lo = 0, hi = (int)N;                // first n in [0, N] with rowptr[n] >= target (rowptr[N] = E)
-  while (lo < hi) {
-    const int mid = (lo + hi) >> 1;
-    if (rowptr[mid] >= target) hi = mid;
-    else lo = mid + 1;
-  }
-  info[2 * j] = lo;
-  info[2 * j + 1] = rowptr[lo];
+  if (j <= ntiles) gnx_edge_tile_entry(rowptr, N, E, W, ntiles, j, info);
 }
 
 extern "C" int32_t gnx_edge_tiles_count(int64_t E, int32_t tile_w) { return tile_w > 0 ? (int32_t)(E / tile_w) + 1 : 0; }

@@ -263,6 +263,123 @@ def pack_graph(edge_index: torch.Tensor, edge_attr: Optional[torch.Tensor], batc
     return g
 
 
+def pack_batch(edge_index: torch.Tensor, edge_attr: Optional[torch.Tensor], batch: Optional[torch.Tensor],
+               num_nodes: int, num_graphs: Optional[int] = None, bond_dims: Sequence[int] = (5, 6, 2), *,
+               max_degree_hint: int, R: Optional[int] = None, avg_deg_logs: Sequence[float] = (), classes: bool = True,
+               edge_tiles: Optional[bool] = None, validate: bool = True, tiled_scan: bool = False) -> GraphPack:
+    """``pack_graph`` plus everything its getters would build later, in one native call (gnx_pack_batch, 8 launches): the
+    returned GraphPack has ``max_degree_hint`` set and its degree classes (``classes``; PNA only), the bond-code index for
+    ``R`` codes, the edge tiles for the hint (``edge_tiles``, default = ``classes``) and the degree scalers of up to 4
+    ``avg_deg_logs`` in its caches, bit-identical to what the getters build; a getter asked for another ``R``, width or
+    ``avg_deg_log`` builds its own as before.  Every output and the workspace are views of one int32 allocation.
+    ``tiled_scan`` forces the multi-launch scan that batches above ``gnx_pack_batch_scan_bound()`` nodes take (tests)."""
+    dev = edge_index.device
+    lib, h = _lib.load(), handle(dev)
+    if edge_index.dtype != torch.int64 or edge_index.dim() != 2 or edge_index.size(0) != 2:
+        raise _lib.GnxError(_lib.GNX_E_INVALID, f"edge_index must be int64[2,E], got {edge_index.dtype} "
+                                                f"{tuple(edge_index.shape)}")
+    edge_index = edge_index.contiguous()
+    N, E = int(num_nodes), int(edge_index.size(1))
+    a = _lib.PackBatchArgs()
+    a.edge_index, a.N, a.E = edge_index.data_ptr(), N, E
+    if edge_attr is not None:
+        if edge_attr.dtype != torch.int64 or edge_attr.dim() != 2 or edge_attr.size(0) != E or \
+                edge_attr.size(1) != len(bond_dims):
+            raise _lib.GnxError(_lib.GNX_E_INVALID, f"edge_attr must be int64[E,{len(bond_dims)}], got "
+                                                    f"{edge_attr.dtype} {tuple(edge_attr.shape)}")
+        edge_attr = edge_attr.contiguous()
+        a.edge_attr, a.K = edge_attr.data_ptr(), len(bond_dims)
+        for k, d in enumerate(bond_dims):
+            a.bond_dims[k] = int(d)
+    g = GraphPack()
+    g.N, g.E, g.device, g._scalers, g._classes, g._code_index, g._edge_tiles = N, E, dev, {}, None, None, None
+    g.max_degree_hint = int(max_degree_hint)
+    if batch is not None:
+        if batch.dtype != torch.int64 or batch.dim() != 1 or batch.size(0) != N:
+            raise _lib.GnxError(_lib.GNX_E_INVALID, f"batch must be int64[N], got {batch.dtype} {tuple(batch.shape)}")
+        if num_graphs is None:
+            num_graphs = int(batch.max()) + 1 if N > 0 else 0
+        batch = batch.contiguous()
+        g.B, g.has_batch = int(num_graphs), True
+        a.batch, a.B = batch.data_ptr(), g.B
+    else:
+        g.B, g.has_batch = 1, False
+    # which parts, as the getters decide
+    D = g.max_degree_hint + 1
+    dc = None
+    if classes:
+        dc = g._classes = DegreeClasses()
+        dc.D = D
+    build_dc = classes and D <= DegreeClasses.MAX_D
+    build_ci = R is not None and R <= 64 and E > 0
+    if edge_tiles is None:
+        edge_tiles = classes
+    build_et = bool(edge_tiles) and g.max_degree_hint <= GraphPack.EDGE_TILE_MAX_DEG and E > 0 and N > 0
+    avgs = [float(v) for v in dict.fromkeys(float(v) for v in avg_deg_logs)][:_lib.PACK_MAX_AVG]
+    a.max_degree, a.R, a.n_avg = g.max_degree_hint, int(R) if R is not None else 0, len(avgs)
+    a.parts = (_lib.PACK_CLASSES if build_dc else 0) | (_lib.PACK_CODE_INDEX if build_ci else 0) | \
+        (_lib.PACK_EDGE_TILES if build_et else 0) | (_lib.PACK_TILED_SCAN if tiled_scan else 0)
+    # one allocation: every piece starts on a 256-byte boundary
+    sizes: List[Tuple[str, int]] = [("rowptr", N + 1), ("colptr", N + 1), ("perm", E), ("src", E), ("dst", E), ("cpos", E),
+                                    ("code", E), ("graph_ptr", g.B + 1)]
+    for i in range(len(avgs)):
+        sizes += [(f"amp{i}", N), (f"att{i}", N)]
+    rows = [0, 0, 0]
+    if build_dc:
+        rows[0], rows[1] = DegreeClasses.GEMM_ROWS, DegreeClasses.WGRAD_ROWS
+        dc.tile_rows_p = int(lib.gnx_gemm_tile_rows(h, N, 128))
+        dc.max_tiles, dc.max_chunks = N // rows[0] + D, N // rows[1] + D
+        sizes += [("dperm", max(N, 1)), ("cls_ptr", D + 1), ("tiles", 3 * dc.max_tiles), ("ntiles", 1),
+                  ("chunks", 3 * dc.max_chunks), ("nchunks", 1)]
+        if dc.tile_rows_p != rows[0]:
+            rows[2] = dc.tile_rows_p
+            dc.max_tiles_p = N // dc.tile_rows_p + D
+            sizes += [("tiles_p", 3 * dc.max_tiles_p), ("ntiles_p", 1)]
+    if build_ci:
+        sizes += [("code_pos", E), ("code_ptr", R + 1)]
+    if build_et:
+        w = GraphPack.EDGE_TILE_ROWS + 1 - max(g.max_degree_hint, 1)
+        a.edge_tile_w = w
+        sizes.append(("edge_tiles", 2 * (lib.gnx_edge_tiles_count(E, w) + 1)))
+    ws_bytes = lib.gnx_pack_batch_workspace_bytes(N, E, D if build_dc else 1, R if build_ci else 1)
+    sizes.append(("ws", (ws_bytes + 3) // 4))
+    off, total = {}, 0
+    for name, n in sizes:
+        off[name] = total
+        total += (n + 63) & ~63
+    buf = torch.empty(total, dtype=torch.int32, device=dev)
+    v = {name: buf[off[name]:off[name] + n] for name, n in sizes}
+    g.rowptr, g.colptr, g.perm, g.src, g.dst, g.cpos, g.code, g.graph_ptr = (
+        v["rowptr"], v["colptr"], v["perm"], v["src"], v["dst"], v["cpos"], v["code"], v["graph_ptr"])
+    for name in ("rowptr", "colptr", "perm", "src", "dst", "cpos", "code", "graph_ptr"):
+        setattr(a, name, v[name].data_ptr())
+    for i, key in enumerate(avgs):
+        amp, att = v[f"amp{i}"].view(torch.float32), v[f"att{i}"].view(torch.float32)
+        a.avg_deg_log[i], a.amp[i], a.att[i] = key, amp.data_ptr(), att.data_ptr()
+        g._scalers[key] = (amp, att)
+    if build_dc:
+        dc.dperm, dc.cls_ptr, dc.tiles, dc.ntiles, dc.chunks, dc.nchunks = (
+            v["dperm"], v["cls_ptr"], v["tiles"], v["ntiles"], v["chunks"], v["nchunks"])
+        if rows[2]:
+            dc.tiles_p, dc.ntiles_p = v["tiles_p"], v["ntiles_p"]
+        else:
+            dc.tiles_p, dc.ntiles_p, dc.max_tiles_p = dc.tiles, dc.ntiles, dc.max_tiles
+        a.dperm, a.cls_ptr = dc.dperm.data_ptr(), dc.cls_ptr.data_ptr()
+        for i, (t, n) in enumerate(((dc.tiles, dc.ntiles), (dc.chunks, dc.nchunks), (dc.tiles_p, dc.ntiles_p))):
+            a.tile_rows[i], a.tiles[i], a.ntiles[i] = rows[i], t.data_ptr(), n.data_ptr()
+    if build_ci:
+        a.code_pos, a.code_ptr = v["code_pos"].data_ptr(), v["code_ptr"].data_ptr()
+        g._code_index = (int(R), v["code_pos"], v["code_ptr"])
+    if build_et:
+        a.edge_tiles = v["edge_tiles"].data_ptr()
+        g._edge_tiles = (v["edge_tiles"], a.edge_tile_w)
+    a.ws, a.ws_bytes = v["ws"].data_ptr(), ws_bytes
+    check(lib.gnx_pack_batch(h, C.byref(a)))
+    if validate:
+        check_range(dev)
+    return g
+
+
 # ------------------------------------------------------------------------------------------------------------------
 # batch collation from a device-resident dataset (data/device.py)
 # ------------------------------------------------------------------------------------------------------------------

@@ -28,15 +28,22 @@ _LOWER = (1.0, 1.9, 50.0, -math.log10(0.9), math.log10(200.0))
 _UPPER = (25.0, 4.5, 550.0, -math.log10(0.0001), math.log10(5000.0))
 
 
-def _pack_of(graphs, validate: bool, max_degree_hint: Optional[int] = None) -> GraphPack:
-    """GraphPack of a Batch-like object, cached on it (the packer runs once per batch, like PyG's collate)."""
+def _pack_of(graphs, validate: bool, max_degree_hint: Optional[int] = None,
+             model: Optional["GNNePCSAFT"] = None) -> GraphPack:
+    """GraphPack of a Batch-like object, cached on it (the packer runs once per batch, like PyG's collate).  With a degree
+    hint and the model that will consume it, the pack comes from one native call with its getters' tables already built
+    (``ops.pack_batch``); without a hint the degree classes need the batch's maximum in-degree first (one sync)."""
     pack = getattr(graphs, "_gnx_pack", None)
     if pack is None or pack.device != graphs.x.device:
         batch = getattr(graphs, "batch", None)
         num_graphs = getattr(graphs, "num_graphs", None) if batch is not None else None
-        pack = ops.pack_graph(graphs.edge_index, graphs.edge_attr, batch, graphs.x.size(0), num_graphs,
-                              validate=validate)
-        pack.max_degree_hint = max_degree_hint
+        if max_degree_hint is not None and model is not None and graphs.x.is_cuda:
+            pack = ops.pack_batch(graphs.edge_index, graphs.edge_attr, batch, graphs.x.size(0), num_graphs,
+                                  max_degree_hint=max_degree_hint, validate=validate, **model.pack_spec())
+        else:
+            pack = ops.pack_graph(graphs.edge_index, graphs.edge_attr, batch, graphs.x.size(0), num_graphs,
+                                  validate=validate)
+            pack.max_degree_hint = max_degree_hint
         try:
             graphs._gnx_pack = pack
         except AttributeError:
@@ -79,7 +86,7 @@ class GNNePCSAFTL(LightningModuleLite):
 
     def training_step(self, graphs, batch_idx):  # pylint: disable=W0613
         target = self._target(graphs)
-        pack = _pack_of(graphs, self.model.validate_inputs, self.model.max_degree_hint)
+        pack = _pack_of(graphs, self.model.validate_inputs, self.model.max_degree_hint, self.model)
         pred = self(graphs.x, graphs.edge_index, graphs.edge_attr, graphs.batch, pack=pack)
         # ape = (pred - target) / target ; huber(ape, 0, delta=0.01) ; mape(pred, target) -- one kernel
         loss, both = Fn.HuberAPEFn.apply(pred, target, 0.01)
@@ -184,6 +191,14 @@ class GNNePCSAFT(torch.nn.Module):  # pylint: disable=R0902
         # readout mlp (reference :186-194, :226): Linear -> BN -> ReLU -> Linear -> BN -> ReLU -> Linear
         lin0, bn0, _, lin1, bn1, _, lin2 = self.mlp
         return lin2(bn1(lin1(bn0(lin0(h), relu=True)), relu=True))
+
+    def pack_spec(self) -> dict:
+        """What ``ops.pack_batch`` should build for this model's layers: the bond-code count, and for PNA the degree
+        classes (when enabled) and the degree scalers of the layers' ``avg_deg_log`` values."""
+        is_pna = isinstance(self.convs[0], gnn.PNAConv)
+        avgs = [conv.aggr_module.avg_log() for conv in self.convs] if is_pna else []
+        return {"R": int(self.edge_embed.combos.size(0)), "avg_deg_logs": avgs,
+                "classes": is_pna and Fn.degree_classes_enabled(), "edge_tiles": is_pna}
 
     def _bounds(self, device):
         key = (device, self.num_para)

@@ -389,6 +389,58 @@ int32_t gnx_pna_aggregate_bwd(gnx_handle* h, const float* dA, const float* m, co
  *   float operands 16-byte aligned. */
 int32_t gnx_edge_tiles_count(int64_t E, int32_t tile_w);
 int32_t gnx_edge_tiles(gnx_handle* h, const int32_t* rowptr, int64_t N, int64_t E, int32_t tile_w, int32_t* tile_info);
+
+/* ---- a whole batch's integer structure in one call ---------------------------------------------------------------
+ * gnx_pack_batch writes what gnx_pack_csr, gnx_feature_code (through perm), gnx_graph_ptr, gnx_degree_scalers (once per
+ * avg_deg_log), gnx_degree_classes, gnx_class_tiles (once per tile_rows), gnx_group_by_small_key (of code) and
+ * gnx_edge_tiles write, bit for bit (clamped values and sticky range-flag bits on bad input included), in 8 launches
+ * (15 above gnx_pack_batch_scan_bound() nodes) instead of 37.  No workgroup waits for another, nothing is read back and
+ * nothing synchronises: the call captures into a HIP graph.
+ *   edge_attr NULL: code = 0.  batch NULL: graph_ptr = [0, N] (B is ignored).
+ *   parts: which optional outputs to build; an unbuilt part's pointers may be NULL and its buffers are not touched.
+ *     GNX_PACK_CLASSES     dperm, cls_ptr and, per tile_rows[i] > 0, tiles[i] / ntiles[i]; D = max_degree + 1 <= 64 classes
+ *     GNX_PACK_CODE_INDEX  code_pos, code_ptr (R <= 64 codes; E > 0)
+ *     GNX_PACK_EDGE_TILES  edge_tiles with width edge_tile_w (E > 0, N > 0)
+ *     GNX_PACK_TILED_SCAN  use the multi-launch scan whatever N is (tests, measurements)
+ *   n_avg <= GNX_PACK_MAX_AVG degree-scaler pairs amp[i] / att[i] fp32[N] for avg_deg_log[i].
+ * Buffer sizes are those of the single-purpose entries.  ws: gnx_pack_batch_workspace_bytes(N, E, max_degree + 1, R). */
+#define GNX_PACK_MAX_AVG 4
+#define GNX_PACK_CLASSES 1u
+#define GNX_PACK_CODE_INDEX 2u
+#define GNX_PACK_EDGE_TILES 4u
+#define GNX_PACK_TILED_SCAN 256u
+typedef struct {
+  const int64_t* edge_index; /* [2, E] */
+  const int64_t* edge_attr;  /* [E, K] or NULL */
+  const int64_t* batch;      /* [N] or NULL */
+  int64_t N, E, B;
+  int32_t K;
+  int32_t bond_dims[16];
+  int32_t max_degree; /* the caller's bound of the in-degree: D - 1 */
+  int32_t R;
+  int32_t n_avg;
+  float avg_deg_log[GNX_PACK_MAX_AVG];
+  int32_t tile_rows[3]; /* 0 = no table */
+  int32_t edge_tile_w;
+  uint32_t parts;
+  int32_t _pad;
+  int32_t *rowptr, *perm, *src, *dst, *colptr, *cpos, *code, *graph_ptr;
+  float* amp[GNX_PACK_MAX_AVG];
+  float* att[GNX_PACK_MAX_AVG];
+  int32_t *dperm, *cls_ptr;
+  int32_t* tiles[3];
+  int32_t* ntiles[3];
+  int32_t *code_pos, *code_ptr;
+  int32_t* edge_tiles;
+  void* ws;
+  size_t ws_bytes;
+} gnx_pack_batch_args;
+size_t gnx_pack_batch_workspace_bytes(int64_t N, int64_t E, int32_t D, int32_t R);
+int32_t gnx_pack_batch(gnx_handle* h, const gnx_pack_batch_args* args);
+/* gnx_pack_batch scans its counters in tiles of gnx_pack_batch_scan_chunk() and folds the tile offsets into the next
+ * launch while a block can scan all tile sums, i.e. up to gnx_pack_batch_scan_bound() nodes */
+int64_t gnx_pack_batch_scan_chunk(void);
+int64_t gnx_pack_batch_scan_bound(void);
 /* backward of the same stage in one pass over the message gradient ge [E, T*F] (CSR order):
  *   gh1[p] = (ge[p] W1_t) * (h1[p] > 0);  dP[n] = sum of gh1 over the CSR row of n;  dTe[c] += sum of gh1 over the positions
  *   with bond code c  (R <= 64 codes; dTe [R, T*F] is ACCUMULATED with one atomic add per (code, column) and workgroup).
