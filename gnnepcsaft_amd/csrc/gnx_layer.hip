@@ -298,6 +298,141 @@ extern "C" int32_t gnx_pna_conv_bwd_images(gnx_handle* h, const gnx_pna_bwd_args
 }
 
 // ---------------------------------------------------------------------------------------------------------------
+// PNA post-layer 0 effective weights per in-degree class d (amp/att depend on d only):
+//   Weff[d][o][j] = W[o][F + j] + amp(d) W[o][5F + j] + att(d) W[o][9F + j],   o < F, j < 4F
+// and the matching weight gradient:  dW[:, F:5F] += sum_d dWeff[d], [:, 5F:9F] += sum_d amp(d) dWeff[d], ...
+// Up to GNX_SMALL_BATCH (layer, tower) pairs per launch (blockIdx.y = pair); gnx_pna_weff(_bwd) is a batch of one.
+// ---------------------------------------------------------------------------------------------------------------
+struct weff_batch_args {
+  const float* W[GNX_SMALL_BATCH];
+  float* out[GNX_SMALL_BATCH];
+  float avg_log[GNX_SMALL_BATCH];
+  int64_t ldw;
+  int F, D;
+};
+
+// Entry-wise within 4 u (|W1| + amp |W2| + att |W3|) of the exact value (u = 2^-24; tests/test_wgrad_gpu.py): the two
+// factors are evaluated in double and rounded once (<= 1 u each; fp32 logf-and-divide is up to 3 u), then each scaled
+// term carries its factor's and its product's rounding (2 u of the term) and the two additions one rounding each.  Once
+// per block instead of per thread: a block's 256 consecutive elements belong to at most 256 / (4 F^2) + 2 <= 66 classes.
+#define WEFF_BLOCK 256
+#define WEFF_CLS (WEFF_BLOCK / 4 + 2)
+__global__ void __launch_bounds__(WEFF_BLOCK) k_pna_weff_batched(weff_batch_args a) {
+  __shared__ float s_amp[WEFF_CLS], s_att[WEFF_CLS];
+  const int b = blockIdx.y;
+  const int F = a.F;
+  const int64_t first = (int64_t)blockIdx.x * WEFF_BLOCK;
+  int64_t i = first + threadIdx.x;
+  int64_t per = (int64_t)F * 4 * F;
+  const int d0 = (int)(first / per);
+  if (threadIdx.x < WEFF_CLS) {
+    const double dd = (double)(d0 + (int)threadIdx.x), avg = (double)a.avg_log[b];
+    s_amp[threadIdx.x] = (float)(log(dd + 1.0) / avg);
+    s_att[threadIdx.x] = (float)(avg / log(fmax(dd, 1.0) + 1.0));
+  }
+  __syncthreads();
+  if (i >= per * a.D) return;
+  int d = (int)(i / per);
+  int o = (int)((i % per) / (4 * F)), j = (int)(i % (4 * F));
+  const float amp = s_amp[d - d0], att = s_att[d - d0];
+  const float* w = a.W[b] + (int64_t)o * a.ldw;
+  a.out[b][i] = w[F + j] + amp * w[5 * F + j] + att * w[9 * F + j];
+}
+
+struct weff_bwd_batch_args {
+  const float* dWeff[GNX_SMALL_BATCH];
+  float* dW[GNX_SMALL_BATCH];
+  float avg_log[GNX_SMALL_BATCH];
+  int64_t lddw;
+  int F, D;
+};
+
+__global__ void k_pna_weff_bwd_batched(weff_bwd_batch_args a) {
+  const int b = blockIdx.y;
+  const int F = a.F;
+  int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  int64_t per = (int64_t)F * 4 * F;
+  if (i >= per) return;
+  int o = (int)(i / (4 * F)), j = (int)(i % (4 * F));
+  float s1 = 0.f, s2 = 0.f, s3 = 0.f;
+  const float avg_log = a.avg_log[b];
+  const float* dWeff = a.dWeff[b];
+  for (int d = 0; d < a.D; ++d) {
+    float dd = (float)d;
+    float amp = logf(dd + 1.0f) / avg_log;
+    float att = avg_log / logf(fmaxf(dd, 1.0f) + 1.0f);
+    float v = dWeff[(int64_t)d * per + i];
+    s1 += v;
+    s2 += amp * v;
+    s3 += att * v;
+  }
+  float* w = a.dW[b] + (int64_t)o * a.lddw;
+  w[F + j] += s1;
+  w[5 * F + j] += s2;
+  w[9 * F + j] += s3;
+}
+
+extern "C" int32_t gnx_pna_weff_bwd_batched(gnx_handle* h, int32_t n, const float* const* dWeff, int32_t F, int32_t D,
+                                            const float* avg_deg_log, float* const* dW, int64_t lddw) {
+  GNX_CHECK_ARG(h && dWeff && dW && avg_deg_log && n >= 0 && F > 0 && D > 0 && lddw >= 13 * F,
+                "gnx_pna_weff_bwd_batched: bad argument");
+  const int64_t cnt = (int64_t)F * 4 * F;
+  for (int32_t i0 = 0; i0 < n; i0 += GNX_SMALL_BATCH) {
+    weff_bwd_batch_args a;
+    const int m = n - i0 < GNX_SMALL_BATCH ? n - i0 : GNX_SMALL_BATCH;
+    for (int i = 0; i < GNX_SMALL_BATCH; ++i) {
+      const int k = i < m ? i0 + i : i0;
+      a.dWeff[i] = dWeff[k];
+      a.dW[i] = dW[k];
+      a.avg_log[i] = avg_deg_log[k];
+      GNX_CHECK_ARG(a.dWeff[i] && a.dW[i], "gnx_pna_weff_bwd_batched: NULL pointer at %d", k);
+    }
+    a.lddw = lddw;
+    a.F = F;
+    a.D = D;
+    hipLaunchKernelGGL(k_pna_weff_bwd_batched, dim3((unsigned)gnx_cdiv(cnt, 256), (unsigned)m), dim3(256), 0, h->stream, a);
+    GNX_LAUNCH_CHECK();
+  }
+  return GNX_OK;
+}
+
+// W[i] / out[i]: HOST arrays of n device pointers (post_nns[t][0].weight [F,13F] -> Weff [D,F,4F]); avg_log: HOST [n]
+extern "C" int32_t gnx_pna_weff_batched(gnx_handle* h, int32_t n, const float* const* W, int64_t ldw, int32_t F, int32_t D,
+                                        const float* avg_deg_log, float* const* Weff) {
+  GNX_CHECK_ARG(h && W && Weff && avg_deg_log && n >= 0 && F > 0 && D > 0 && ldw >= 13 * F, "gnx_pna_weff_batched: bad argument");
+  const int64_t cnt = (int64_t)F * 4 * F * D;
+  for (int32_t i0 = 0; i0 < n; i0 += GNX_SMALL_BATCH) {
+    weff_batch_args a;
+    const int m = n - i0 < GNX_SMALL_BATCH ? n - i0 : GNX_SMALL_BATCH;
+    for (int i = 0; i < GNX_SMALL_BATCH; ++i) {
+      const int k = i < m ? i0 + i : i0;
+      a.W[i] = W[k];
+      a.out[i] = Weff[k];
+      a.avg_log[i] = avg_deg_log[k];
+      GNX_CHECK_ARG(a.W[i] && a.out[i], "gnx_pna_weff_batched: NULL pointer at %d", k);
+    }
+    a.ldw = ldw;
+    a.F = F;
+    a.D = D;
+    hipLaunchKernelGGL(k_pna_weff_batched, dim3((unsigned)gnx_cdiv(cnt, 256), (unsigned)m), dim3(256), 0, h->stream, a);
+    GNX_LAUNCH_CHECK();
+  }
+  return GNX_OK;
+}
+
+extern "C" int32_t gnx_pna_weff(gnx_handle* h, const float* W, int64_t ldw, int32_t F, int32_t D, float avg_deg_log,
+                                float* Weff) {
+  GNX_CHECK_ARG(h && W && Weff && F > 0 && D > 0 && ldw >= 13 * F, "gnx_pna_weff: bad argument");
+  return gnx_pna_weff_batched(h, 1, &W, ldw, F, D, &avg_deg_log, &Weff);
+}
+
+extern "C" int32_t gnx_pna_weff_bwd(gnx_handle* h, const float* dWeff, int32_t F, int32_t D, float avg_deg_log,
+                                    float* dW, int64_t lddw) {
+  GNX_CHECK_ARG(h && dWeff && dW && F > 0 && D > 0 && lddw >= 13 * F, "gnx_pna_weff_bwd: bad argument");
+  return gnx_pna_weff_bwd_batched(h, 1, &dWeff, F, D, &avg_deg_log, &dW, lddw);
+}
+
+// ---------------------------------------------------------------------------------------------------------------
 // Weight-only part of a PNAConv forward (functional._pna_weight_only): EE = BondEmb W_enc^T + b_enc, Te (edge slice of
 // pre-layer 0 on the 60-row bond table), Weff(d) per tower, merged lin o last post layer.  5 + 3(T-1) tiny launches.
 // ---------------------------------------------------------------------------------------------------------------

@@ -109,30 +109,6 @@ __device__ __forceinline__ void pk_convert_edge(const int64_t* __restrict__ ei, 
   dO = (int)d;
 }
 
-__global__ void k_convert_edges(const int64_t* __restrict__ ei, int64_t E, int64_t N, int* __restrict__ src0,
-                                int* __restrict__ dst0, int* __restrict__ flag) {
-  int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (e >= E) return;
-  int s, d;
-  pk_convert_edge(ei, e, E, N, flag, s, d);
-  src0[e] = s;
-  dst0[e] = d;
-}
-
-__global__ void k_count_keys(const int* __restrict__ key, int64_t E, int* __restrict__ counts) {
-  int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (e < E) atomicAdd(&counts[key[e]], 1);
-}
-
-__global__ void k_fill_groups(const int* __restrict__ key, int64_t E, const int* __restrict__ ptr,
-                              int* __restrict__ cursor, int* __restrict__ items) {
-  int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (e >= E) return;
-  int k = key[e];
-  int pos = ptr[k] + atomicAdd(&cursor[k], 1);
-  items[pos] = (int)e;
-}
-
 // one thread per group: ascending insertion sort of its items (degrees are tiny for molecules; O(d^2) worst case)
 __device__ __forceinline__ void pk_sort_group(int* __restrict__ items, int b, int e) {
   for (int a = b + 1; a < e; ++a) {
@@ -146,86 +122,29 @@ __device__ __forceinline__ void pk_sort_group(int* __restrict__ items, int b, in
   }
 }
 
-__global__ void k_sort_groups(const int* __restrict__ ptr, int64_t N, int* __restrict__ items) {
-  int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= N) return;
-  pk_sort_group(items, ptr[i], ptr[i + 1]);
-}
-
-__global__ void k_gather_endpoints(const int* __restrict__ perm, const int* __restrict__ src0,
-                                   const int* __restrict__ dst0, int64_t E, int* __restrict__ src,
-                                   int* __restrict__ dst) {
-  int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (p >= E) return;
-  int e = perm[p];
-  src[p] = src0[e];
-  dst[p] = dst0[e];
-}
-
-static int32_t group_by_key(gnx_handle* h, const int* key, int64_t E, int64_t N, int* ptr, int* items, int* cursor,
-                            int* scan_ws) {
-  gnx_zero_ints(h, cursor, N > 0 ? N : 1);
-  if (E > 0) {
-    hipLaunchKernelGGL(k_count_keys, dim3((unsigned)gnx_cdiv(E, 256)), dim3(256), 0, h->stream, key, E, cursor);
-    GNX_LAUNCH_CHECK();
-  }
-  int32_t st = exclusive_scan(h, cursor, ptr, N, scan_ws, true);
-  if (st != GNX_OK) return st;
-  gnx_zero_ints(h, cursor, N > 0 ? N : 1);
-  if (E > 0) {
-    hipLaunchKernelGGL(k_fill_groups, dim3((unsigned)gnx_cdiv(E, 256)), dim3(256), 0, h->stream, key, E, ptr, cursor,
-                       items);
-    GNX_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_sort_groups, dim3((unsigned)gnx_cdiv(N, 256)), dim3(256), 0, h->stream, ptr, N, items);
-    GNX_LAUNCH_CHECK();
-  }
-  return GNX_OK;
-}
-
-extern "C" size_t gnx_pack_csr_workspace_bytes(int64_t N, int64_t E) {
-  if (N < 0) N = 0;
-  if (E < 0) E = 0;
-  size_t ints = 2 * (size_t)E + (size_t)N + 1 + scan_ws_ints_total(N) + 64;
-  return ints * sizeof(int);
-}
-
-extern "C" int32_t gnx_pack_csr(gnx_handle* h, const int64_t* edge_index, int64_t E, int64_t N, int32_t* rowptr,
-                                int32_t* perm, int32_t* src, int32_t* dst, int32_t* colptr, int32_t* cpos, void* ws,
-                                size_t ws_bytes) {
-  GNX_CHECK_ARG(h != nullptr, "gnx_pack_csr: handle is NULL");
-  GNX_CHECK_ARG(N >= 0 && E >= 0 && N < (1ll << 31) - 1 && E < (1ll << 31) - 1, "gnx_pack_csr: N=%lld E=%lld out of int32 range",
+// N nodes and E edges must leave room in int32; `who`: the entry that was called
+static int32_t check_sizes(const char* who, int64_t N, int64_t E) {
+  GNX_CHECK_ARG(N >= 0 && E >= 0 && N < (1ll << 31) - 1 && E < (1ll << 31) - 1, "%s: N=%lld E=%lld out of int32 range", who,
                 (long long)N, (long long)E);
-  GNX_CHECK_ARG(rowptr && colptr, "gnx_pack_csr: rowptr/colptr NULL");
-  GNX_CHECK_ARG(E == 0 || (edge_index && perm && src && dst && cpos), "gnx_pack_csr: NULL edge array with E>0");
-  if (ws_bytes < gnx_pack_csr_workspace_bytes(N, E) || (!ws && ws_bytes)) {
-    gnx_set_error("gnx_pack_csr: workspace %zu < %zu", ws_bytes, gnx_pack_csr_workspace_bytes(N, E));
-    return GNX_E_WORKSPACE;
-  }
-  GNX_CHECK_ARG(ws != nullptr, "gnx_pack_csr: workspace is NULL");
-  int* w = reinterpret_cast<int*>(ws);
-  int* src0 = w;
-  int* dst0 = src0 + E;
-  int* cursor = dst0 + E;
-  int* scan_ws = cursor + N + 1;
-  if (E > 0) {
-    hipLaunchKernelGGL(k_convert_edges, dim3((unsigned)gnx_cdiv(E, 256)), dim3(256), 0, h->stream, edge_index, E, N,
-                       src0, dst0, h->d_flag);
-    GNX_LAUNCH_CHECK();
-  }
-  int32_t st = group_by_key(h, dst0, E, N, rowptr, perm, cursor, scan_ws);
-  if (st != GNX_OK) return st;
-  if (E > 0) {
-    hipLaunchKernelGGL(k_gather_endpoints, dim3((unsigned)gnx_cdiv(E, 256)), dim3(256), 0, h->stream, perm, src0,
-                       dst0, E, src, dst);
-    GNX_LAUNCH_CHECK();
-  }
-  return group_by_key(h, src, E, N, colptr, cpos, cursor, scan_ws);
+  return GNX_OK;
 }
 
 // ---------------------------------------------------------------------------------------------------------------
 struct dims_t {
   int d[16];
 };
+
+// d = the K <= 16 vocabulary sizes dims (HOST), padded with 1; they must be positive and their product fit int32
+static int32_t fill_dims(const char* who, int32_t K, const int32_t* dims, dims_t& d) {
+  int64_t prod = 1;
+  for (int k = 0; k < 16; ++k) d.d[k] = (k < K) ? dims[k] : 1;
+  for (int k = 0; k < K; ++k) {
+    GNX_CHECK_ARG(dims[k] > 0, "%s: vocabulary size %d <= 0", who, k);
+    prod *= dims[k];
+    GNX_CHECK_ARG(prod < (1ll << 31), "%s: code space overflows int32", who);
+  }
+  return GNX_OK;
+}
 
 // mixed-radix code of feature row r; a feature outside its vocabulary counts as 0 and sets range-flag bit 1
 __device__ __forceinline__ int pk_feature_code(const int64_t* __restrict__ feat, int64_t r, int K, const dims_t& dims,
@@ -259,13 +178,8 @@ extern "C" int32_t gnx_feature_code(gnx_handle* h, const int64_t* feat, int64_t 
   GNX_CHECK_ARG(h && dims && K > 0 && K <= 16 && rows >= 0, "gnx_feature_code: bad argument");
   GNX_CHECK_ARG(rows == 0 || (feat && code), "gnx_feature_code: NULL array with rows>0");
   dims_t d;
-  int64_t prod = 1;
-  for (int k = 0; k < 16; ++k) d.d[k] = (k < K) ? dims[k] : 1;
-  for (int k = 0; k < K; ++k) {
-    GNX_CHECK_ARG(dims[k] > 0, "gnx_feature_code: dims[%d] <= 0", k);
-    prod *= dims[k];
-  }
-  GNX_CHECK_ARG(prod < (1ll << 31), "gnx_feature_code: code space overflows int32");
+  const int32_t st = fill_dims("gnx_feature_code", K, dims, d);
+  if (st != GNX_OK) return st;
   if (rows > 0) {
     hipLaunchKernelGGL(k_feature_code, dim3((unsigned)gnx_cdiv(rows, 256)), dim3(256), 0, h->stream, feat, rows, (int)K,
                        d, perm, code, h->d_flag);
@@ -330,141 +244,6 @@ extern "C" int32_t gnx_degree_scalers(gnx_handle* h, const int32_t* rowptr, int6
                      avg_deg_log, amp, att);
   GNX_LAUNCH_CHECK();
   return GNX_OK;
-}
-
-// ---------------------------------------------------------------------------------------------------------------
-// PNA post-layer 0 effective weights per in-degree class d (amp/att depend on d only):
-//   Weff[d][o][j] = W[o][F + j] + amp(d) W[o][5F + j] + att(d) W[o][9F + j],   o < F, j < 4F
-// and the matching weight gradient:  dW[:, F:5F] += sum_d dWeff[d], [:, 5F:9F] += sum_d amp(d) dWeff[d], ...
-// Up to GNX_SMALL_BATCH (layer, tower) pairs per launch (blockIdx.y = pair); gnx_pna_weff(_bwd) is a batch of one.
-// ---------------------------------------------------------------------------------------------------------------
-struct weff_batch_args {
-  const float* W[GNX_SMALL_BATCH];
-  float* out[GNX_SMALL_BATCH];
-  float avg_log[GNX_SMALL_BATCH];
-  int64_t ldw;
-  int F, D;
-};
-
-// Entry-wise within 4 u (|W1| + amp |W2| + att |W3|) of the exact value (u = 2^-24; tests/test_wgrad_gpu.py): the two
-// factors are evaluated in double and rounded once (<= 1 u each; fp32 logf-and-divide is up to 3 u), then each scaled
-// term carries its factor's and its product's rounding (2 u of the term) and the two additions one rounding each.  Once
-// per block instead of per thread: a block's 256 consecutive elements belong to at most 256 / (4 F^2) + 2 <= 66 classes.
-#define WEFF_BLOCK 256
-#define WEFF_CLS (WEFF_BLOCK / 4 + 2)
-__global__ void __launch_bounds__(WEFF_BLOCK) k_pna_weff_batched(weff_batch_args a) {
-  __shared__ float s_amp[WEFF_CLS], s_att[WEFF_CLS];
-  const int b = blockIdx.y;
-  const int F = a.F;
-  const int64_t first = (int64_t)blockIdx.x * WEFF_BLOCK;
-  int64_t i = first + threadIdx.x;
-  int64_t per = (int64_t)F * 4 * F;
-  const int d0 = (int)(first / per);
-  if (threadIdx.x < WEFF_CLS) {
-    const double dd = (double)(d0 + (int)threadIdx.x), avg = (double)a.avg_log[b];
-    s_amp[threadIdx.x] = (float)(log(dd + 1.0) / avg);
-    s_att[threadIdx.x] = (float)(avg / log(fmax(dd, 1.0) + 1.0));
-  }
-  __syncthreads();
-  if (i >= per * a.D) return;
-  int d = (int)(i / per);
-  int o = (int)((i % per) / (4 * F)), j = (int)(i % (4 * F));
-  const float amp = s_amp[d - d0], att = s_att[d - d0];
-  const float* w = a.W[b] + (int64_t)o * a.ldw;
-  a.out[b][i] = w[F + j] + amp * w[5 * F + j] + att * w[9 * F + j];
-}
-
-struct weff_bwd_batch_args {
-  const float* dWeff[GNX_SMALL_BATCH];
-  float* dW[GNX_SMALL_BATCH];
-  float avg_log[GNX_SMALL_BATCH];
-  int64_t lddw;
-  int F, D;
-};
-
-__global__ void k_pna_weff_bwd_batched(weff_bwd_batch_args a) {
-  const int b = blockIdx.y;
-  const int F = a.F;
-  int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  int64_t per = (int64_t)F * 4 * F;
-  if (i >= per) return;
-  int o = (int)(i / (4 * F)), j = (int)(i % (4 * F));
-  float s1 = 0.f, s2 = 0.f, s3 = 0.f;
-  const float avg_log = a.avg_log[b];
-  const float* dWeff = a.dWeff[b];
-  for (int d = 0; d < a.D; ++d) {
-    float dd = (float)d;
-    float amp = logf(dd + 1.0f) / avg_log;
-    float att = avg_log / logf(fmaxf(dd, 1.0f) + 1.0f);
-    float v = dWeff[(int64_t)d * per + i];
-    s1 += v;
-    s2 += amp * v;
-    s3 += att * v;
-  }
-  float* w = a.dW[b] + (int64_t)o * a.lddw;
-  w[F + j] += s1;
-  w[5 * F + j] += s2;
-  w[9 * F + j] += s3;
-}
-
-extern "C" int32_t gnx_pna_weff_bwd_batched(gnx_handle* h, int32_t n, const float* const* dWeff, int32_t F, int32_t D,
-                                            const float* avg_deg_log, float* const* dW, int64_t lddw) {
-  GNX_CHECK_ARG(h && dWeff && dW && avg_deg_log && n >= 0 && F > 0 && D > 0 && lddw >= 13 * F,
-                "gnx_pna_weff_bwd_batched: bad argument");
-  const int64_t cnt = (int64_t)F * 4 * F;
-  for (int32_t i0 = 0; i0 < n; i0 += GNX_SMALL_BATCH) {
-    weff_bwd_batch_args a;
-    const int m = n - i0 < GNX_SMALL_BATCH ? n - i0 : GNX_SMALL_BATCH;
-    for (int i = 0; i < GNX_SMALL_BATCH; ++i) {
-      const int k = i < m ? i0 + i : i0;
-      a.dWeff[i] = dWeff[k];
-      a.dW[i] = dW[k];
-      a.avg_log[i] = avg_deg_log[k];
-      GNX_CHECK_ARG(a.dWeff[i] && a.dW[i], "gnx_pna_weff_bwd_batched: NULL pointer at %d", k);
-    }
-    a.lddw = lddw;
-    a.F = F;
-    a.D = D;
-    hipLaunchKernelGGL(k_pna_weff_bwd_batched, dim3((unsigned)gnx_cdiv(cnt, 256), (unsigned)m), dim3(256), 0, h->stream, a);
-    GNX_LAUNCH_CHECK();
-  }
-  return GNX_OK;
-}
-
-// W[i] / out[i]: HOST arrays of n device pointers (post_nns[t][0].weight [F,13F] -> Weff [D,F,4F]); avg_log: HOST [n]
-extern "C" int32_t gnx_pna_weff_batched(gnx_handle* h, int32_t n, const float* const* W, int64_t ldw, int32_t F, int32_t D,
-                                        const float* avg_deg_log, float* const* Weff) {
-  GNX_CHECK_ARG(h && W && Weff && avg_deg_log && n >= 0 && F > 0 && D > 0 && ldw >= 13 * F, "gnx_pna_weff_batched: bad argument");
-  const int64_t cnt = (int64_t)F * 4 * F * D;
-  for (int32_t i0 = 0; i0 < n; i0 += GNX_SMALL_BATCH) {
-    weff_batch_args a;
-    const int m = n - i0 < GNX_SMALL_BATCH ? n - i0 : GNX_SMALL_BATCH;
-    for (int i = 0; i < GNX_SMALL_BATCH; ++i) {
-      const int k = i < m ? i0 + i : i0;
-      a.W[i] = W[k];
-      a.out[i] = Weff[k];
-      a.avg_log[i] = avg_deg_log[k];
-      GNX_CHECK_ARG(a.W[i] && a.out[i], "gnx_pna_weff_batched: NULL pointer at %d", k);
-    }
-    a.ldw = ldw;
-    a.F = F;
-    a.D = D;
-    hipLaunchKernelGGL(k_pna_weff_batched, dim3((unsigned)gnx_cdiv(cnt, 256), (unsigned)m), dim3(256), 0, h->stream, a);
-    GNX_LAUNCH_CHECK();
-  }
-  return GNX_OK;
-}
-
-extern "C" int32_t gnx_pna_weff(gnx_handle* h, const float* W, int64_t ldw, int32_t F, int32_t D, float avg_deg_log,
-                                float* Weff) {
-  GNX_CHECK_ARG(h && W && Weff && F > 0 && D > 0 && ldw >= 13 * F, "gnx_pna_weff: bad argument");
-  return gnx_pna_weff_batched(h, 1, &W, ldw, F, D, &avg_deg_log, &Weff);
-}
-
-extern "C" int32_t gnx_pna_weff_bwd(gnx_handle* h, const float* dWeff, int32_t F, int32_t D, float avg_deg_log,
-                                    float* dW, int64_t lddw) {
-  GNX_CHECK_ARG(h && dWeff && dW && F > 0 && D > 0 && lddw >= 13 * F, "gnx_pna_weff_bwd: bad argument");
-  return gnx_pna_weff_bwd_batched(h, 1, &dWeff, F, D, &avg_deg_log, &dW, lddw);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -567,27 +346,35 @@ extern "C" size_t gnx_degree_classes_workspace_bytes(int64_t N, int32_t D) {
   return ints * sizeof(int);
 }
 
+// Stable grouping of n items by a key in [0, D), D <= DC_MAX_CLASSES: the in-degree of node i (rowptr) or keys[i] (rowptr
+// NULL).  pos int32[n] = item ids sorted by key, ascending inside a key; bounds int32[D+1].  Per-block histograms -> scan
+// -> stable ranks.  ws: gnx_degree_classes_workspace_bytes(n, D); a shorter one is GNX_E_WORKSPACE of the entry `who`.
+static int32_t group_small_keys(gnx_handle* h, const char* who, const int* rowptr, const int* keys, int64_t n, int D,
+                                int* pos, int* bounds, void* ws, size_t ws_bytes) {
+  if (ws_bytes < gnx_degree_classes_workspace_bytes(n, D) || !ws) {
+    gnx_set_error("%s: workspace %zu < %zu", who, ws_bytes, gnx_degree_classes_workspace_bytes(n, D));
+    return GNX_E_WORKSPACE;
+  }
+  int nblocks = (int)gnx_cdiv(n > 0 ? n : 1, DC_BLOCK);
+  int* blockhist = reinterpret_cast<int*>(ws);
+  int* blockoff = blockhist + (size_t)D * nblocks + 1;
+  int* scan_ws = blockoff + (size_t)D * nblocks + 1;
+  hipLaunchKernelGGL(k_dc_hist, dim3(nblocks), dim3(DC_BLOCK), 0, h->stream, rowptr, keys, n, D, nblocks, blockhist,
+                     h->d_flag);
+  GNX_LAUNCH_CHECK();
+  int32_t st = exclusive_scan(h, blockhist, blockoff, (int64_t)D * nblocks, scan_ws, false);
+  if (st != GNX_OK) return st;
+  hipLaunchKernelGGL(k_dc_fill, dim3(nblocks), dim3(DC_BLOCK), 0, h->stream, rowptr, keys, n, D, nblocks, blockoff, pos,
+                     bounds);
+  GNX_LAUNCH_CHECK();
+  return GNX_OK;
+}
+
 extern "C" int32_t gnx_degree_classes(gnx_handle* h, const int32_t* rowptr, int64_t N, int32_t D, int32_t* dperm,
                                       int32_t* cls_ptr, void* ws, size_t ws_bytes) {
   GNX_CHECK_ARG(h && rowptr && cls_ptr && N >= 0 && D >= 1 && D <= DC_MAX_CLASSES && (N == 0 || dperm),
                 "gnx_degree_classes: bad argument (D must be in [1,%d])", DC_MAX_CLASSES);
-  if (ws_bytes < gnx_degree_classes_workspace_bytes(N, D) || !ws) {
-    gnx_set_error("gnx_degree_classes: workspace %zu < %zu", ws_bytes, gnx_degree_classes_workspace_bytes(N, D));
-    return GNX_E_WORKSPACE;
-  }
-  int nblocks = (int)gnx_cdiv(N > 0 ? N : 1, DC_BLOCK);
-  int* blockhist = reinterpret_cast<int*>(ws);
-  int* blockoff = blockhist + (size_t)D * nblocks + 1;
-  int* scan_ws = blockoff + (size_t)D * nblocks + 1;
-  hipLaunchKernelGGL(k_dc_hist, dim3(nblocks), dim3(DC_BLOCK), 0, h->stream, rowptr, (const int*)nullptr, N, (int)D,
-                     nblocks, blockhist, h->d_flag);
-  GNX_LAUNCH_CHECK();
-  int32_t st = exclusive_scan(h, blockhist, blockoff, (int64_t)D * nblocks, scan_ws, false);
-  if (st != GNX_OK) return st;
-  hipLaunchKernelGGL(k_dc_fill, dim3(nblocks), dim3(DC_BLOCK), 0, h->stream, rowptr, (const int*)nullptr, N, (int)D,
-                     nblocks, blockoff, dperm, cls_ptr);
-  GNX_LAUNCH_CHECK();
-  return GNX_OK;
+  return group_small_keys(h, "gnx_degree_classes", rowptr, nullptr, N, D, dperm, cls_ptr, ws, ws_bytes);
 }
 
 // Stable grouping of E items by a small integer key (0 <= key < R <= 64): pos int32[E] = item ids sorted by key
@@ -597,23 +384,7 @@ extern "C" int32_t gnx_group_by_small_key(gnx_handle* h, const int32_t* keys, in
                                           int32_t* ptr, void* ws, size_t ws_bytes) {
   GNX_CHECK_ARG(h && ptr && E >= 0 && R >= 1 && R <= DC_MAX_CLASSES && (E == 0 || (keys && pos)),
                 "gnx_group_by_small_key: bad argument (R must be in [1,%d])", DC_MAX_CLASSES);
-  if (ws_bytes < gnx_degree_classes_workspace_bytes(E, R) || !ws) {
-    gnx_set_error("gnx_group_by_small_key: workspace %zu < %zu", ws_bytes, gnx_degree_classes_workspace_bytes(E, R));
-    return GNX_E_WORKSPACE;
-  }
-  int nblocks = (int)gnx_cdiv(E > 0 ? E : 1, DC_BLOCK);
-  int* blockhist = reinterpret_cast<int*>(ws);
-  int* blockoff = blockhist + (size_t)R * nblocks + 1;
-  int* scan_ws = blockoff + (size_t)R * nblocks + 1;
-  hipLaunchKernelGGL(k_dc_hist, dim3(nblocks), dim3(DC_BLOCK), 0, h->stream, (const int*)nullptr, keys, E, (int)R,
-                     nblocks, blockhist, h->d_flag);
-  GNX_LAUNCH_CHECK();
-  int32_t st = exclusive_scan(h, blockhist, blockoff, (int64_t)R * nblocks, scan_ws, false);
-  if (st != GNX_OK) return st;
-  hipLaunchKernelGGL(k_dc_fill, dim3(nblocks), dim3(DC_BLOCK), 0, h->stream, (const int*)nullptr, keys, E, (int)R,
-                     nblocks, blockoff, pos, ptr);
-  GNX_LAUNCH_CHECK();
-  return GNX_OK;
+  return group_small_keys(h, "gnx_group_by_small_key", nullptr, keys, E, R, pos, ptr, ws, ws_bytes);
 }
 
 // tile table: for class c, ceil(n_c / tile_rows) tiles of (first position in dperm, #rows, class); ntiles[0] = count.
@@ -672,8 +443,9 @@ extern "C" int32_t gnx_class_tiles(gnx_handle* h, const int32_t* cls_ptr, int32_
 //   7 offsets   one workgroup per class / code: its row of per-block counts -> offsets inside the class, and its total
 //   8 tables    every block sums the <= 64 totals below its class itself.  dperm and code positions from the offsets
 //               (with cls_ptr / code ptr); class tile tables; edge tiles from rowptr
-// Above PB_SCAN_MAX_N nodes the tile sums no longer fit one block's scan: launches 3 and 4 become exclusive_scan (twice
-// three launches and a total) and a fill that reads rowptr.
+// Above PB_SCAN_MAX_N nodes the tile sums no longer fit one block's scan: launch 3 becomes an exclusive_scan of each
+// counter array (three levels of tiles, two adds and the total: 6 launches each) and launch 4 a fill that reads rowptr.
+// gnx_pack_csr (at the end of this file) is launches 1 to 6 with no optional part.
 //
 // A single workgroup per counter array (4096 counts per round, next round's loads in flight) was measured against the
 // tiled form and lost at every size: 44 us against 21 us for both arrays at N = 81 920, 171 us against 26 us at 327 680
@@ -858,8 +630,8 @@ extern "C" size_t gnx_pack_batch_workspace_bytes(int64_t N, int64_t E, int32_t D
 extern "C" int32_t gnx_pack_batch(gnx_handle* h, const gnx_pack_batch_args* g) {
   GNX_CHECK_ARG(h && g, "gnx_pack_batch: NULL argument");
   const int64_t N = g->N, E = g->E;
-  GNX_CHECK_ARG(N >= 0 && E >= 0 && N < (1ll << 31) - 1 && E < (1ll << 31) - 1, "gnx_pack_batch: N=%lld E=%lld out of int32 range",
-                (long long)N, (long long)E);
+  int32_t st = check_sizes("gnx_pack_batch", N, E);
+  if (st != GNX_OK) return st;
   GNX_CHECK_ARG(g->rowptr && g->colptr && g->graph_ptr, "gnx_pack_batch: rowptr/colptr/graph_ptr NULL");
   GNX_CHECK_ARG(E == 0 || (g->edge_index && g->perm && g->src && g->dst && g->cpos && g->code),
                 "gnx_pack_batch: NULL edge array with E>0");
@@ -871,13 +643,7 @@ extern "C" int32_t gnx_pack_batch(gnx_handle* h, const gnx_pack_batch_args* g) {
   pb_args a = {};
   if (g->edge_attr) {
     GNX_CHECK_ARG(g->K > 0 && g->K <= 16, "gnx_pack_batch: K must be in [1,16]");
-    int64_t prod = 1;
-    for (int k = 0; k < 16; ++k) a.dims.d[k] = (k < g->K) ? g->bond_dims[k] : 1;
-    for (int k = 0; k < g->K; ++k) {
-      GNX_CHECK_ARG(g->bond_dims[k] > 0, "gnx_pack_batch: bond_dims[%d] <= 0", k);
-      prod *= g->bond_dims[k];
-      GNX_CHECK_ARG(prod < (1ll << 31), "gnx_pack_batch: code space overflows int32");
-    }
+    if ((st = fill_dims("gnx_pack_batch", g->K, g->bond_dims, a.dims)) != GNX_OK) return st;
   }
   for (int k = 0; k < g->n_avg; ++k) {
     GNX_CHECK_ARG(N == 0 || (g->amp[k] && g->att[k]), "gnx_pack_batch: amp/att[%d] NULL", k);
@@ -967,4 +733,35 @@ extern "C" int32_t gnx_pack_batch(gnx_handle* h, const gnx_pack_batch_args* g) {
     GNX_LAUNCH_CHECK();
   }
   return GNX_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// gnx_pack_csr: the CSR alone, by launches 1 to 6 of gnx_pack_batch.  The bond codes (all 0) and graph_ptr = [0, N] that
+// those launches write anyway go behind the batch workspace.
+// ---------------------------------------------------------------------------------------------------------------
+extern "C" size_t gnx_pack_csr_workspace_bytes(int64_t N, int64_t E) {
+  if (E < 0) E = 0;
+  return gnx_pack_batch_workspace_bytes(N, E, 1, 1) + (pb_pad((size_t)E) + 2) * sizeof(int);
+}
+
+extern "C" int32_t gnx_pack_csr(gnx_handle* h, const int64_t* edge_index, int64_t E, int64_t N, int32_t* rowptr,
+                                int32_t* perm, int32_t* src, int32_t* dst, int32_t* colptr, int32_t* cpos, void* ws,
+                                size_t ws_bytes) {
+  GNX_CHECK_ARG(h != nullptr, "gnx_pack_csr: handle is NULL");
+  const int32_t st = check_sizes("gnx_pack_csr", N, E);
+  if (st != GNX_OK) return st;
+  GNX_CHECK_ARG(rowptr && colptr, "gnx_pack_csr: rowptr/colptr NULL");
+  GNX_CHECK_ARG(E == 0 || (edge_index && perm && src && dst && cpos), "gnx_pack_csr: NULL edge array with E>0");
+  if (ws_bytes < gnx_pack_csr_workspace_bytes(N, E) || (!ws && ws_bytes)) {
+    gnx_set_error("gnx_pack_csr: workspace %zu < %zu", ws_bytes, gnx_pack_csr_workspace_bytes(N, E));
+    return GNX_E_WORKSPACE;
+  }
+  GNX_CHECK_ARG(ws != nullptr, "gnx_pack_csr: workspace is NULL");
+  gnx_pack_batch_args a = {};
+  a.edge_index = edge_index, a.N = N, a.E = E;
+  a.rowptr = rowptr, a.perm = perm, a.src = src, a.dst = dst, a.colptr = colptr, a.cpos = cpos;
+  a.ws = ws, a.ws_bytes = gnx_pack_batch_workspace_bytes(N, E, 1, 1);
+  a.code = reinterpret_cast<int32_t*>(static_cast<char*>(ws) + a.ws_bytes);
+  a.graph_ptr = a.code + pb_pad((size_t)E);
+  return gnx_pack_batch(h, &a);
 }

@@ -118,15 +118,12 @@ class InferenceEngine:
                  batch: Optional[torch.Tensor] = None, pack: Optional[GraphPack] = None,
                  validate: bool = True) -> torch.Tensor:
         """fp32[B, P] (B = 1 with keepdim semantics when ``batch`` is None), same values as ``model.eval()(…)``."""
-        if pack is None and self.max_degree is not None:
-            # everything the layers ask of the pack in one native call; the grouped post-layer product needs no scalers
-            scalers = self.is_pna and self.max_degree + 1 > ops.DegreeClasses.MAX_D
+        if pack is None:
+            # with a degree bound, everything the layers ask of the pack; the grouped post-layer product needs no scalers
+            scalers = self.is_pna and self.max_degree is not None and self.max_degree + 1 > ops.DegreeClasses.MAX_D
             pack = ops.pack_batch(edge_index, edge_attr, batch, x.size(0), None, max_degree_hint=self.max_degree,
                                   avg_deg_logs=[lay["avg"] for lay in self.layers] if scalers else (),
                                   classes=self.is_pna, validate=validate)
-        elif pack is None:
-            pack = ops.pack_graph(edge_index, edge_attr, batch, x.size(0), None, validate=validate)
-            pack.max_degree_hint = self.max_degree
         h = ops.embed_sum_fwd(x, self.atom_table, self.atom_offsets)
         for lay in self.layers:
             h = self._pna_layer(h, pack, lay) if self.is_pna else self._gine_layer(h, pack, lay)

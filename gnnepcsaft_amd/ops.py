@@ -87,13 +87,33 @@ class GraphPack:
     EDGE_TILE_ROWS = 64     # message rows of one tile of the fused edge kernels (gnx_pna_edge_fwd)
     EDGE_TILE_MAX_DEG = 16  # above this in-degree bound the tiles would be mostly padding: unfused kernels instead
 
-    def edge_tiles(self, max_degree: int) -> Optional[Tuple[torch.Tensor, int]]:
-        """(tile_info int32[2 (count + 1)], tile width) of gnx_edge_tiles for in-degrees <= ``max_degree`` (tile j = the
-        nodes whose first CSR position lies in [w j, w (j + 1)), w = 65 - max_degree, so no tile exceeds 64 message
-        rows); None when the bound is too large for the fused edge kernels or the batch has no edges.  Built once."""
-        if max_degree > GraphPack.EDGE_TILE_MAX_DEG or self.E == 0 or self.N == 0:
+    def __init__(self, N: int, E: int, B: int, has_batch: bool, device: torch.device,
+                 max_degree_hint: Optional[int] = None):
+        self.N, self.E, self.B, self.has_batch, self.device = N, E, B, has_batch, device
+        self.max_degree_hint = max_degree_hint
+        self.rowptr = self.perm = self.src = self.dst = self.colptr = self.cpos = self.code = self.graph_ptr = None
+        self._scalers, self._classes, self._code_index, self._edge_tiles = {}, None, None, None
+
+    @staticmethod
+    def edge_tile_width(max_degree: int) -> Optional[int]:
+        """Nodes' first CSR positions per edge tile for in-degrees <= ``max_degree``: 65 - max_degree, so no tile exceeds
+        64 message rows; None when the bound is too large for the fused edge kernels."""
+        if max_degree > GraphPack.EDGE_TILE_MAX_DEG:
             return None
-        w = GraphPack.EDGE_TILE_ROWS + 1 - max(int(max_degree), 1)
+        return GraphPack.EDGE_TILE_ROWS + 1 - max(int(max_degree), 1)
+
+    @staticmethod
+    def has_code_index(R: int) -> bool:
+        """Whether positions can be grouped by R bond codes (gnx_group_by_small_key takes at most 64 keys)."""
+        return R <= 64
+
+    def edge_tiles(self, max_degree: int) -> Optional[Tuple[torch.Tensor, int]]:
+        """(tile_info int32[2 (count + 1)], tile width w) of gnx_edge_tiles for in-degrees <= ``max_degree`` (tile j = the
+        nodes whose first CSR position lies in [w j, w (j + 1)), w = ``edge_tile_width``); None when the bound is too
+        large for the fused edge kernels or the batch has no edges.  Built once."""
+        w = GraphPack.edge_tile_width(max_degree)
+        if w is None or self.E == 0 or self.N == 0:
+            return None
         hit = self._edge_tiles
         if hit is None or hit[1] != w:
             lib = _lib.load()
@@ -105,7 +125,7 @@ class GraphPack:
 
     def code_index(self, R: int) -> Optional[torch.Tensor]:
         """CSR positions stably grouped by bond code (inverted index for the bond-table gradient); None if R > 64."""
-        if R > 64:
+        if not GraphPack.has_code_index(R):
             return None
         if self._code_index is None or self._code_index[0] != R:
             lib, h = _lib.load(), handle(self.device)
@@ -150,46 +170,53 @@ class DegreeClasses:
     __slots__ = ("D", "dperm", "cls_ptr", "tiles", "ntiles", "max_tiles", "chunks", "nchunks", "max_chunks",
                  "tiles_p", "ntiles_p", "max_tiles_p", "tile_rows_p")
 
+    def __init__(self, D: int):
+        self.D = D  # the tables exist only for D <= MAX_D
+
+    def layout(self, lib, h, N: int) -> List[Tuple[str, int]]:
+        """[(table, int32 count)] of the tables over N nodes, to be handed to ``take`` as tensors; sets their bounds.
+        The tile table of the pipelined forward product (post-layer 0) has 96-row tiles where 128-row ones would leave the
+        last round of its persistent workgroups mostly idle (gnx_gemm_tile_rows); otherwise, and for the input-gradient
+        product always, it is ``tiles`` itself and has no entry."""
+        D = self.D
+        self.tile_rows_p = int(lib.gnx_gemm_tile_rows(h, N, 128))
+        self.max_tiles, self.max_chunks = N // DegreeClasses.GEMM_ROWS + D, N // DegreeClasses.WGRAD_ROWS + D
+        sizes = [("dperm", max(N, 1)), ("cls_ptr", D + 1), ("tiles", 3 * self.max_tiles), ("ntiles", 1),
+                 ("chunks", 3 * self.max_chunks), ("nchunks", 1)]
+        if self.tile_rows_p == DegreeClasses.GEMM_ROWS:
+            self.max_tiles_p = self.max_tiles
+        else:
+            self.max_tiles_p = N // self.tile_rows_p + D
+            sizes += [("tiles_p", 3 * self.max_tiles_p), ("ntiles_p", 1)]
+        return sizes
+
+    def take(self, v: dict) -> List[Tuple[int, torch.Tensor, torch.Tensor]]:
+        """Adopt the tensors v[table]; returns (tile rows, table, count) of every tile table to fill."""
+        self.dperm, self.cls_ptr, self.tiles, self.ntiles, self.chunks, self.nchunks = (
+            v["dperm"], v["cls_ptr"], v["tiles"], v["ntiles"], v["chunks"], v["nchunks"])
+        self.tiles_p, self.ntiles_p = v.get("tiles_p", self.tiles), v.get("ntiles_p", self.ntiles)
+        tables = [(DegreeClasses.GEMM_ROWS, self.tiles, self.ntiles), (DegreeClasses.WGRAD_ROWS, self.chunks, self.nchunks)]
+        if self.tiles_p is not self.tiles:
+            tables.append((self.tile_rows_p, self.tiles_p, self.ntiles_p))
+        return tables
+
     @staticmethod
     def build(g: "GraphPack", max_degree_hint: Optional[int] = None) -> "DegreeClasses":
         lib, h = _lib.load(), handle(g.device)
-        dc = DegreeClasses()
         if max_degree_hint is None:
             mx = _I32(0)
             check(lib.gnx_degree_max(h, g.rowptr.data_ptr(), g.N, C.byref(mx)))
-            dc.D = int(mx.value) + 1
-        else:
-            dc.D = int(max_degree_hint) + 1
+            max_degree_hint = mx.value
+        dc = DegreeClasses(int(max_degree_hint) + 1)
         if dc.D > DegreeClasses.MAX_D:
             return dc
-        i32 = dict(dtype=torch.int32, device=g.device)
-        dc.dperm = torch.empty(max(g.N, 1), **i32)
-        dc.cls_ptr = torch.empty(dc.D + 1, **i32)
+        tables = dc.take({name: torch.empty(n, dtype=torch.int32, device=g.device) for name, n in dc.layout(lib, h, g.N)})
         nbytes = lib.gnx_degree_classes_workspace_bytes(g.N, dc.D)
         ws = torch.empty(nbytes, dtype=torch.uint8, device=g.device)
         check(lib.gnx_degree_classes(h, g.rowptr.data_ptr(), g.N, dc.D, dc.dperm.data_ptr(), dc.cls_ptr.data_ptr(),
                                      ws.data_ptr(), nbytes))
-        dc.max_tiles = g.N // DegreeClasses.GEMM_ROWS + dc.D
-        dc.max_chunks = g.N // DegreeClasses.WGRAD_ROWS + dc.D
-        dc.tiles = torch.empty(3 * dc.max_tiles, **i32)
-        dc.chunks = torch.empty(3 * dc.max_chunks, **i32)
-        dc.ntiles = torch.empty(1, **i32)
-        dc.nchunks = torch.empty(1, **i32)
-        check(lib.gnx_class_tiles(h, dc.cls_ptr.data_ptr(), dc.D, DegreeClasses.GEMM_ROWS, dc.tiles.data_ptr(),
-                                  dc.ntiles.data_ptr()))
-        check(lib.gnx_class_tiles(h, dc.cls_ptr.data_ptr(), dc.D, DegreeClasses.WGRAD_ROWS, dc.chunks.data_ptr(),
-                                  dc.nchunks.data_ptr()))
-        # tile table of the pipelined forward product (post-layer 0): 96-row tiles where 128-row ones would leave the last
-        # round of its persistent workgroups mostly idle (gnx_gemm_tile_rows); the input-gradient product keeps `tiles`
-        dc.tile_rows_p = int(lib.gnx_gemm_tile_rows(h, g.N, 128))
-        if dc.tile_rows_p == DegreeClasses.GEMM_ROWS:
-            dc.tiles_p, dc.ntiles_p, dc.max_tiles_p = dc.tiles, dc.ntiles, dc.max_tiles
-        else:
-            dc.max_tiles_p = g.N // dc.tile_rows_p + dc.D
-            dc.tiles_p = torch.empty(3 * dc.max_tiles_p, **i32)
-            dc.ntiles_p = torch.empty(1, **i32)
-            check(lib.gnx_class_tiles(h, dc.cls_ptr.data_ptr(), dc.D, dc.tile_rows_p, dc.tiles_p.data_ptr(),
-                                      dc.ntiles_p.data_ptr()))
+        for rows, tiles, ntiles in tables:
+            check(lib.gnx_class_tiles(h, dc.cls_ptr.data_ptr(), dc.D, rows, tiles.data_ptr(), ntiles.data_ptr()))
         return dc
 
 
@@ -210,68 +237,25 @@ def check_range(device: torch.device) -> None:
 def pack_graph(edge_index: torch.Tensor, edge_attr: Optional[torch.Tensor], batch: Optional[torch.Tensor],
                num_nodes: int, num_graphs: Optional[int] = None, bond_dims: Sequence[int] = (5, 6, 2),
                validate: bool = True) -> GraphPack:
-    """edge_index int64[2,E], edge_attr int64[E,K], batch int64[N]|None  ->  GraphPack (all on edge_index.device)."""
-    dev = edge_index.device
-    lib, h = _lib.load(), handle(dev)
-    if edge_index.dtype != torch.int64 or edge_index.dim() != 2 or edge_index.size(0) != 2:
-        raise _lib.GnxError(_lib.GNX_E_INVALID, f"edge_index must be int64[2,E], got {edge_index.dtype} "
-                                                f"{tuple(edge_index.shape)}")
-    edge_index = edge_index.contiguous()
-    N, E = int(num_nodes), int(edge_index.size(1))
-    i32 = dict(dtype=torch.int32, device=dev)
-    g = GraphPack()
-    g.N, g.E, g.device, g._scalers, g._classes, g._code_index = N, E, dev, {}, None, None
-    g._edge_tiles = None
-    g.max_degree_hint = None
-    g.rowptr = torch.empty(N + 1, **i32)
-    g.colptr = torch.empty(N + 1, **i32)
-    g.perm = torch.empty(E, **i32)
-    g.src = torch.empty(E, **i32)
-    g.dst = torch.empty(E, **i32)
-    g.cpos = torch.empty(E, **i32)
-    ws_bytes = lib.gnx_pack_csr_workspace_bytes(N, E)
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-    check(lib.gnx_pack_csr(h, edge_index.data_ptr(), E, N, g.rowptr.data_ptr(), g.perm.data_ptr(), g.src.data_ptr(),
-                           g.dst.data_ptr(), g.colptr.data_ptr(), g.cpos.data_ptr(), ws.data_ptr(), ws_bytes))
-    g.code = torch.empty(E, **i32)
-    if edge_attr is not None:
-        if edge_attr.dtype != torch.int64 or edge_attr.dim() != 2 or edge_attr.size(0) != E or \
-                edge_attr.size(1) != len(bond_dims):
-            raise _lib.GnxError(_lib.GNX_E_INVALID, f"edge_attr must be int64[E,{len(bond_dims)}], got "
-                                                    f"{edge_attr.dtype} {tuple(edge_attr.shape)}")
-        edge_attr = edge_attr.contiguous()
-        check(lib.gnx_feature_code(h, edge_attr.data_ptr(), E, len(bond_dims), _carr(list(bond_dims)),
-                                   g.perm.data_ptr(), g.code.data_ptr(), None, 0))
-    else:
-        g.code.zero_()
-    if batch is not None:
-        if batch.dtype != torch.int64 or batch.dim() != 1 or batch.size(0) != N:
-            raise _lib.GnxError(_lib.GNX_E_INVALID, f"batch must be int64[N], got {batch.dtype} {tuple(batch.shape)}")
-        if num_graphs is None:
-            # PyG: dim_size = batch.max() + 1 (device sync); pass num_graphs to avoid it
-            num_graphs = int(batch.max()) + 1 if N > 0 else 0
-        g.B = int(num_graphs)
-        g.has_batch = True
-        g.graph_ptr = torch.empty(g.B + 1, **i32)
-        check(lib.gnx_graph_ptr(h, batch.contiguous().data_ptr(), N, g.B, g.graph_ptr.data_ptr(), None, 0))
-    else:
-        g.B = 1
-        g.has_batch = False
-        g.graph_ptr = torch.arange(2, **i32) * N  # [0, N] built on the device (capturable; no host-to-device copy)
-    if validate:
-        check_range(dev)
-    return g
+    """edge_index int64[2,E], edge_attr int64[E,K], batch int64[N]|None  ->  GraphPack (all on edge_index.device):
+    ``pack_batch`` without a degree hint, i.e. the base arrays alone; the getters build the rest on first use."""
+    return pack_batch(edge_index, edge_attr, batch, num_nodes, num_graphs, bond_dims, max_degree_hint=None,
+                      validate=validate)
 
 
 def pack_batch(edge_index: torch.Tensor, edge_attr: Optional[torch.Tensor], batch: Optional[torch.Tensor],
                num_nodes: int, num_graphs: Optional[int] = None, bond_dims: Sequence[int] = (5, 6, 2), *,
-               max_degree_hint: int, R: Optional[int] = None, avg_deg_logs: Sequence[float] = (), classes: bool = True,
-               edge_tiles: Optional[bool] = None, validate: bool = True, tiled_scan: bool = False) -> GraphPack:
-    """``pack_graph`` plus everything its getters would build later, in one native call (gnx_pack_batch, 8 launches): the
-    returned GraphPack has ``max_degree_hint`` set and its degree classes (``classes``; PNA only), the bond-code index for
-    ``R`` codes, the edge tiles for the hint (``edge_tiles``, default = ``classes``) and the degree scalers of up to 4
-    ``avg_deg_logs`` in its caches, bit-identical to what the getters build; a getter asked for another ``R``, width or
-    ``avg_deg_log`` builds its own as before.  Every output and the workspace are views of one int32 allocation.
+               max_degree_hint: Optional[int], R: Optional[int] = None, avg_deg_logs: Sequence[float] = (),
+               classes: bool = True, edge_tiles: Optional[bool] = None, validate: bool = True,
+               tiled_scan: bool = False) -> GraphPack:
+    """The GraphPack of a batch in one native call (gnx_pack_batch, 8 launches; 6 for the base arrays alone).  With
+    ``max_degree_hint``, an upper bound of the in-degree, the pack has the hint set and everything its getters would build
+    later in its caches: the degree classes (``classes``; PNA only), the bond-code index for ``R`` codes, the edge tiles
+    for the hint (``edge_tiles``, default = ``classes``) and the degree scalers of up to 4 ``avg_deg_logs``, bit-identical
+    to what the getters build; a getter asked for another ``R``, width or ``avg_deg_log`` builds its own.  With
+    ``max_degree_hint=None`` only the base arrays are built, ``g.max_degree_hint`` stays None and the other arguments
+    are ignored (``degree_classes()`` then reads the maximum in-degree back).  Every output and the call's workspace are
+    views of one int32 allocation, so the workspace (a few MB at most here) lives as long as the pack.
     ``tiled_scan`` forces the multi-launch scan that batches above ``gnx_pack_batch_scan_bound()`` nodes take (tests)."""
     dev = edge_index.device
     lib, h = _lib.load(), handle(dev)
@@ -291,54 +275,41 @@ def pack_batch(edge_index: torch.Tensor, edge_attr: Optional[torch.Tensor], batc
         a.edge_attr, a.K = edge_attr.data_ptr(), len(bond_dims)
         for k, d in enumerate(bond_dims):
             a.bond_dims[k] = int(d)
-    g = GraphPack()
-    g.N, g.E, g.device, g._scalers, g._classes, g._code_index, g._edge_tiles = N, E, dev, {}, None, None, None
-    g.max_degree_hint = int(max_degree_hint)
+    B = 1
     if batch is not None:
         if batch.dtype != torch.int64 or batch.dim() != 1 or batch.size(0) != N:
             raise _lib.GnxError(_lib.GNX_E_INVALID, f"batch must be int64[N], got {batch.dtype} {tuple(batch.shape)}")
         if num_graphs is None:
+            # PyG: dim_size = batch.max() + 1 (device sync); pass num_graphs to avoid it
             num_graphs = int(batch.max()) + 1 if N > 0 else 0
         batch = batch.contiguous()
-        g.B, g.has_batch = int(num_graphs), True
-        a.batch, a.B = batch.data_ptr(), g.B
-    else:
-        g.B, g.has_batch = 1, False
-    # which parts, as the getters decide
-    D = g.max_degree_hint + 1
-    dc = None
-    if classes:
-        dc = g._classes = DegreeClasses()
-        dc.D = D
+        B = int(num_graphs)
+        a.batch, a.B = batch.data_ptr(), B
+    if max_degree_hint is None:
+        R, avg_deg_logs, classes, edge_tiles = None, (), False, False
+    g = GraphPack(N, E, B, batch is not None, dev, None if max_degree_hint is None else int(max_degree_hint))
+    # which parts: where the getters would build one for this hint
+    D = (g.max_degree_hint or 0) + 1
+    dc = g._classes = DegreeClasses(D) if classes else None
     build_dc = classes and D <= DegreeClasses.MAX_D
-    build_ci = R is not None and R <= 64 and E > 0
+    build_ci = R is not None and GraphPack.has_code_index(R) and E > 0
     if edge_tiles is None:
         edge_tiles = classes
-    build_et = bool(edge_tiles) and g.max_degree_hint <= GraphPack.EDGE_TILE_MAX_DEG and E > 0 and N > 0
+    w = GraphPack.edge_tile_width(g.max_degree_hint) if edge_tiles and E > 0 and N > 0 else None
     avgs = [float(v) for v in dict.fromkeys(float(v) for v in avg_deg_logs)][:_lib.PACK_MAX_AVG]
-    a.max_degree, a.R, a.n_avg = g.max_degree_hint, int(R) if R is not None else 0, len(avgs)
+    a.max_degree, a.R, a.n_avg = D - 1, int(R) if R is not None else 0, len(avgs)
     a.parts = (_lib.PACK_CLASSES if build_dc else 0) | (_lib.PACK_CODE_INDEX if build_ci else 0) | \
-        (_lib.PACK_EDGE_TILES if build_et else 0) | (_lib.PACK_TILED_SCAN if tiled_scan else 0)
+        (_lib.PACK_EDGE_TILES if w is not None else 0) | (_lib.PACK_TILED_SCAN if tiled_scan else 0)
     # one allocation: every piece starts on a 256-byte boundary
-    sizes: List[Tuple[str, int]] = [("rowptr", N + 1), ("colptr", N + 1), ("perm", E), ("src", E), ("dst", E), ("cpos", E),
-                                    ("code", E), ("graph_ptr", g.B + 1)]
+    base = ("rowptr", "colptr", "perm", "src", "dst", "cpos", "code", "graph_ptr")
+    sizes: List[Tuple[str, int]] = list(zip(base, (N + 1, N + 1, E, E, E, E, E, B + 1)))
     for i in range(len(avgs)):
         sizes += [(f"amp{i}", N), (f"att{i}", N)]
-    rows = [0, 0, 0]
     if build_dc:
-        rows[0], rows[1] = DegreeClasses.GEMM_ROWS, DegreeClasses.WGRAD_ROWS
-        dc.tile_rows_p = int(lib.gnx_gemm_tile_rows(h, N, 128))
-        dc.max_tiles, dc.max_chunks = N // rows[0] + D, N // rows[1] + D
-        sizes += [("dperm", max(N, 1)), ("cls_ptr", D + 1), ("tiles", 3 * dc.max_tiles), ("ntiles", 1),
-                  ("chunks", 3 * dc.max_chunks), ("nchunks", 1)]
-        if dc.tile_rows_p != rows[0]:
-            rows[2] = dc.tile_rows_p
-            dc.max_tiles_p = N // dc.tile_rows_p + D
-            sizes += [("tiles_p", 3 * dc.max_tiles_p), ("ntiles_p", 1)]
+        sizes += dc.layout(lib, h, N)
     if build_ci:
         sizes += [("code_pos", E), ("code_ptr", R + 1)]
-    if build_et:
-        w = GraphPack.EDGE_TILE_ROWS + 1 - max(g.max_degree_hint, 1)
+    if w is not None:
         a.edge_tile_w = w
         sizes.append(("edge_tiles", 2 * (lib.gnx_edge_tiles_count(E, w) + 1)))
     ws_bytes = lib.gnx_pack_batch_workspace_bytes(N, E, D if build_dc else 1, R if build_ci else 1)
@@ -349,30 +320,23 @@ def pack_batch(edge_index: torch.Tensor, edge_attr: Optional[torch.Tensor], batc
         total += (n + 63) & ~63
     buf = torch.empty(total, dtype=torch.int32, device=dev)
     v = {name: buf[off[name]:off[name] + n] for name, n in sizes}
-    g.rowptr, g.colptr, g.perm, g.src, g.dst, g.cpos, g.code, g.graph_ptr = (
-        v["rowptr"], v["colptr"], v["perm"], v["src"], v["dst"], v["cpos"], v["code"], v["graph_ptr"])
-    for name in ("rowptr", "colptr", "perm", "src", "dst", "cpos", "code", "graph_ptr"):
+    for name in base:
+        setattr(g, name, v[name])
         setattr(a, name, v[name].data_ptr())
     for i, key in enumerate(avgs):
         amp, att = v[f"amp{i}"].view(torch.float32), v[f"att{i}"].view(torch.float32)
         a.avg_deg_log[i], a.amp[i], a.att[i] = key, amp.data_ptr(), att.data_ptr()
         g._scalers[key] = (amp, att)
     if build_dc:
-        dc.dperm, dc.cls_ptr, dc.tiles, dc.ntiles, dc.chunks, dc.nchunks = (
-            v["dperm"], v["cls_ptr"], v["tiles"], v["ntiles"], v["chunks"], v["nchunks"])
-        if rows[2]:
-            dc.tiles_p, dc.ntiles_p = v["tiles_p"], v["ntiles_p"]
-        else:
-            dc.tiles_p, dc.ntiles_p, dc.max_tiles_p = dc.tiles, dc.ntiles, dc.max_tiles
+        for i, (rows, tiles, ntiles) in enumerate(dc.take(v)):
+            a.tile_rows[i], a.tiles[i], a.ntiles[i] = rows, tiles.data_ptr(), ntiles.data_ptr()
         a.dperm, a.cls_ptr = dc.dperm.data_ptr(), dc.cls_ptr.data_ptr()
-        for i, (t, n) in enumerate(((dc.tiles, dc.ntiles), (dc.chunks, dc.nchunks), (dc.tiles_p, dc.ntiles_p))):
-            a.tile_rows[i], a.tiles[i], a.ntiles[i] = rows[i], t.data_ptr(), n.data_ptr()
     if build_ci:
         a.code_pos, a.code_ptr = v["code_pos"].data_ptr(), v["code_ptr"].data_ptr()
         g._code_index = (int(R), v["code_pos"], v["code_ptr"])
-    if build_et:
+    if w is not None:
         a.edge_tiles = v["edge_tiles"].data_ptr()
-        g._edge_tiles = (v["edge_tiles"], a.edge_tile_w)
+        g._edge_tiles = (v["edge_tiles"], w)
     a.ws, a.ws_bytes = v["ws"].data_ptr(), ws_bytes
     check(lib.gnx_pack_batch(h, C.byref(a)))
     if validate:

@@ -31,19 +31,15 @@ _UPPER = (25.0, 4.5, 550.0, -math.log10(0.0001), math.log10(5000.0))
 def _pack_of(graphs, validate: bool, max_degree_hint: Optional[int] = None,
              model: Optional["GNNePCSAFT"] = None) -> GraphPack:
     """GraphPack of a Batch-like object, cached on it (the packer runs once per batch, like PyG's collate).  With a degree
-    hint and the model that will consume it, the pack comes from one native call with its getters' tables already built
-    (``ops.pack_batch``); without a hint the degree classes need the batch's maximum in-degree first (one sync)."""
+    hint and the model that will consume it, the same native call also builds its getters' tables (``ops.pack_batch``);
+    without a hint the degree classes need the batch's maximum in-degree first (one sync)."""
     pack = getattr(graphs, "_gnx_pack", None)
     if pack is None or pack.device != graphs.x.device:
         batch = getattr(graphs, "batch", None)
         num_graphs = getattr(graphs, "num_graphs", None) if batch is not None else None
-        if max_degree_hint is not None and model is not None and graphs.x.is_cuda:
-            pack = ops.pack_batch(graphs.edge_index, graphs.edge_attr, batch, graphs.x.size(0), num_graphs,
-                                  max_degree_hint=max_degree_hint, validate=validate, **model.pack_spec())
-        else:
-            pack = ops.pack_graph(graphs.edge_index, graphs.edge_attr, batch, graphs.x.size(0), num_graphs,
-                                  validate=validate)
-            pack.max_degree_hint = max_degree_hint
+        spec = model.pack_spec() if model is not None else {"classes": False}
+        pack = ops.pack_batch(graphs.edge_index, graphs.edge_attr, batch, graphs.x.size(0), num_graphs,
+                              max_degree_hint=max_degree_hint, validate=validate, **spec)
         try:
             graphs._gnx_pack = pack
         except AttributeError:

@@ -122,7 +122,11 @@ int32_t gnx_prof_end(gnx_handle* h);
  *   row, i.e. the order scatter_add_ visits them);  src int32[E], dst int32[E]: endpoints in CSR order;
  *   colptr int32[N+1], cpos int32[E]: for every source node the ascending list of CSR positions leaving it.
  * Bit-exact integer work.  Out-of-range node ids are clamped and set the handle's sticky range flag (bit 0), which
- * gnx_check_range reports (the only synchronising call), so a training loop can validate once per step. */
+ * gnx_check_range reports (the only synchronising call), so a training loop can validate once per step.
+ * gnx_pack_csr is gnx_pack_batch (below) with no optional part, no edge_attr and no batch: its first 6 launches (5 with
+ * E = 0; 17 above gnx_pack_batch_scan_bound() nodes).  ws: gnx_pack_csr_workspace_bytes(N, E), which is
+ * gnx_pack_batch_workspace_bytes(N, E, 1, 1) plus room for the bond codes and graph_ptr that those launches also write;
+ * a shorter one is GNX_E_WORKSPACE and nothing is launched.  E = 0: the edge arrays may be NULL. */
 size_t gnx_pack_csr_workspace_bytes(int64_t N, int64_t E);
 int32_t gnx_pack_csr(gnx_handle* h, const int64_t* edge_index, int64_t E, int64_t N, int32_t* rowptr, int32_t* perm,
                      int32_t* src, int32_t* dst, int32_t* colptr, int32_t* cpos, void* ws, size_t ws_bytes);
@@ -391,11 +395,12 @@ int32_t gnx_edge_tiles_count(int64_t E, int32_t tile_w);
 int32_t gnx_edge_tiles(gnx_handle* h, const int32_t* rowptr, int64_t N, int64_t E, int32_t tile_w, int32_t* tile_info);
 
 /* ---- a whole batch's integer structure in one call ---------------------------------------------------------------
- * gnx_pack_batch writes what gnx_pack_csr, gnx_feature_code (through perm), gnx_graph_ptr, gnx_degree_scalers (once per
- * avg_deg_log), gnx_degree_classes, gnx_class_tiles (once per tile_rows), gnx_group_by_small_key (of code) and
- * gnx_edge_tiles write, bit for bit (clamped values and sticky range-flag bits on bad input included), in 8 launches
- * (15 above gnx_pack_batch_scan_bound() nodes) instead of 37.  No workgroup waits for another, nothing is read back and
- * nothing synchronises: the call captures into a HIP graph.
+ * gnx_pack_batch builds the CSR of gnx_pack_csr and writes what gnx_feature_code (through perm), gnx_graph_ptr,
+ * gnx_degree_scalers (once per avg_deg_log), gnx_degree_classes, gnx_class_tiles (once per tile_rows),
+ * gnx_group_by_small_key (of code) and gnx_edge_tiles write, bit for bit (clamped values and sticky range-flag bits on bad
+ * input included), in 8 launches: 6 for the CSR, codes, graph_ptr and scalers, 2 more with any of the optional parts.
+ * Above gnx_pack_batch_scan_bound() nodes the one scan launch becomes 6 per counter array, 19 in all.  No workgroup waits
+ * for another, nothing is read back and nothing synchronises: the call captures into a HIP graph.
  *   edge_attr NULL: code = 0.  batch NULL: graph_ptr = [0, N] (B is ignored).
  *   parts: which optional outputs to build; an unbuilt part's pointers may be NULL and its buffers are not touched.
  *     GNX_PACK_CLASSES     dperm, cls_ptr and, per tile_rows[i] > 0, tiles[i] / ntiles[i]; D = max_degree + 1 <= 64 classes

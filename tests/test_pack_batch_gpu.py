@@ -1,7 +1,9 @@
-"""``ops.pack_batch`` (gnx_pack_batch: one native call, 8 launches) against today's sequence of single-purpose entries
-(``ops.pack_graph`` + the getters of GraphPack / DegreeClasses) on the same tensors: every output array equal
-(``torch.equal``, counts included; a table is compared up to its own count, the rest of its buffer is unwritten in both),
-the CSR arrays also against a numpy stable-argsort reference, and the same sticky range-flag report on bad input.
+"""``ops.pack_batch`` (gnx_pack_batch: one native call, 8 launches) against ``ops.pack_graph`` + the getters of GraphPack /
+DegreeClasses on the same tensors: every output array equal (``torch.equal``, counts included; a table is compared up to
+its own count, the rest of its buffer is unwritten in both) and the same sticky range-flag report on bad input.  The
+getters' tables come from the single-purpose entries, a separate implementation; the eight base arrays come from the same
+launches in both, so they are held to the numpy references of tests/pack_ref.py on every case, as is gnx_pack_csr called
+directly.
 
 The range-flag bit that the PACKER sets for an in-degree above the hint is bit 5 (the class histogram clamps the degree);
 bit 6 belongs to the fused edge kernels that consume the edge tiles.  Both paths must report the same bits here.
@@ -11,6 +13,8 @@ import ctypes as C
 import numpy as np
 import pytest
 import torch
+
+from tests import pack_ref as R
 
 pytestmark = pytest.mark.gpu
 
@@ -95,6 +99,9 @@ def _cases():
     bad_f = _random("bad_bond_feature", 50, 120, 11)
     bad_f.ea[3, 1], bad_f.ea[90, 0] = 6, -2
     out.append(bad_f)
+    gaps = _random("empty_graphs_start_middle_end", 6, 14, 12)  # graphs 0, 2, 4, 6 and 7 of 8 have no node
+    gaps.batch, gaps.B = torch.tensor([1, 1, 3, 3, 3, 5]), 8
+    out.append(gaps)
     return out
 
 
@@ -110,7 +117,8 @@ def _all_cases():
 
 CASE_NAMES = ["E0_N5", "N1_self_loops", "one_molecule", "32_molecules", "isolated_start_middle_end", "multi_edges_self_loops",
               "scan_tile_N1023", "scan_tile_N1024", "scan_tile_N1025", "past_scan_bound", "multi_launch_scan_forced",
-              "degree_at_hint", "degree_above_hint", "hub_17", "R65", "gine_flags", "bad_node_index", "bad_bond_feature"]
+              "degree_at_hint", "degree_above_hint", "hub_17", "R65", "gine_flags", "bad_node_index", "bad_bond_feature",
+              "empty_graphs_start_middle_end"]
 
 
 def _new(c, dev, **kw):
@@ -173,15 +181,16 @@ def _assert_same(a, b):
         assert a._edge_tiles[1] == b._edge_tiles[1] and torch.equal(a._edge_tiles[0], b._edge_tiles[0])
 
 
-def _assert_csr_is_stable_sort(g, c):
-    ei = c.ei.numpy()
-    bad = ((ei < 0) | (ei >= c.N)).any(0)
-    s0, d0 = np.where(bad, 0, ei[0]), np.where(bad, 0, ei[1])
-    perm = np.argsort(d0, kind="stable")
-    src = s0[perm]
-    ptr = lambda k: np.concatenate([[0], np.cumsum(np.bincount(k, minlength=c.N))])
-    for name, ref in (("perm", perm), ("src", src), ("dst", d0[perm]), ("rowptr", ptr(d0)), ("colptr", ptr(s0)),
-                      ("cpos", np.argsort(src, kind="stable"))):
+def _base_reference(c):
+    """The eight base arrays of case c by numpy (tests/pack_ref.py)."""
+    ref = R.csr_reference(c.ei.numpy(), c.N)
+    ref["code"] = R.code_reference(None if c.ea is None else c.ea.numpy(), c.bond_dims, ref["perm"])
+    ref["graph_ptr"] = R.graph_ptr_reference(None if c.batch is None else c.batch.numpy(), c.N, c.B)
+    return ref
+
+
+def _assert_base_arrays_are_the_reference(g, c):
+    for name, ref in _base_reference(c).items():
         assert np.array_equal(getattr(g, name).cpu().numpy(), ref), name
 
 
@@ -193,7 +202,8 @@ def test_every_output_equals_todays_calls(gpu_device, name):
     print(name, "N", c.N, "E", c.ei.size(1), "hint", c.hint, "flag:", flag_new or "clean")
     assert flag_new == flag_old
     _assert_same(new, old)
-    _assert_csr_is_stable_sort(new, c)
+    _assert_base_arrays_are_the_reference(new, c)
+    _assert_base_arrays_are_the_reference(old, c)
     # what the case is about
     if name == "degree_above_hint":
         assert "in-degree" in flag_new
@@ -243,6 +253,56 @@ def test_unbuilt_parts_are_not_touched(gpu_device):
     for n in ("rowptr", "perm", "src", "dst", "colptr", "cpos", "code"):
         assert torch.equal(need[n], getattr(old, n)), n
     assert need["graph_ptr"][:2].tolist() == [0, N]
+
+
+def _pack_csr(c, dev, short_by=0):
+    """gnx_pack_csr called the way a C caller would, outputs and one spare buffer pre-filled with -7, the workspace
+    ``short_by`` bytes below the queried size: (status, outputs, spare)."""
+    from gnnepcsaft_amd import _lib
+    lib = _lib.load()
+    N, E = c.N, c.ei.size(1)
+    i32 = lambda n: torch.full((n,), -7, dtype=torch.int32, device=dev)
+    out = {n: i32(N + 1 if n in ("rowptr", "colptr") else E) for n in ("rowptr", "perm", "src", "dst", "colptr", "cpos")}
+    spare = i32(4 * (N + E))
+    ei = c.ei.to(dev).contiguous()
+    p = lambda t: t.data_ptr() if E > 0 else None  # E = 0: the edge arrays may be NULL
+    nbytes = lib.gnx_pack_csr_workspace_bytes(N, E)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    st = lib.gnx_pack_csr(_lib.handle(dev), p(ei), E, N, out["rowptr"].data_ptr(), p(out["perm"]), p(out["src"]),
+                          p(out["dst"]), out["colptr"].data_ptr(), p(out["cpos"]), ws.data_ptr(), nbytes - short_by)
+    return st, out, spare
+
+
+@pytest.mark.parametrize("name", ["E0_N5", "N1_self_loops", "scan_tile_N1023", "scan_tile_N1024", "scan_tile_N1025",
+                                  "multi_edges_self_loops", "bad_node_index"])
+def test_pack_csr_called_directly(gpu_device, name):
+    """Nothing in ``ops`` calls gnx_pack_csr: its six arrays against the numpy reference, through ctypes."""
+    from gnnepcsaft_amd import _lib
+    c = _all_cases()[name]
+    _flag(gpu_device)
+    st, out, spare = _pack_csr(c, gpu_device)
+    _lib.check(st)
+    flag = _flag(gpu_device)
+    ref = R.csr_reference(c.ei.numpy(), c.N)
+    for n, t in out.items():
+        assert np.array_equal(t.cpu().numpy(), ref[n]), n
+    assert bool((spare == -7).all())
+    if name == "bad_node_index":  # one id equal to N, one equal to -1: both endpoints of those edges become 0
+        assert "node id" in flag
+        pos = {int(e): p for p, e in enumerate(out["perm"].tolist())}
+        assert [(int(out["src"][pos[e]]), int(out["dst"][pos[e]])) for e in (7, 50)] == [(0, 0), (0, 0)]
+    else:
+        assert flag == ""
+
+
+def test_pack_csr_short_workspace_writes_nothing(gpu_device):
+    from gnnepcsaft_amd import _lib
+    st, out, spare = _pack_csr(_all_cases()["multi_edges_self_loops"], gpu_device, short_by=1)
+    assert st == _lib.GNX_E_WORKSPACE
+    torch.cuda.synchronize()
+    for n, t in list(out.items()) + [("spare", spare)]:
+        assert bool((t == -7).all()), n
+    assert _flag(gpu_device) == ""
 
 
 def test_two_calls_give_identical_bytes(gpu_device):
