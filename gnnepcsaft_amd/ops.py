@@ -1169,6 +1169,7 @@ _PCSAFT_MIX = {"pcsaft_mix_state": ("gnx_pcsaft_mix_state", (0, 0, 0)),
                "pcsaft_mix_lnphi_state": ("gnx_pcsaft_mix_lnphi_state", (1, 0)),
                "pcsaft_mix_lnphi": ("gnx_pcsaft_mix_lnphi", (0, 1, 1)),
                "pcsaft_mix_bubble": ("gnx_pcsaft_mix_bubble", (0, 1, 0, 0)),
+               "pcsaft_mix_dew": ("gnx_pcsaft_mix_dew", (0, 1, 0, 0)),
                "pcsaft_mix_flash": ("gnx_pcsaft_mix_flash", (0, 1, 1, 0, 0)),
                "pcsaft_mix_stability": ("gnx_pcsaft_mix_stability", (0, 1, 0, 0))}
 
@@ -1263,6 +1264,22 @@ def pcsaft_mix_bubble(params: torch.Tensor, comp: torch.Tensor, kij: Optional[to
     -> (P [n] Pa, y [n, nc], rho_l [n], rho_v [n] mol/m^3, status [n] int32).  A used slot with x = 0 is dropped (y = 0.0),
     a -1 slot has y = NaN; where status != 0, P and the densities are 0.0 and the y row is NaN."""
     return _pcsaft_mix_bubble(params, comp, kij, eab, owner, T, x)
+
+
+def _pcsaft_mix_dew(params, comp, kij, eab, owner, T, y, out=None):
+    """``pcsaft_mix_dew`` writing into ``out`` = (P, x, rho_l, rho_v, status) where given; rho_l and rho_v may be None
+    there."""
+    return _pcsaft_mix(params, comp, kij, eab, owner, T, None, y, "pcsaft_mix_dew", out=out)
+
+
+def pcsaft_mix_dew(params: torch.Tensor, comp: torch.Tensor, kij: Optional[torch.Tensor],
+                   eab: Optional[torch.Tensor], owner: torch.Tensor, T: torch.Tensor, y: torch.Tensor
+                   ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Mixture PC-SAFT dew point at (T, y) (gnx_pcsaft_mix_dew): arguments as ``pcsaft_mix_bubble`` with the vapour y
+    [n, nc] in place of x -> (P [n] Pa, x [n, nc], rho_l [n], rho_v [n] mol/m^3, status [n] int32).  A used slot with
+    y = 0 is dropped (x = 0.0), a -1 slot has x = NaN; where status != 0, P and the densities are 0.0 and the x row is
+    NaN."""
+    return _pcsaft_mix_dew(params, comp, kij, eab, owner, T, y)
 
 
 def _pcsaft_mix_flash(params, comp, kij, eab, owner, T, P, z, out=None):

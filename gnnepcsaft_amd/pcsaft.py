@@ -25,7 +25,13 @@ value at infinite dilution.  x is normalised by its sum, and 0 ln 0 counts as 0 
 Bubble points of a mixture, the pressure at which the liquid x starts to boil at T and the vapour y that forms
 (csrc/gnx_pcsaft_mix_vle.hip): ``mix_bubble`` for one point (the bubble half of the reference's ``mix_vp_feos``),
 ``mix_bubble_batch`` for every point of every system in one launch, ``mix_vle_pxy`` for the P-x-y diagram of a binary
-(``mix_vle_pxy_diagram_feos``), ``mixture_bubble_pressure`` on device tensors.  Dew pressures are not provided.
+(``mix_vle_pxy_diagram_feos``), ``mixture_bubble_pressure`` on device tensors.
+
+Dew points of a mixture, the pressure at which the vapour y starts to condense at T and the liquid x that forms
+(csrc/gnx_pcsaft_mix_dew.hip): ``mix_dew`` for one point (the dew half of the reference's ``mix_vp_feos``),
+``mix_dew_batch`` for every point of every system in one launch, ``mixture_dew_pressure`` on device tensors, and
+``mix_vp``, the reference's ``mix_vp_feos`` itself: (bubble pressure, dew pressure) of one composition.  A vapour can have
+more than one dew point (retrograde condensation); the one reported is the one the Raoult's-law start leads to.
 
 Isothermal two-phase flashes, the split of a feed z at (T, P) into a liquid x and a vapour y with the vapour mole fraction
 beta (csrc/gnx_pcsaft_mix_flash.hip): ``mix_tp_flash`` for one point (the reference's ``mix_tp_flash_feos``),
@@ -259,6 +265,17 @@ def mixture_bubble_pressure(params: torch.Tensor, comp: torch.Tensor, x: torch.T
     return ops.pcsaft_mix_bubble(params, comp, kij, eab, _owner(owner, T), T, x)
 
 
+def mixture_dew_pressure(params: torch.Tensor, comp: torch.Tensor, y: torch.Tensor, T: torch.Tensor,
+                         owner: Optional[torch.Tensor] = None, kij: Optional[torch.Tensor] = None,
+                         eab: Optional[torch.Tensor] = None
+                         ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Tensor form on device tensors, arguments as ``mixture_bubble_pressure`` with the vapour y [n, nc] in place of x ->
+    (P [n] Pa, x [n, nc], rho_l [n], rho_v [n] mol/m³, status [n] int32): the dew point of the vapour y at T.  A used slot
+    with y = 0 is dropped (x = 0.0), a -1 slot has x = NaN; where status != 0 (1 also means "no dew point found at this
+    T"), P and the densities are 0.0 and the x row is NaN.  Asynchronous, on the current stream."""
+    return ops.pcsaft_mix_dew(params, comp, kij, eab, _owner(owner, T), T, y)
+
+
 def mixture_tp_flash(params: torch.Tensor, comp: torch.Tensor, z: torch.Tensor, T: torch.Tensor, P: torch.Tensor,
                      owner: Optional[torch.Tensor] = None, kij: Optional[torch.Tensor] = None,
                      eab: Optional[torch.Tensor] = None
@@ -313,9 +330,11 @@ def _run_mix(kind: str, params: np.ndarray, comp: np.ndarray, kij: Optional[np.n
              owner: np.ndarray, states: np.ndarray) -> Tuple[List[Optional[np.ndarray]], np.ndarray]:
     """states [n, 2 + nc] -> (values, status [n] int32); values is [rho [n]] for kind "density", [rho, lnphi [n, nc],
     None] for "lnphi", [rho, lnphi, lnphi_pure [n, nc]] for "lnphi_pure" and [P [n], y [n, nc], rho_l [n], rho_v [n]]
-    for "bubble", which does not read the P column, and [beta [n], x [n, nc], y [n, nc], rho_l [n], rho_v [n]] for "flash",
-    whose composition columns hold the feed, as do those of "stability": [tpd [n], w [n, nc]] of the points, their nc + 2
-    trials each expanded here into rows of the launch and reduced by ``_reduce_trials`` after the download."""
+    for "bubble", which does not read the P column, [P [n], x [n, nc], rho_l [n], rho_v [n]] for "dew", whose composition
+    columns hold the vapour and which does not read it either, and [beta [n], x [n, nc], y [n, nc], rho_l [n], rho_v [n]]
+    for "flash", whose composition columns hold the feed, as do those of "stability": [tpd [n], w [n, nc]] of the points,
+    their nc + 2 trials each expanded here into rows of the launch and reduced by ``_reduce_trials`` after the
+    download."""
     n, nc = owner.shape[0], comp.shape[1]
     if kind == "stability":
         nt = nc + 2
@@ -329,8 +348,9 @@ def _run_mix(kind: str, params: np.ndarray, comp: np.ndarray, kij: Optional[np.n
     if kind == "flash":
         return _run(ops._pcsaft_mix_flash, [params, comp, kij, eab, owner, states[:, 0], states[:, 1], states[:, 2:]], n,
                     [(n,), (n, nc), (n, nc), (n,), (n,)])
-    if kind == "bubble":
-        return _run(ops._pcsaft_mix_bubble, [params, comp, kij, eab, owner, states[:, 0], states[:, 2:]], n,
+    if kind in ("bubble", "dew"):
+        entry = ops._pcsaft_mix_bubble if kind == "bubble" else ops._pcsaft_mix_dew
+        return _run(entry, [params, comp, kij, eab, owner, states[:, 0], states[:, 2:]], n,
                     [(n,), (n, nc), (n,), (n,)])
     inputs = [params, comp, kij, eab, owner, states[:, 0], states[:, 1], states[:, 2:]]
     if kind == "density":
@@ -499,7 +519,7 @@ def mix_ln_phi_batch(mixtures: List[List[List[Any]]], states_batch: List[Any], k
 
 
 def _failed_nan(values: np.ndarray, P: np.ndarray) -> np.ndarray:
-    """rows of NaN where a bubble point failed (P = 0.0)"""
+    """rows of NaN where a bubble or dew point failed (P = 0.0)"""
     return np.where((P > 0.0)[:, None], values, np.nan)
 
 
@@ -522,6 +542,36 @@ def mix_bubble_batch(mixtures: List[List[List[Any]]], states_batch: List[Any], k
 
     parts = _mix_batch("bubble", mixtures, states_batch, kij, pick)
     return [v[:, :1 + len(mixtures[i])].copy() for i, v in parts]
+
+
+def mix_dew(parameters: Sequence[Sequence[float]], state: Sequence[float], kij_matrix: Optional[Any] = None,
+            epsilon_ab: Optional[Any] = None) -> Tuple[float, np.ndarray]:
+    """Dew point of the vapour ``state = [T (K), P, y1, y2, ...]`` (P is ignored) of the components ``parameters``:
+    (P (Pa), x [k]), the dew half of the reference's ``mix_vp_feos``; raises ``RuntimeError`` where no dew point is found
+    at this T or the solve does not converge."""
+    (P, x, _, _), _ = _mix_point("dew point", "dew", parameters, state, kij_matrix, epsilon_ab)
+    return float(P[0]), x[0, :len(parameters)].copy()
+
+
+def mix_dew_batch(mixtures: List[List[List[Any]]], states_batch: List[Any], kij: Optional[List[Any]] = None
+                  ) -> List[np.ndarray]:
+    """Dew points of every state of every non-empty table in one launch, arguments as ``mix_bubble_batch`` (the
+    composition columns hold the vapour): one fp64 array [rows, 1 + nc_i] of rows ``[P (Pa), x1..x_nc]`` per non-empty
+    table, a row of NaN where a point failed."""
+    def pick(values):
+        return _failed_nan(np.concatenate([values[0][:, None], values[1]], axis=1), values[0])
+
+    parts = _mix_batch("dew", mixtures, states_batch, kij, pick)
+    return [v[:, :1 + len(mixtures[i])].copy() for i, v in parts]
+
+
+def mix_vp(parameters: Sequence[Sequence[float]], state: Sequence[float], kij_matrix: Optional[Any] = None,
+           epsilon_ab: Optional[Any] = None) -> Tuple[float, float]:
+    """(bubble pressure, dew pressure) in Pa of the composition in ``state = [T (K), P, z1, z2, ...]`` (P is ignored),
+    the reference's ``mix_vp_feos``: the composition is the liquid of the bubble point and the vapour of the dew point.
+    The numbers are those of ``mix_bubble`` and ``mix_dew``; raises ``RuntimeError`` where either fails."""
+    return (mix_bubble(parameters, state, kij_matrix, epsilon_ab)[0],
+            mix_dew(parameters, state, kij_matrix, epsilon_ab)[0])
 
 
 def mix_vle_pxy(parameters: Sequence[Sequence[float]], temperature: float, kij_matrix: Optional[Any] = None,

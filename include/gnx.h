@@ -581,6 +581,20 @@ int32_t gnx_pcsaft_mix_bubble(gnx_handle* h, const double* params, int64_t B, co
                               const double* mix_kij, const double* mix_eab, int64_t M, int32_t nc, const int64_t* owner,
                               const double* T, const double* x, int64_t n, double* P, double* y, double* rho_l,
                               double* rho_v, int32_t* status);
+/* Dew point (ref: pcsaft/pcsaft_feos.py mix_vp_feos, the dew half): the bubble entry with the roles of x and y
+ * exchanged.  At T[i] and the vapour composition y[i, :] the pressure P[i] (Pa) at which a first drop of liquid forms,
+ * that liquid's composition x[i, :] and the molar densities rho_l[i], rho_v[i] of both phases (either may be NULL).  The
+ * same equations, by successive substitution on x from Raoult's law on each component's own liquid at zero pressure (a
+ * component without one counts as 100 times as volatile as the most volatile one that has); they hold to 1e-10 at the
+ * numbers returned.  A dew point need not be unique (a retrograde vapour has two): the one reported is the one that
+ * start leads to.  A used slot with y = 0 is dropped; its x is 0.0, that of a -1 slot NaN.  A point with status != 0 has
+ * P = 0.0, NaN in its whole x row and densities 0.0; status 1 covers every failure that is not bad input: no component
+ * with a liquid at zero pressure, no root, no end within 400 steps, only the trivial solution.  The launch has no kernel
+ * id (GNX_K_NONE). */
+int32_t gnx_pcsaft_mix_dew(gnx_handle* h, const double* params, int64_t B, const int64_t* mix_comp,
+                           const double* mix_kij, const double* mix_eab, int64_t M, int32_t nc, const int64_t* owner,
+                           const double* T, const double* y, int64_t n, double* P, double* x, double* rho_l,
+                           double* rho_v, int32_t* status);
 /* Isothermal two-phase flash (ref: pcsaft/pcsaft_feos.py mix_tp_flash_feos): at T[i], P[i] (Pa) the split of the feed
  * z[i, :] (normalised by its sum) into a liquid x[i, :] and a vapour y[i, :], the vapour mole fraction beta[i] in [0, 1]
  * and the molar densities rho_l[i], rho_v[i] of both phases (either may be NULL).  Equal mu_i^res/kT + ln(rho x_i) of

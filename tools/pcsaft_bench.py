@@ -12,6 +12,10 @@ With ``--bubble`` it times the bubble-point kernel of csrc/gnx_pcsaft_mix_vle.hi
 tests/pcsaft_mix_vle_ref.py and the first point of each system of the binary fixture, repeated, and that module's oracle
 solve on a sample.  The launch has no kernel id, so the events around the call are the only timing there is.
 
+With ``--dew`` it times the dew-point kernel of csrc/gnx_pcsaft_mix_dew.hip on the vapours of those bubble points (the y
+the bubble kernel reports for them), repeated, the bubble-point kernel on the liquids of the same points in the same run
+for the ratio, and the oracle of tests/pcsaft_mix_dew_ref.py on a sample.
+
 With ``--flash`` it times the (T, P) flash kernel of csrc/gnx_pcsaft_mix_flash.hip on the tie-line feeds of
 tests/pcsaft_mix_flash_ref.py (the six named bubble points at beta = 0.3, six fixture points at beta = 0.5), repeated, the
 bubble-point kernel on the liquids of the same tie lines for the ratio, and that module's oracle flash on a sample.
@@ -20,7 +24,7 @@ With ``--stability`` it times the tangent-plane stability test of csrc/gnx_pcsaf
 ``pcsaft.mixture_stability`` (nc + 2 = 6 trial rows per point) on the 43 cases of tests/pcsaft_mix_stab_ref.py, repeated,
 the flash kernel on the 12 tie-line feeds among them in the same run, and that module's oracle on a sample.
 
-Usage: python tools/pcsaft_bench.py [--mixture | --bubble | --flash | --stability] [--reps 3] [--sizes 1000,100000,1000000] [--oracle-sample 20] [--out FILE.json]
+Usage: python tools/pcsaft_bench.py [--mixture | --bubble | --dew | --flash | --stability] [--reps 3] [--sizes 1000,100000,1000000] [--oracle-sample 20] [--out FILE.json]
 """
 import argparse
 import json
@@ -119,6 +123,43 @@ def _bubble(args, dev):
     return res
 
 
+def _dew(args, dev):
+    from tests import pcsaft_mix_dew_ref as D
+    from tests import pcsaft_mix_vle_ref as V
+    cases = list(V.NAMED) + V.fixture_cases()
+    params, comp, T, x = [], np.full((len(cases), 4), -1, dtype=np.int64), [], np.zeros((len(cases), 4))
+    for i, (_, rows, t, xi) in enumerate(cases):
+        comp[i, :len(rows)] = np.arange(len(params), len(params) + len(rows))
+        params.extend(np.asarray(rows, dtype=np.float64).tolist())
+        x[i, :len(rows)] = xi
+        T.append(t)
+    T = np.array(T)
+    d_params, d_comp = torch.from_numpy(np.array(params)).to(dev), torch.from_numpy(comp).to(dev)
+    every = torch.arange(len(cases), dtype=torch.int64, device=dev)
+    _, y, _, _, st = pcsaft.mixture_bubble_pressure(d_params, d_comp, torch.from_numpy(x).to(dev),
+                                                   torch.from_numpy(T).to(dev), every)
+    assert int((st != 0).sum().item()) == 0, "a bubble point failed: no vapour to start from"
+    y = torch.nan_to_num(y).cpu().numpy()
+    step = max(1, len(cases) // args.oracle_sample)
+    t0 = time.perf_counter()
+    sols = [D.dew(rows, y[j, :len(rows)], t) for j, (_, rows, t, _) in list(enumerate(cases))[::step]]
+    oracle = (time.perf_counter() - t0) / len(sols)
+    res = []
+    for n in [int(s) for s in args.sizes.split(",")]:
+        idx = np.arange(n) % len(cases)
+        o, t, xx, yy = (torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+                        for a in (idx.astype(np.int64), T[idx], x[idx], y[idx]))
+        k = _kernel_ms(lambda: pcsaft.mixture_dew_pressure(d_params, d_comp, yy, t, o))
+        st = pcsaft.mixture_dew_pressure(d_params, d_comp, yy, t, o)[4]
+        kb = _kernel_ms(lambda: pcsaft.mixture_bubble_pressure(d_params, d_comp, xx, t, o))
+        rec = dict(points=n, mix_dew_kernel_ms=k, mix_dew_points_per_s=n / k * 1e3,
+                   failed_points=int((st != 0).sum().item()), mix_bubble_same_points_kernel_ms=kb, dew_over_bubble=k / kb,
+                   oracle_dew_ms_est=oracle * n * 1e3)
+        print(json.dumps(rec), flush=True)
+        res.append(rec)
+    return res
+
+
 def _flash(args, dev):
     from tests import pcsaft_mix_flash_ref as F
     points = F.tie_line_points()
@@ -192,15 +233,16 @@ def main():
     ap.add_argument("--oracle-sample", type=int, default=20)
     ap.add_argument("--mixture", action="store_true")
     ap.add_argument("--bubble", action="store_true")
+    ap.add_argument("--dew", action="store_true")
     ap.add_argument("--flash", action="store_true")
     ap.add_argument("--stability", action="store_true")
     ap.add_argument("--reps", type=int, default=REPS, help="timed repetitions per kernel, the best of which counts")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     REPS = args.reps
-    if args.mixture or args.bubble or args.flash or args.stability:
+    if args.mixture or args.bubble or args.dew or args.flash or args.stability:
         dev = torch.device("cuda", torch.cuda.current_device())
-        res = (_stability if args.stability else _flash if args.flash else _bubble if args.bubble else _mixture)(args, dev)
+        res = (_stability if args.stability else _flash if args.flash else _dew if args.dew else _bubble if args.bubble else _mixture)(args, dev)
         if args.out:
             with open(args.out, "w") as fh:
                 json.dump(dict(device=torch.cuda.get_device_name(dev), oracle_sample=args.oracle_sample, results=res), fh,
