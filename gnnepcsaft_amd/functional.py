@@ -6,12 +6,14 @@ reference wires at ``/root/reference/gnnepcsaft/train/models.py``.
 """
 from __future__ import annotations
 
+from collections import namedtuple
 from typing import Optional, Sequence
 
 import torch
 
-from . import ops
+from . import ops, pna_native
 from .ops import GraphPack
+from .pna_native import PnaLayerGrads, PnaDims
 
 
 # ---- module switches (plain module state; each has a setter and a read accessor) -------------------------------------
@@ -268,47 +270,42 @@ class HuberAPEFn(torch.autograd.Function):
         return dpred * dloss, None, None
 
 
-def _pna_weight_only(BE, T, F, pre_layers, post_layers, avg_deg_log, params, D):
-    """Everything a PNAConv forward needs that depends on the weights alone (plus the number of degree classes D, 0 =
-    ungrouped): EE = BondEmb W_enc^T + b_enc [R,F];  Te = per tower EE W_e^T + b (the edge part of pre-layer 0 on the
-    60-row bond table) [R,H];  Weff(d) per tower;  the merged (lin o last post layer) weight / bias."""
-    R, H = BE.size(0), T * F
-    merged = post_layers > 1  # the last post layer and ``lin`` as ONE product with a merged H x H weight (see forward)
+# The weight-only part of a PNAConv forward: EE = BondEmb W_enc^T + b_enc [R,F];  Te = per tower EE W_e^T + b (the edge part
+# of pre-layer 0 on the 60-row bond table) [R,H];  Weff(d) per tower;  the merged (lin o last post layer) weight / bias or
+# None;  ``images``: (PnaLayerImages, slab) of ``WeightOnlyAll``, the layer's split weight images, or None.
+PnaPrep = namedtuple("PnaPrep", "EE Te weffs Wm bm images", defaults=(None,))
+# ``cfg`` of ``PNAConvFn.apply``; a plain tuple of the first five, six or all eight fields is accepted as well.
+PnaCfg = namedtuple("PnaCfg", "T F pre_layers post_layers avg_deg_log prepared bond_acc layer_index", defaults=(None, None, 0))
+
+
+def _pna_weight_only(BE, dims: PnaDims, avg_deg_log, params) -> PnaPrep:
+    """Everything a PNAConv forward needs that depends on the weights alone (plus the number of degree classes, 0 =
+    ungrouped); ``dims.merged`` says whether the last post layer and ``lin`` become ONE product (see forward)."""
+    T, F, R, H, D = dims.T, dims.F, dims.R, dims.H, dims.D
     if _NATIVE_LAYER_BWD and BE.is_cuda and T <= 8:
         # one native call (gnx_pna_weight_only) instead of 5 + 3 (T - 1) launches from Python
-        import ctypes as C
-        from . import _lib
         EE, Te = _empty(R, F, BE), _empty(R, H, BE)
         weffs = [torch.empty(D, F, 4 * F, dtype=torch.float32, device=BE.device) for _ in range(T)] if D > 0 else []
-        Wm = _empty(H, H, BE) if merged else None
-        bm = torch.empty(H, dtype=torch.float32, device=BE.device) if merged else None
-        n = len(params)
-        parr = (C.c_void_p * n)(*[p.data_ptr() for p in params])
-        warr = (C.c_void_p * max(T, 1))(*[w.data_ptr() for w in weffs]) if weffs else None
-        ops.check(_lib.load().gnx_pna_weight_only(
-            _lib.handle(BE.device), BE.data_ptr(), R, T, F, pre_layers, post_layers, D, float(avg_deg_log),
-            C.cast(parr, C.POINTER(C.c_void_p)), int(merged), EE.data_ptr(), Te.data_ptr(),
-            None if warr is None else C.cast(warr, C.POINTER(C.c_void_p)), None if Wm is None else Wm.data_ptr(),
-            None if bm is None else bm.data_ptr()))
-        return EE, Te, weffs, Wm, bm
+        Wm = _empty(H, H, BE) if dims.merged else None
+        bm = torch.empty(H, dtype=torch.float32, device=BE.device) if dims.merged else None
+        pna_native.weight_only(BE, dims, avg_deg_log, params, EE, Te, weffs, Wm, bm)
+        return PnaPrep(EE, Te, weffs, Wm, bm)
     enc_w, enc_b, lin_w, lin_b = params[:4]
-    per = 2 * (pre_layers + post_layers)
     sl = _tower_slices(T, F)
     EE = ops.gemm([(BE, None, enc_w)], _empty(R, F, BE), bias=enc_b)
     Te = _empty(R, H, BE)
     weffs, last = [], []
     for t in range(T):
-        W0, b0 = params[4 + t * per], params[4 + t * per + 1]
-        ops.gemm([(EE, None, W0[:, 2 * F:3 * F])], _cols(Te, sl[t]), bias=b0)
-        Wp = params[4 + t * per + 2 * pre_layers]
+        k0 = dims.param_index(t, "pre", 0)
+        ops.gemm([(EE, None, params[k0][:, 2 * F:3 * F])], _cols(Te, sl[t]), bias=params[k0 + 1])
         if D > 0:
-            weffs.append(ops.pna_weff(Wp, F, D, avg_deg_log))
-        k = 4 + t * per + 2 * (pre_layers + post_layers - 1)
+            weffs.append(ops.pna_weff(params[dims.param_index(t, "post", 0)], F, D, avg_deg_log))
+        k = dims.param_index(t, "post", dims.post_layers - 1)
         last.append((params[k], params[k + 1]))
     Wm = bm = None
-    if merged:
+    if dims.merged:
         Wm, bm = _merge_last_post_with_lin(lin_w, lin_b, last, sl, BE)
-    return EE, Te, weffs, Wm, bm
+    return PnaPrep(EE, Te, weffs, Wm, bm)
 
 
 class BondGradAccumulator:
@@ -322,59 +319,40 @@ class BondGradAccumulator:
         self.encoder = None  # (combos, offsets, tables) of the BondEncoder whose table() this gradient belongs to
         # deferred small work (functional.set_batch_weight_only): every PNA layer's backward leaves its 60-row bond-table
         # chain, its lin o last-post un-merge and its Weff gradient to ONE batched finish at the end of the pass
-        self.defer = False
         self.slab = None      # zero-filled fp32 slab: [acc.buf | per layer: dTe, dEE, dWm, dbm, dWeff x T]
-        self.deferred = []    # per deferring layer: dict of what gnx_pna_stack_finish needs (keeps the tensors alive)
+        self.deferred = []    # per deferring layer: the PnaLayerGrads of gnx_pna_stack_finish (keeps the tensors alive)
 
-    def layer_slab(self, layer_index: int, R: int, H: int, F: int, T: int, D: int, device):
-        """This layer's zeroed accumulators (dTe [R,H], dEE [R,F], dWm [H,H], dbm [H], dWeff [T,D,F,4F]) inside the slab
-        shared by the model's layers: ONE fill launch per backward pass, issued by the layer whose backward runs first
-        (which also stands in for clearing ``buf``, the slab's first R x H entries)."""
-        per = R * H + R * F + H * H + H + T * D * F * 4 * F
+    def layer_slab(self, layer_index: int, dims: PnaDims, device) -> torch.Tensor:
+        """This layer's zeroed accumulators (``dims.small_sizes()``, back to back) inside the slab shared by the model's
+        layers: ONE fill launch per backward pass, issued by the layer whose backward runs first (which also stands in for
+        clearing ``buf``, the slab's first R x H entries)."""
+        RH, per = dims.R * dims.H, dims.small_total
         if self.slab is None:
-            self.slab = ops.zeros(R * H + self.depth * per, device=device)
-            self.buf = self.slab[:R * H].view(R, H)
-        o = R * H + layer_index * per
-        out = []
-        for n in (R * H, R * F, H * H, H, T * D * F * 4 * F):
-            out.append(self.slab[o:o + n])
-            o += n
-        return out
+            self.slab = ops.zeros(RH + self.depth * per, device=device)
+            self.buf = self.slab[:RH].view(dims.R, dims.H)
+        o = RH + layer_index * per
+        return self.slab[o:o + per]
 
     def finish_deferred(self, device) -> None:
-        """gnx_pna_stack_finish over the layers that deferred (side stream 1: bond chain tails; side stream 0: un-merge and
-        Weff gradients, behind the layers' weight gradients)."""
-        if not self.deferred:
-            return
-        import ctypes as C
-        from . import _lib
-        d0 = self.deferred[0]
-        L = len(self.deferred)
-        T, F, pre, post, R, D, merged = d0["T"], d0["F"], d0["pre"], d0["post"], d0["R"], d0["D"], d0["merged"]
-        np_ = 4 + T * 2 * (pre + post)
-        a = _lib.PnaFinishArgs()
-        a.L, a.T, a.F, a.pre_layers, a.post_layers, a.R, a.D, a.merged = L, T, F, pre, post, R, D, int(merged)
-        a.use_side_streams = int(ops.wgrad_stream_enabled())
-        ones = ops.ones_vector(device, max(R, 1))
-        a.BE, a.acc_buf, a.ones = d0["BE"].data_ptr(), self.buf.data_ptr(), ones.data_ptr()
-        avg = (C.c_float * L)(*[d["avg"] for d in self.deferred])
-        vp = C.c_void_p
-        params = (vp * (L * np_))(*[p.data_ptr() for d in self.deferred for p in d["params"]])
-        grads = (vp * (L * np_))(*[g.data_ptr() for d in self.deferred for g in d["sinks"]])
-        EE = (vp * L)(*[d["EE"].data_ptr() for d in self.deferred])
-        dTe = (vp * L)(*[d["dTe"].data_ptr() for d in self.deferred])
-        dEE = (vp * L)(*[d["dEE"].data_ptr() for d in self.deferred])
-        dWm = (vp * L)(*[d["dWm"].data_ptr() for d in self.deferred])
-        dbm = (vp * L)(*[d["dbm"].data_ptr() for d in self.deferred])
-        per_w = D * F * 4 * F
-        dWeff = (vp * (L * T))(*[d["dWeff"].data_ptr() + 4 * t * per_w for d in self.deferred for t in range(T)])
-        a.avg_deg_log = C.cast(avg, C.POINTER(C.c_float))
-        for name, arr in (("params", params), ("grads", grads), ("EE", EE), ("dTe", dTe), ("dEE", dEE), ("dWm", dWm),
-                          ("dbm", dbm), ("dWeff", dWeff)):
-            setattr(a, name, C.cast(arr, C.POINTER(vp)))
-        ops.check(_lib.load().gnx_pna_stack_finish(_lib.handle(device), C.byref(a)))
-        ops.keep_until_join(device, [self.slab, ones] + [t for d in self.deferred for t in (d["BE"], d["EE"], *d["params"], *d["sinks"])])
+        """gnx_pna_stack_finish over the layers that deferred; raises GnxError if their shapes differ."""
+        if self.deferred:
+            ops.keep_until_join(device, [self.slab] + pna_native.stack_finish(device, self.deferred, self.buf))
         self.deferred = []
+
+    def add(self, layer_index: int, d: torch.Tensor, w: torch.Tensor) -> None:
+        """buf += d @ w on the current stream.  The layers of one model share the accumulator; the layer whose backward
+        runs first clears it."""
+        if self.first_in_backward(layer_index):
+            ops.zero_(self.buf)
+        ops.gemm([(d, None, w)], self.buf, b_trans=False, accumulate=True)
+
+    def run_chain(self, layer_index: int, ref: torch.Tensor, keep: list, chain) -> Optional[torch.Tensor]:
+        """Runs a layer's bond-table gradient chain on side stream 1, forked from the main stream here (behind the kernel
+        that produced ``ref``).  ``keep``: what the chain reads; ``chain()`` returns its temporaries; both stay alive until
+        the join.  Returns None, or for layer 0 -- the last conv backward of the pass -- the ``handoff``."""
+        keep = keep + [self.buf]
+        ops.run_on_second_side_stream(ref, keep, lambda: keep.extend(chain()))
+        return self.handoff(ref.device) if layer_index == 0 else None
 
     def first_in_backward(self, layer_index: int) -> bool:
         return layer_index == self.depth - 1
@@ -404,10 +382,10 @@ class WeightOnlyAhead:
 
     def __init__(self, BE, T, F, pre_layers, post_layers, avg_deg_log, params, D):
         self.device = BE.device
+        dims = PnaDims(T, F, pre_layers, post_layers, BE.size(0), D, post_layers > 1)
         box = []
         # raw kernel launches on .data pointers: nothing here is recorded by autograd, so no detach() is needed
-        ops.run_after_wgrads(BE, (), lambda: box.append(_pna_weight_only(BE, T, F, pre_layers, post_layers, avg_deg_log,
-                                                                        params, D)))
+        ops.run_after_wgrads(BE, (), lambda: box.append(_pna_weight_only(BE, dims, avg_deg_log, params)))
         self.value = box[0]
 
     def wait(self):
@@ -427,47 +405,22 @@ class WeightOnlyAll:
     ``(PnaLayerImages, slab)``, else None.  The plans need both numbers: a product below 4096 rows reads no images."""
 
     def __init__(self, BE, T, F, pre_layers, post_layers, layers, D, n_rows: int = 0, tile_rows: int = 0):
-        import ctypes as C
-        from . import _lib
         self.device = BE.device
-        L, R, H = len(layers), BE.size(0), T * F
-        merged = post_layers > 1
+        dims = PnaDims(T, F, pre_layers, post_layers, BE.size(0), D, post_layers > 1)
+        L, R, H = len(layers), dims.R, dims.H
         f32 = dict(dtype=torch.float32, device=BE.device)
         EE = torch.empty(L, R, F, **f32)
         Te = torch.empty(L, R, H, **f32)
         weff = torch.empty(L, T, D, F, 4 * F, **f32) if D > 0 else None
-        Wm = torch.empty(L, H, H, **f32) if merged else None
-        bm = torch.empty(L, H, **f32) if merged else None
-        vp = C.c_void_p
-        np_ = len(layers[0][1])
-        avg = (C.c_float * L)(*[float(a_) for a_, _ in layers])
-        params = (vp * (L * np_))(*[p.data_ptr() for _, ps in layers for p in ps])
-        ptrs = lambda t_, n: (vp * n)(*[t_[i].data_ptr() for i in range(n)]) if t_ is not None else None  # noqa: E731
-        a_EE, a_Te, a_Wm, a_bm = ptrs(EE, L), ptrs(Te, L), ptrs(Wm, L), ptrs(bm, L)
-        a_weff = (vp * (L * T))(*[weff[l, t].data_ptr() for l in range(L) for t in range(T)]) if weff is not None else None
-        cast = lambda arr: None if arr is None else C.cast(arr, C.POINTER(vp))  # noqa: E731
-        lib = _lib.load()
-        slab, images = None, None
-        if _SPLIT_ALL and weff is not None and n_rows > 0:
-            need = lib.gnx_pna_split_all_bytes(_lib.handle(BE.device), L, T, F, pre_layers, post_layers, D, n_rows, tile_rows)
-            if need > 0:
-                slab = torch.empty(need, dtype=torch.uint8, device=BE.device)
-                images = (_lib.PnaLayerImages * L)()
-
-        def launch():
-            ops.check(_lib.load().gnx_pna_weight_only_all(
-                _lib.handle(BE.device), L, BE.data_ptr(), R, T, F, pre_layers, post_layers, D,
-                C.cast(avg, C.POINTER(C.c_float)), cast(params), int(merged), cast(a_EE), cast(a_Te), cast(a_weff),
-                cast(a_Wm), cast(a_bm)))
-            if slab is not None:
-                ops.check(lib.gnx_pna_split_all(_lib.handle(BE.device), L, T, F, pre_layers, post_layers, D, n_rows, tile_rows,
-                                                cast(params), cast(a_weff), slab.data_ptr(), slab.numel(), images))
-
-        keep = [BE, EE, Te, weff, Wm, bm, slab] + [p for _, ps in layers for p in ps]
-        ops.run_after_wgrads(BE, keep, launch)
-        self.values = [(EE[l], Te[l], [weff[l, t] for t in range(T)] if weff is not None else [],
-                        Wm[l] if merged else None, bm[l] if merged else None,
-                        (images[l], slab) if slab is not None else None) for l in range(L)]
+        Wm = torch.empty(L, H, H, **f32) if dims.merged else None
+        bm = torch.empty(L, H, **f32) if dims.merged else None
+        split = _SPLIT_ALL and weff is not None and n_rows > 0
+        need = pna_native.split_all_bytes(BE.device, L, dims, n_rows, tile_rows) if split else 0
+        slab = torch.empty(need, dtype=torch.uint8, device=BE.device) if need > 0 else None
+        images = pna_native.weight_only_all(BE, dims, layers, EE, Te, weff, Wm, bm, slab, n_rows, tile_rows)
+        self.values = [PnaPrep(EE[l], Te[l], [weff[l, t] for t in range(T)] if weff is not None else [],
+                               Wm[l] if dims.merged else None, bm[l] if dims.merged else None,
+                               (images[l], slab) if slab is not None else None) for l in range(L)]
         self._joined = False
 
     def get(self, l: int):
@@ -503,150 +456,63 @@ def _unmerge_last_post_and_lin(dWm, dbm, lin_w, d_lin_w, d_lin_b, last, last_bia
     ops.axpy_(d_lin_b, dbm)
 
 
-def _pna_forward_native(ctx, x, BE, pack, cfg, params, dc, prep):
+def _edge_tiles(pack, dims: PnaDims):
+    """Edge tiles of the fused gather -> pre-layer 1 -> aggregate kernel (D - 1 bounds the in-degree: a batch above the hint
+    trips the range flag; cached on the pack), or None: the three-launch sequence, as when the table is not eligible."""
+    return pack.edge_tiles(dims.D - 1) if (_FUSED_EDGE and dims.pre_layers == 2) else None
+
+
+def _pna_forward_native(ctx, x, BE, pack, dims, avg_deg_log, params, dc, prep):
     """PNAConvFn.forward through gnx_pna_conv_fwd (one call for the ~12 launches after the weight-only part)."""
-    import ctypes as C
-    from . import _lib
-    T, F, pre_layers, post_layers, avg_deg_log = cfg[:5]
-    EE, Te, weffs, Wm, bm = prep[:5]
-    images = prep[5] if len(prep) > 5 else None  # (PnaLayerImages, slab) of WeightOnlyAll, kept for the backward
-    N, H = x.shape
-    E, D = pack.E, dc.D
-    dev = x.device
-    merged = Wm is not None
-    n_z = post_layers - 1 if merged else post_layers
-    f32 = dict(dtype=torch.float32, device=dev)
+    (N, H), E = x.shape, pack.E
+    n_z = dims.post_layers - 1 if dims.merged else dims.post_layers
+    f32 = dict(dtype=torch.float32, device=x.device)
     PQ = torch.empty(2, N, H, **f32)
-    hs_all = torch.empty(pre_layers, max(E, 1), H, **f32)
+    hs_all = torch.empty(dims.pre_layers, max(E, 1), H, **f32)
     zs_all = torch.empty(max(n_z, 1), N, H, **f32)
-    A = torch.empty(N, T * 4 * F, **f32)
+    A = torch.empty(N, dims.T * 4 * dims.F, **f32)
     out = torch.empty(N, H, **f32)
-    lib = _lib.load()
-    ws_bytes = lib.gnx_pna_conv_bwd_workspace_bytes(T, F, D)
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-    a = _lib.PnaFwdArgs()
-    a.N, a.E, a.T, a.F, a.pre_layers, a.post_layers, a.D, a.merged = N, E, T, F, pre_layers, post_layers, D, int(merged)
-    a.rowptr, a.src, a.dst, a.code = pack.rowptr.data_ptr(), pack.src.data_ptr(), pack.dst.data_ptr(), pack.code.data_ptr()
-    a.dperm, a.tiles, a.ntiles, a.max_tiles = dc.dperm.data_ptr(), dc.tiles_p.data_ptr(), dc.ntiles_p.data_ptr(), dc.max_tiles_p
-    a.tile_rows = dc.tile_rows_p
-    a.x, a.Te = x.data_ptr(), Te.data_ptr()
-    for i, w in enumerate(weffs):
-        a.weff[i] = w.data_ptr()
-    a.Wm, a.bm = (Wm.data_ptr(), bm.data_ptr()) if merged else (None, None)
-    n = len(params)
-    parr = (C.c_void_p * n)(*[p.data_ptr() for p in params])
-    a.params = C.cast(parr, C.POINTER(C.c_void_p))
-    a.P, a.Q, a.A = PQ[0].data_ptr(), PQ[1].data_ptr(), A.data_ptr()
-    hs = [hs_all[i][:E] if E != hs_all.size(1) else hs_all[i] for i in range(pre_layers)]
+    ws = torch.empty(pna_native.workspace_bytes(dims), dtype=torch.uint8, device=x.device)
+    hs = [hs_all[i][:E] if E != hs_all.size(1) else hs_all[i] for i in range(dims.pre_layers)]
     zs = [zs_all[i] for i in range(n_z)]
-    for i, t_ in enumerate(hs):
-        a.hs[i] = t_.data_ptr()
-    for i, t_ in enumerate(zs):
-        a.zs[i] = t_.data_ptr()
-    a.ws, a.ws_bytes, a.out = ws.data_ptr(), ws_bytes, out.data_ptr()
-    # edge tiles of the fused gather -> pre-layer 1 -> aggregate kernel (D - 1 bounds the in-degree: a batch above the
-    # hint trips the range flag); the library falls back to the three-launch sequence when it is not eligible
-    etiles = pack.edge_tiles(D - 1) if (_FUSED_EDGE and pre_layers == 2) else None
-    a.etile_info, a.etile_w = (etiles[0].data_ptr(), etiles[1]) if etiles is not None else (None, 0)
-    if images is None:
-        ops.check(lib.gnx_pna_conv_fwd(_lib.handle(dev), C.byref(a)))
-    else:
-        ops.check(lib.gnx_pna_conv_fwd_images(_lib.handle(dev), C.byref(a), C.byref(images[0])))
-    amp, att = pack.degree_scalers(avg_deg_log)
-    ctx.pack, ctx.cfg = pack, cfg[:5]
-    ctx.n_h, ctx.n_z = len(hs), len(zs)
-    ctx.sinks = grad_sinks(params)
-    ctx.dc, ctx.weffs, ctx.Wm = dc, weffs, Wm
-    ctx.images = images
-    ctx.save_for_backward(x, BE, EE, A, amp, att, *hs, *zs, *params)
+    # (PnaLayerImages, slab) of WeightOnlyAll and the pointer array of ``params``, kept for the backward
+    ctx.images, ctx.parr = prep.images, pna_native.conv_fwd(dims, pack, dc, _edge_tiles(pack, dims), prep, params, x=x, PQ=PQ,
+                                                            A=A, hs=hs, zs=zs, ws=ws, out=out)
+    ctx.save_for_backward(x, BE, prep.EE, A, *pack.degree_scalers(avg_deg_log), *hs, *zs, *params)
     return out
 
 
 def _pna_backward_native(ctx, dout, x, BE, EE, A, hs, zs, params, sinks, code_pos):
-    """PNAConvFn.backward through gnx_pna_conv_bwd: Python only allocates the temporaries and fills the argument block."""
-    import ctypes as C
-    from . import _lib
-    T, F, pre_layers, post_layers, avg_deg_log = ctx.cfg
-    pack, dc, acc = ctx.pack, ctx.dc, ctx.bond_acc
-    N, H = x.shape
-    E, R, D = pack.E, BE.size(0), dc.D
-    dev = x.device
+    """PNAConvFn.backward through gnx_pna_conv_bwd: Python only allocates the temporaries."""
+    dims, pack, acc = ctx.dims, ctx.pack, ctx.bond_acc
+    (N, H), dev = x.shape, x.device
     dout = dout.contiguous()
-    merged = ctx.Wm is not None
-    n_g = post_layers - 1 if merged else post_layers
+    n_g = dims.post_layers - 1 if dims.merged else dims.post_layers
     f32 = dict(dtype=torch.float32, device=dev)
     gbuf = torch.empty(max(n_g, 1), N, H, **f32)
-    gebuf = torch.empty(pre_layers, max(E, 1), H, **f32)
-    dA = torch.empty(N, T * 4 * F, **f32)
+    gebuf = torch.empty(dims.pre_layers, max(pack.E, 1), H, **f32)
+    dA = torch.empty(N, dims.T * 4 * dims.F, **f32)
     pq = torch.empty(2, N, H, **f32)
-    # small accumulators: private scratch, or (deferral) zeroed slices of the model's slab that stay alive until the ONE
+    # small accumulators: private scratch, or (deferral) a zeroed part of the model's slab that stays alive until the ONE
     # batched finish at the end of the pass; a data-parallel exchange that hands every layer's slice to RCCL the moment
     # its launches are issued (ops.set_wgrad_done_hook) needs the layer's gradients complete here: no deferral then
-    defer = _BATCH_WEIGHT_ONLY and acc is not None and not ops.wgrad_done_hook_set() and \
+    defer = _BATCH_WEIGHT_ONLY and not ops.wgrad_done_hook_set() and \
         (acc.slab is not None or acc.first_in_backward(ctx.layer_index))
+    small = acc.layer_slab(ctx.layer_index, dims, dev) if defer else torch.empty(dims.small_total, **f32)
+    grads = PnaLayerGrads(dims, float(ctx.avg_deg_log), BE, EE, params, sinks, small)
     if defer:
-        dTe_t, dEE_t, dWm_t, dbm_t, dWeff_t = acc.layer_slab(ctx.layer_index, R, H, F, T, D, dev)
-        small = None
-    else:
-        small = torch.empty(R * H + R * F + H * H + H + T * D * F * 4 * F, **f32)
+        acc.deferred.append(grads)
     dx = torch.empty(N, H, **f32)
-    lib = _lib.load()
-    ws_bytes = lib.gnx_pna_conv_bwd_workspace_bytes(T, F, D)
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-    a = _lib.PnaBwdArgs()
-    a.N, a.E, a.T, a.F, a.pre_layers, a.post_layers, a.R, a.D = N, E, T, F, pre_layers, post_layers, R, D
-    a.avg_deg_log, a.merged = float(avg_deg_log), int(merged)
-    a.acc_first, a.use_side_streams = int(acc.first_in_backward(ctx.layer_index)), int(ops.wgrad_stream_enabled())
-    a.n_h, a.n_z = len(hs), len(zs)
-    a.rowptr, a.colptr, a.cpos, a.code = pack.rowptr.data_ptr(), pack.colptr.data_ptr(), pack.cpos.data_ptr(), pack.code.data_ptr()
-    a.code_pos = None if code_pos is None else code_pos.data_ptr()
-    a.dperm, a.tiles, a.ntiles = dc.dperm.data_ptr(), dc.tiles.data_ptr(), dc.ntiles.data_ptr()
-    a.chunks, a.nchunks, a.max_tiles, a.max_chunks = dc.chunks.data_ptr(), dc.nchunks.data_ptr(), dc.max_tiles, dc.max_chunks
-    a.x, a.BE, a.EE, a.A = x.data_ptr(), BE.data_ptr(), EE.data_ptr(), A.data_ptr()
-    for i, t_ in enumerate(hs):
-        a.hs[i] = t_.data_ptr()
-    for i, t_ in enumerate(zs):
-        a.zs[i] = t_.data_ptr()
-    for i, t_ in enumerate(ctx.weffs):
-        a.weff[i] = t_.data_ptr()
-    a.Wm = ctx.Wm.data_ptr() if merged else None
-    n = len(params)
-    parr = (C.c_void_p * n)(*[p.data_ptr() for p in params])
-    garr = (C.c_void_p * n)(*[g_.data_ptr() for g_ in sinks])
-    a.params, a.grads, a.dout = C.cast(parr, C.POINTER(C.c_void_p)), C.cast(garr, C.POINTER(C.c_void_p)), dout.data_ptr()
-    for i in range(gbuf.size(0)):
-        a.gbuf[i] = gbuf[i].data_ptr()
-    for i in range(pre_layers):
-        a.gebuf[i] = gebuf[i].data_ptr()
-    a.dA, a.dP, a.dQ = dA.data_ptr(), pq[0].data_ptr(), pq[1].data_ptr()
-    if defer:
-        a.dTe, a.dEE, a.dWm, a.dbm, a.dWeff = (t_.data_ptr() for t_ in (dTe_t, dEE_t, dWm_t, dbm_t, dWeff_t))
-        a.flags = _lib.PNA_BWD_DEFER_SMALL
-        acc.deferred.append(dict(T=T, F=F, pre=pre_layers, post=post_layers, R=R, D=D, merged=merged, avg=float(avg_deg_log),
-                                 BE=BE, EE=EE, params=list(params), sinks=list(sinks), dTe=dTe_t, dEE=dEE_t, dWm=dWm_t,
-                                 dbm=dbm_t, dWeff=dWeff_t))
-    else:
-        base, o = small.data_ptr(), 0
-        a.dTe, o = base + 4 * o, o + R * H
-        a.dEE, o = base + 4 * o, o + R * F
-        a.dWm, o = base + 4 * o, o + H * H
-        a.dbm, o = base + 4 * o, o + H
-        a.dWeff = base + 4 * o
-        a.flags = 0
-    if ctx.layer_index == 0:
-        # the last conv backward of the pass: its batched weight gradients take every CU, at the end of the layer (6.760 ->
-        # 6.687 ms; the post layers' ones launched earlier, before the edge backward, compete with it: 6.612 vs 6.554 ms)
-        a.flags |= _lib.PNA_BWD_LAST_OF_PASS
-    a.ws, a.ws_bytes, a.acc_buf, a.dx = ws.data_ptr(), ws_bytes, acc.buf.data_ptr(), dx.data_ptr()
-    etiles = pack.edge_tiles(D - 1) if (_FUSED_EDGE and pre_layers == 2) else None  # (the forward's table, cached on the pack)
-    a.etile_info, a.etile_w = (etiles[0].data_ptr(), etiles[1]) if etiles is not None else (None, 0)
-    images = getattr(ctx, "images", None)
-    ops.pna_conv_bwd(a, dev, images[0] if images is not None else None)
+    ws = torch.empty(pna_native.workspace_bytes(dims), dtype=torch.uint8, device=dev)
+    last = ctx.layer_index == 0  # the last conv backward of the pass
+    keep = pna_native.conv_bwd(grads, pack, ctx.dc, _edge_tiles(pack, dims), code_pos, x=x, A=A, hs=hs, zs=zs, weffs=ctx.weffs,
+                               Wm=ctx.Wm, dout=dout, gbuf=gbuf, gebuf=gebuf, dA=dA, dPQ=pq, ws=ws, acc_buf=acc.buf, dx=dx,
+                               acc_first=acc.first_in_backward(ctx.layer_index), defer=defer, last_of_pass=last,
+                               images=ctx.images[0] if ctx.images is not None else None, parr=ctx.parr)
     # everything the side-stream launches touch stays alive until the join at the end of backward
-    ops.keep_until_join(dev, [dout, x, BE, EE, A, *hs, *zs, *ctx.weffs, ctx.Wm, gbuf, gebuf, dA, pq, small, ws, acc.buf,
-                              acc.slab, *params, *sinks])
+    ops.keep_until_join(dev, keep + [acc.slab])
     dBE = None
-    if ctx.layer_index == 0:  # the last conv backward of the pass: the deferred small work, then the bond encoder's own
+    if last:  # the deferred small work, then the bond encoder's own backward
         acc.finish_deferred(dev)
         dBE = acc.handoff(dev)
     ops.finish_backward(dev, True, sinks)
@@ -666,28 +532,27 @@ class PNAConvFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, BE, pack: GraphPack, cfg, *params):
-        T, F, pre_layers, post_layers, avg_deg_log, prep = cfg[:6]
-        ctx.bond_acc, ctx.layer_index = (cfg[6], cfg[7]) if len(cfg) > 6 else (None, 0)
+        T, F, pre_layers, post_layers, avg_deg_log, prep, ctx.bond_acc, ctx.layer_index = PnaCfg(*cfg)
         x = x.contiguous()
-        N, H = x.shape
-        E, R = pack.E, BE.size(0)
-        enc_w, enc_b, lin_w, lin_b = params[:4]
-        per = 2 * (pre_layers + post_layers)
-        pre = [[(params[4 + t * per + 2 * i], params[4 + t * per + 2 * i + 1]) for i in range(pre_layers)]
-               for t in range(T)]
-        post = [[(params[4 + t * per + 2 * (pre_layers + i)], params[4 + t * per + 2 * (pre_layers + i) + 1])
-                 for i in range(post_layers)] for t in range(T)]
-        sl = _tower_slices(T, F)
+        (N, H), E = x.shape, pack.E
         # degree classes: amp/att depend on the in-degree only, so with rows grouped by degree class the 12F-wide scaled
         # operand of post-layer 0 collapses to A @ Weff(d)^T; hub-heavy batches (> 64 classes) keep 4 segments
         dc = pack.degree_classes(pack.max_degree_hint) if _USE_DEGREE_CLASSES else None
         # everything that depends on the WEIGHTS only (60-row bond-table chain, Weff(d), lin o last post layer): taken
-        # from ``prep`` when the caller evaluated it ahead of time on the side stream (pna_weight_only_async)
-        if prep is None:
-            prep = _pna_weight_only(BE, T, F, pre_layers, post_layers, avg_deg_log, params, dc.D if dc is not None else 0)
-        EE, Te, weffs, Wm, bm = prep[:5]
+        # from ``prep`` when the caller evaluated it ahead of time on the side stream (WeightOnlyAhead / WeightOnlyAll)
+        dims = PnaDims(T, F, pre_layers, post_layers, BE.size(0), dc.D if dc is not None else 0,
+                       post_layers > 1 if prep is None else prep[3] is not None)
+        prep = _pna_weight_only(BE, dims, avg_deg_log, params) if prep is None else PnaPrep(*prep)
+        # what the backward reads back, the same from either path (``images`` / ``parr``: of the native forward only)
+        ctx.pack, ctx.dims, ctx.avg_deg_log, ctx.dc, ctx.weffs, ctx.Wm = pack, dims, avg_deg_log, dc, prep.weffs, prep.Wm
+        ctx.sinks, ctx.images, ctx.parr = grad_sinks(params), None, None
         if _NATIVE_LAYER_BWD and dc is not None and x.is_cuda and pre_layers <= 8 and post_layers <= 8 and T <= 8:
-            return _pna_forward_native(ctx, x, BE, pack, cfg, params, dc, prep)
+            return _pna_forward_native(ctx, x, BE, pack, dims, avg_deg_log, params, dc, prep)
+        EE, Te, weffs, Wm, bm = prep[:5]
+        lin_w, lin_b = params[2:4]
+        pre, post = ([[(params[k], params[k + 1]) for k in (dims.param_index(t, kind, i) for i in range(n))] for t in range(T)]
+                     for kind, n in (("pre", pre_layers), ("post", post_layers)))
+        sl = _tower_slices(T, F)
         P, Q = _empty(N, H, x), _empty(N, H, x)
         for t in range(T):
             W0 = pre[t][0][0]
@@ -731,26 +596,18 @@ class PNAConvFn(torch.autograd.Function):
             out = ops.gemm([(z, None, Wm)], _empty(N, H, x), bias=bm)
         else:
             out = ops.gemm([(z, None, lin_w)], _empty(N, H, x), bias=lin_b)
-        ctx.pack, ctx.cfg = pack, cfg[:5]
-        ctx.n_h, ctx.n_z = len(hs), len(zs)
-        ctx.sinks = grad_sinks(params)
-        ctx.dc, ctx.weffs, ctx.Wm = dc, weffs, Wm
         ctx.save_for_backward(x, BE, EE, A, amp, att, *hs, *zs, *params)
         return out
 
     @staticmethod
     def backward(ctx, dout):
-        T, F, pre_layers, post_layers, _ = ctx.cfg
-        pack: GraphPack = ctx.pack
-        saved = ctx.saved_tensors
+        dims, pack, saved = ctx.dims, ctx.pack, ctx.saved_tensors
+        T, F, pre_layers, post_layers = dims[:4]
         x, BE, EE, A, amp, att = saved[:6]
-        hs = list(saved[6:6 + ctx.n_h])
-        zs = list(saved[6 + ctx.n_h:6 + ctx.n_h + ctx.n_z])
-        params = saved[6 + ctx.n_h + ctx.n_z:]
-        N, H = x.shape
-        E, R = pack.E, BE.size(0)
+        n_h, n_z = pre_layers, post_layers - dims.merged  # the merged last post layer keeps no activation
+        hs, zs, params = list(saved[6:6 + n_h]), list(saved[6 + n_h:6 + n_h + n_z]), saved[6 + n_h + n_z:]
+        (N, H), E, R = x.shape, pack.E, BE.size(0)
         enc_w, enc_b, lin_w, lin_b = params[:4]
-        per = 2 * (pre_layers + post_layers)
         sinks = ctx.sinks
         if _NATIVE_LAYER_BWD and ctx.bond_acc is not None and ctx.dc is not None and x.is_cuda and \
                 all(sk is not None for sk in sinks) and pre_layers <= 8 and post_layers <= 8 and T <= 8:
@@ -759,10 +616,7 @@ class PNAConvFn(torch.autograd.Function):
                 return _pna_backward_native(ctx, dout, x, BE, EE, A, hs, zs, params, sinks, code_pos)
         grads = [sk if sk is not None else _zeros_like(p) for p, sk in zip(params, sinks)]
         d_enc_w, d_enc_b, d_lin_w, d_lin_b = grads[:4]
-
-        def pidx(t, kind, i):  # index of (w) in params/grads
-            return 4 + t * per + 2 * (i if kind == "pre" else pre_layers + i)
-
+        pidx = dims.param_index  # index of (w) in params/grads
         sl = _tower_slices(T, F)
         dout = dout.contiguous()
         merged = None
@@ -797,7 +651,7 @@ class PNAConvFn(torch.autograd.Function):
             At = A[:, t * 4 * F:(t + 1) * 4 * F]
             ops.queue_wgrad(gt, _cols(x, sl[t]), dWp[:, 0:F], dbias=grads[k + 1])
             if ctx.dc is not None:
-                ops.pna_post0_wgrad_classes(gt, At, ctx.dc, F, ctx.cfg[4], dWp)
+                ops.pna_post0_wgrad_classes(gt, At, ctx.dc, F, ctx.avg_deg_log, dWp)
                 ops.gemm_grouped([(gt, None, ctx.weffs[t][0], 4 * F * F)], dA[:, t * 4 * F:(t + 1) * 4 * F], ctx.dc,
                                  b_trans=False)
             else:
@@ -832,7 +686,6 @@ class PNAConvFn(torch.autograd.Function):
         code_pos = ops.bond_code_index(pack, R, H)   # (may build the inverted index: on the main stream, before the fork)
         acc = ctx.bond_acc
         dBE_box = []
-        keep = [ge, EE, BE] + ([acc.buf] if acc is not None else [])  # + the chain's temporaries (appended below)
 
         def bond_chain():
             dTe = ops.bond_table_grad(ge, pack, R, code_pos)
@@ -844,20 +697,15 @@ class PNAConvFn(torch.autograd.Function):
             ops.gemm_wgrad_inline(dEE, BE, d_enc_w, dbias=d_enc_b)
             if acc is None:
                 dBE_box.append(ops.gemm([(dEE, None, enc_w)], _empty(R, H, x), b_trans=False))
-            else:  # the layers of one model share one accumulator; the layer whose backward runs first clears it
-                if acc.first_in_backward(ctx.layer_index):
-                    ops.zero_(acc.buf)
-                ops.gemm([(dEE, None, enc_w)], acc.buf, b_trans=False, accumulate=True)
-            keep.extend((dTe, dEE))
+            else:
+                acc.add(ctx.layer_index, dEE, enc_w)
+            return dTe, dEE
 
         if acc is None:
             bond_chain()  # stand-alone use of the layer: the caller gets dBE back at once, so no side stream
             dBE = dBE_box[0]
         else:
-            ops.run_on_second_side_stream(ge, keep, bond_chain)
-            dBE = None
-            if ctx.layer_index == 0:  # the last conv backward of the pass hands the accumulated gradient to autograd
-                dBE = acc.handoff(x.device)
+            dBE = acc.run_chain(ctx.layer_index, ge, [ge, EE, BE], bond_chain)
         ops.flush_wgrads()  # the layer's weight gradients in batched launches on the weight-gradient stream
         if merged is not None:
             dWm, dbm = merged
@@ -896,14 +744,10 @@ class GINEConvFn(torch.autograd.Function):
         pack: GraphPack = ctx.pack
         dout = dout.contiguous()
         N, H = x.shape
-        dev = dict(dtype=torch.float32, device=x.device)
         sk = ctx.sinks
-        dlw = sk[0] if sk[0] is not None else _zeros_like(lin_w)
-        dlb = sk[1] if sk[1] is not None else ops.zeros(lin_w.size(0), device=x.device)
-        dw0 = sk[2] if sk[2] is not None else _zeros_like(w0)
-        db0 = sk[3] if sk[3] is not None else ops.zeros(w0.size(0), device=x.device)
-        dw2 = sk[4] if sk[4] is not None else _zeros_like(w2)
-        db2 = sk[5] if sk[5] is not None else ops.zeros(w2.size(0), device=x.device)
+        shapes = [w.shape[:n] for w in (lin_w, w0, w2) for n in (2, 1)]  # each weight, then its bias
+        dlw, dlb, dw0, db0, dw2, db2 = grads = [g_ if g_ is not None else ops.zeros(*s, device=x.device)
+                                                for g_, s in zip(sk, shapes)]
         ops.gemm_wgrad(dout, a1, dw2, dbias=db2)
         g1 = ops.gemm([(dout, None, w2)], _empty(N, a1.size(1), x), b_trans=False, mask=a1)
         ops.gemm_wgrad(g1, agg, dw0, dbias=db0)
@@ -918,23 +762,16 @@ class GINEConvFn(torch.autograd.Function):
             # rows: 0.45 ms per layer at cfg-3) and what hangs off it run on side stream 1 into the shared accumulator
             dx, _ = ops.gine_aggregate_bwd(dagg, x, Le, pack, ctx.eps, want_dle=False)
             code_pos = pack.code_index(Le.size(0)) if pack.E > 0 else None  # built (once per batch) on the main stream
-            keep = [dagg, x, Le, BE, acc.buf]
 
             def bond_chain():
                 dLe_ = ops.gine_dle(dagg, x, Le, pack, code_pos)
                 ops.gemm_wgrad_inline(dLe_, BE, dlw, dbias=dlb)
-                if acc.first_in_backward(ctx.layer_index):
-                    ops.zero_(acc.buf)
-                ops.gemm([(dLe_, None, lin_w)], acc.buf, b_trans=False, accumulate=True)
-                keep.append(dLe_)
+                acc.add(ctx.layer_index, dLe_, lin_w)
+                return (dLe_,)
 
-            ops.run_on_second_side_stream(dagg, keep, bond_chain)
-            dBE = None
-            if ctx.layer_index == 0:
-                dBE = acc.handoff(x.device)
+            dBE = acc.run_chain(ctx.layer_index, dagg, [dagg, x, Le, BE], bond_chain)
         ops.finish_backward(x.device, all(k is not None for k in sk), sk)
-        outs = [None if k is not None else g_ for g_, k in zip((dlw, dlb, dw0, db0, dw2, db2), sk)]
-        return (dx, dBE, None, None, *outs, None, None)
+        return (dx, dBE, None, None, *[None if k is not None else g_ for g_, k in zip(grads, sk)], None, None)
 
 
 def _stacked(tensors: Sequence[torch.Tensor]) -> torch.Tensor:
@@ -998,20 +835,13 @@ class TransformerConvFn(torch.autograd.Function):
             # the bond-table gradient (a by-code segment sum over the edges) and what hangs off it run on side stream 1
             # into the shared accumulator, as for GINEConvFn
             code_pos = pack.code_index(Le.size(0)) if pack.E > 0 else None  # built (once per batch) on the main stream
-            keep = [dout, qkvs, scratch, Le, BE, we, grads[6], acc.buf]
 
             def bond_chain():
                 dLe_ = ops.transformer_attn_dle(dout, qkvs, scratch, Le, pack, heads, code_pos)
                 ops.gemm_wgrad_inline(dLe_, BE, grads[6])
-                if acc.first_in_backward(ctx.layer_index):
-                    ops.zero_(acc.buf)
-                ops.gemm([(dLe_, None, we)], acc.buf, b_trans=False, accumulate=True)
-                keep.append(dLe_)
+                acc.add(ctx.layer_index, dLe_, we)
+                return (dLe_,)
 
-            ops.run_on_second_side_stream(dout, keep, bond_chain)
-            dBE = None
-            if ctx.layer_index == 0:
-                dBE = acc.handoff(x.device)
+            dBE = acc.run_chain(ctx.layer_index, dout, [dout, qkvs, scratch, Le, BE, we, grads[6]], bond_chain)
         ops.finish_backward(x.device, all(k is not None for k in sk), sk)
-        outs = [None if k is not None else g_ for g_, k in zip(grads, sk)]
-        return (dx, dBE, None, None, *outs)
+        return (dx, dBE, None, None, *[None if k is not None else g_ for g_, k in zip(grads, sk)])

@@ -237,8 +237,8 @@ class PNAConv(Module):
         """x fp32[N,H]; edge_index: GraphPack of the batch; edge_attr: fp32[60,H] encoded bond table.  ``bond_acc``
         (optional, ``Fn.BondGradAccumulator`` shared by the ``depth`` layers of a model, this one being number
         ``layer_index``): the bond-table gradient is accumulated there off the critical path."""
-        cfg = (self.towers, self.F_in, self.pre_layers, self.post_layers, self.aggr_module.avg_log(), prepared,
-               bond_acc, layer_index)
+        cfg = Fn.PnaCfg(self.towers, self.F_in, self.pre_layers, self.post_layers, self.aggr_module.avg_log(), prepared,
+                        bond_acc, layer_index)
         return Fn.PNAConvFn.apply(x, edge_attr, edge_index, cfg, *self._params())
 
 

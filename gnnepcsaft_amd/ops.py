@@ -809,14 +809,6 @@ def keep_until_join(device: torch.device, tensors, whichs=(0, 1)) -> None:
     _SIDE_USED.setdefault(idx, set()).update(whichs)
 
 
-def pna_conv_bwd(args: "_lib.PnaBwdArgs", device: torch.device, images: "Optional[_lib.PnaLayerImages]" = None) -> None:
-    """``images``: the layer's split weight images from gnx_pna_split_all (None: the layer splits in place)."""
-    if images is None:
-        check(_lib.load().gnx_pna_conv_bwd(handle(device), C.byref(args)))
-    else:
-        check(_lib.load().gnx_pna_conv_bwd_images(handle(device), C.byref(args), C.byref(images)))
-
-
 def split_launch_counts(device: torch.device) -> Tuple[int, int]:
     """(per-call, batched) split launches the library has issued on ``device`` so far: k_split_weights in front of one
     product, k_split_weights_batched of gnx_pna_split_all (host counters; tests take differences)."""
