@@ -226,6 +226,10 @@ SIGNATURES = {
                                      _vp]),
     "gnx_pcsaft_mix_dew": (_i32, [_vp, _vp, _i64, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp,
                                   _vp]),
+    "gnx_pcsaft_mix_bubble_t": (_i32, [_vp, _vp, _i64, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp,
+                                       _vp, _vp]),
+    "gnx_pcsaft_mix_dew_t": (_i32, [_vp, _vp, _i64, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp,
+                                    _vp, _vp]),
     "gnx_pcsaft_mix_flash": (_i32, [_vp, _vp, _i64, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp,
                                     _vp, _vp]),
     "gnx_pcsaft_mix_stability": (_i32, [_vp, _vp, _i64, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp,

@@ -36,21 +36,7 @@ constexpr int kDewAccelAfter = 3;
 constexpr double kDewAccelGate = 1e-2;
 constexpr double kDewAccelMax = 0.95;
 
-// f = rho exp(mu^res/kT) [1/angstrom^3] of the component in slot s of m alone at its liquid root at zero pressure; 0.0
-// where it has none (the acceptance test of the bubble start: a root below the lowest step of the density scan is the
-// dilute gas).  c is scratch.  One component: mu^res/kT = a + Z - 1.
-__device__ double dew_raoult(const MixRef& m, int s, double T, Mix& c) {
-  const double one = 1.0;
-  if (!c.init(MixRef{m.params, m.B, m.comp + s, nullptr, nullptr, 1}, &one, T)) return 0.0;
-  double el;
-  if (density_root(c, 0.0, el) != ST_OK || !(el >= kEtaMax / kScanDensity)) return 0.0;
-  const double rn = number_density(molar_density(el, c.c3));
-  const Mix::Eval e = c.eval_rho(rn);
-  const double f = rn * ::exp(e.a + e.z - 1.0);
-  return e.ok && isfinite(f) && f > 0.0 ? f : 0.0;
-}
-
-// dew point of point i at (T, y)
+// dew point of point i at (T, y); dew_raoult, the start, is in gnx_pcsaft_mix_vle.hpp
 struct MixDewPoint {
   const double *T, *y;
   double *P, *x, *rho_l, *rho_v;

@@ -82,4 +82,19 @@ __device__ bool mix_lnf_at(const MixRef& m, const double* xin, double T, double 
   return fin;
 }
 
+// f = rho exp(mu^res/kT) [1/angstrom^3] of the component in slot s of m alone at its liquid root at zero pressure; 0.0
+// where it has none (the acceptance test of the bubble start: a root below the lowest step of the density scan is the
+// dilute gas).  c is scratch.  One component: mu^res/kT = a + Z - 1.  The Raoult's-law start of the dew kernels
+// (gnx_pcsaft_mix_dew.hip at given T, gnx_pcsaft_mix_tvle.hip at given P).
+__device__ double dew_raoult(const MixRef& m, int s, double T, Mix& c) {
+  const double one = 1.0;
+  if (!c.init(MixRef{m.params, m.B, m.comp + s, nullptr, nullptr, 1}, &one, T)) return 0.0;
+  double el;
+  if (density_root(c, 0.0, el) != ST_OK || !(el >= kEtaMax / kScanDensity)) return 0.0;
+  const double rn = number_density(molar_density(el, c.c3));
+  const Mix::Eval e = c.eval_rho(rn);
+  const double f = rn * ::exp(e.a + e.z - 1.0);
+  return e.ok && isfinite(f) && f > 0.0 ? f : 0.0;
+}
+
 }  // namespace

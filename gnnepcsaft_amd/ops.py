@@ -1162,15 +1162,21 @@ _PCSAFT_MIX = {"pcsaft_mix_state": ("gnx_pcsaft_mix_state", (0, 0, 0)),
                "pcsaft_mix_lnphi": ("gnx_pcsaft_mix_lnphi", (0, 1, 1)),
                "pcsaft_mix_bubble": ("gnx_pcsaft_mix_bubble", (0, 1, 0, 0)),
                "pcsaft_mix_dew": ("gnx_pcsaft_mix_dew", (0, 1, 0, 0)),
+               "pcsaft_mix_bubble_t": ("gnx_pcsaft_mix_bubble_t", (0, 1, 0, 0)),
+               "pcsaft_mix_dew_t": ("gnx_pcsaft_mix_dew_t", (0, 1, 0, 0)),
                "pcsaft_mix_flash": ("gnx_pcsaft_mix_flash", (0, 1, 1, 0, 0)),
                "pcsaft_mix_stability": ("gnx_pcsaft_mix_stability", (0, 1, 0, 0))}
 
 
-def _pcsaft_mix(params, comp, kij, eab, owner, T, second, x, name, out=None, last=True, trial=None):
+_NO_START = object()  # an entry without a start column (None there is the NULL of one that has it)
+
+
+def _pcsaft_mix(params, comp, kij, eab, owner, T, second, x, name, out=None, last=True, trial=None, start=_NO_START):
     """The mixture form ``name`` of ``_PCSAFT_MIX``: validate, take ``out`` or make the outputs, call.  ``second`` is the
     state beside T (rho or P), None for the bubble point, which has none.  ``last`` False leaves the last fp64 output
     (lnphi_pure) out: None in the result, NULL for the entry.  ``trial``: the int64 column that the stability entry
-    takes beside ``owner``, and it alone."""
+    takes beside ``owner``, and it alone.  ``start``: the fp64 column of start values that the bubble- and dew-temperature
+    entries take after ``x`` (there ``T`` holds the pressures), None for NULL."""
     entry, widths = _PCSAFT_MIX[name]
     params, owner, T = _pcsaft_args(params, owner, T, name)
     dev = params.device
@@ -1197,13 +1203,22 @@ def _pcsaft_mix(params, comp, kij, eab, owner, T, second, x, name, out=None, las
     if any(t.shape != T.shape for t in state) or tuple(x.shape) != (n, nc):
         raise _lib.GnxError(_lib.GNX_E_INVALID, f"{name}: T {tuple(T.shape)}, state {[tuple(t.shape) for t in state]} "
                                                 f"and x {tuple(x.shape)} do not describe n points of {nc} components")
+    after = []
+    if start is not _NO_START:
+        if start is not None:
+            start = _f64_on(start, f"{name}: start", dev)
+            if start.shape != T.shape:
+                raise _lib.GnxError(_lib.GNX_E_INVALID, f"{name}: start {tuple(start.shape)} and the state "
+                                                        f"{tuple(T.shape)} differ")
+        after.append(_ptr(start))
     specs = [((n, nc) if w else (n,), _F64) for w in widths] + [((n,), _ST)]
     if not last:
         specs[-2] = None
     out = _pcsaft_outs(out, specs, dev, name)
     check(getattr(_lib.load(), entry)(handle(dev), params.data_ptr(), params.size(0), comp.data_ptr(), _ptr(mats[0]),
                                       _ptr(mats[1]), M, nc, owner.data_ptr(), *(t.data_ptr() for t in rows),
-                                      T.data_ptr(), *(t.data_ptr() for t in state), x.data_ptr(), n, *map(_ptr, out)))
+                                      T.data_ptr(), *(t.data_ptr() for t in state), x.data_ptr(), *after, n,
+                                      *map(_ptr, out)))
     return out
 
 
@@ -1272,6 +1287,40 @@ def pcsaft_mix_dew(params: torch.Tensor, comp: torch.Tensor, kij: Optional[torch
     y = 0 is dropped (x = 0.0), a -1 slot has x = NaN; where status != 0, P and the densities are 0.0 and the x row is
     NaN."""
     return _pcsaft_mix_dew(params, comp, kij, eab, owner, T, y)
+
+
+def _pcsaft_mix_bubble_t(params, comp, kij, eab, owner, P, x, T0=None, out=None):
+    """``pcsaft_mix_bubble_t`` writing into ``out`` = (T, y, rho_l, rho_v, status) where given; rho_l and rho_v may be
+    None there."""
+    return _pcsaft_mix(params, comp, kij, eab, owner, P, None, x, "pcsaft_mix_bubble_t", out=out, start=T0)
+
+
+def pcsaft_mix_bubble_t(params: torch.Tensor, comp: torch.Tensor, kij: Optional[torch.Tensor],
+                        eab: Optional[torch.Tensor], owner: torch.Tensor, P: torch.Tensor, x: torch.Tensor,
+                        T0: Optional[torch.Tensor] = None
+                        ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Mixture PC-SAFT bubble temperature at (P, x) (gnx_pcsaft_mix_bubble_t): arguments as ``pcsaft_mix_bubble`` with
+    P [n] Pa in place of T, and T0 [n] K or None, the temperature each solve starts from (NaN: the kernel's own start)
+    -> (T [n] K, y [n, nc], rho_l [n], rho_v [n] mol/m^3, status [n] int32).  A used slot with x = 0 is dropped
+    (y = 0.0), a -1 slot has y = NaN; where status != 0, T and the densities are 0.0 and the y row is NaN."""
+    return _pcsaft_mix_bubble_t(params, comp, kij, eab, owner, P, x, T0)
+
+
+def _pcsaft_mix_dew_t(params, comp, kij, eab, owner, P, y, T0=None, out=None):
+    """``pcsaft_mix_dew_t`` writing into ``out`` = (T, x, rho_l, rho_v, status) where given; rho_l and rho_v may be None
+    there."""
+    return _pcsaft_mix(params, comp, kij, eab, owner, P, None, y, "pcsaft_mix_dew_t", out=out, start=T0)
+
+
+def pcsaft_mix_dew_t(params: torch.Tensor, comp: torch.Tensor, kij: Optional[torch.Tensor],
+                     eab: Optional[torch.Tensor], owner: torch.Tensor, P: torch.Tensor, y: torch.Tensor,
+                     T0: Optional[torch.Tensor] = None
+                     ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Mixture PC-SAFT dew temperature at (P, y) (gnx_pcsaft_mix_dew_t): arguments as ``pcsaft_mix_bubble_t`` with the
+    vapour y [n, nc] in place of x -> (T [n] K, x [n, nc], rho_l [n], rho_v [n] mol/m^3, status [n] int32).  A used slot
+    with y = 0 is dropped (x = 0.0), a -1 slot has x = NaN; where status != 0, T and the densities are 0.0 and the x row
+    is NaN."""
+    return _pcsaft_mix_dew_t(params, comp, kij, eab, owner, P, y, T0)
 
 
 def _pcsaft_mix_flash(params, comp, kij, eab, owner, T, P, z, out=None):

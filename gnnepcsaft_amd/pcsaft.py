@@ -33,6 +33,14 @@ Dew points of a mixture, the pressure at which the vapour y starts to condense a
 ``mix_vp``, the reference's ``mix_vp_feos`` itself: (bubble pressure, dew pressure) of one composition.  A vapour can have
 more than one dew point (retrograde condensation); the one reported is the one the Raoult's-law start leads to.
 
+Bubble and dew temperatures of a mixture at given pressure (csrc/gnx_pcsaft_mix_tvle.hip): ``mix_bubble_t`` and
+``mix_dew_t`` for one point (feos ``PhaseEquilibrium.bubble_point`` / ``dew_point`` at given pressure, with ``t_init`` for
+feos's ``tp_init``), ``mix_bubble_t_batch`` / ``mix_dew_t_batch`` for every point of every system in one launch,
+``mix_vle_txy`` for the isobaric T-x-y diagram of a binary (the reference's ``mix_vle_diagram_feos``),
+``mixture_bubble_temperature`` / ``mixture_dew_temperature`` on device tensors.  Near a critical point of the mixture the
+kernel's own start does not reach the pressure and the point reports ``STATUS_NO_CONVERGENCE``; a start temperature
+from the caller can still get there.
+
 Isothermal two-phase flashes, the split of a feed z at (T, P) into a liquid x and a vapour y with the vapour mole fraction
 beta (csrc/gnx_pcsaft_mix_flash.hip): ``mix_tp_flash`` for one point (the reference's ``mix_tp_flash_feos``),
 ``mix_tp_flash_batch`` for every point of every system in one launch, ``mix_flash_x1`` for the liquid composition of a
@@ -276,6 +284,30 @@ def mixture_dew_pressure(params: torch.Tensor, comp: torch.Tensor, y: torch.Tens
     return ops.pcsaft_mix_dew(params, comp, kij, eab, _owner(owner, T), T, y)
 
 
+def mixture_bubble_temperature(params: torch.Tensor, comp: torch.Tensor, x: torch.Tensor, P: torch.Tensor,
+                               owner: Optional[torch.Tensor] = None, kij: Optional[torch.Tensor] = None,
+                               eab: Optional[torch.Tensor] = None, T0: Optional[torch.Tensor] = None
+                               ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Tensor form on device tensors, arguments as ``mixture_bubble_pressure`` with P [n] Pa in place of T -> (T [n] K,
+    y [n, nc], rho_l [n], rho_v [n] mol/m³, status [n] int32): the temperature at which the liquid x starts to boil at P.
+    T0 [n] or None: the temperature each solve starts from, NaN for the kernel's own start.  A used slot with x = 0 is
+    dropped (y = 0.0), a -1 slot has y = NaN; where status != 0 (1: no bubble temperature found, 3: bad input, a
+    P <= 0 or a T0 <= 0 included), T and the densities are 0.0 and the y row is NaN.  Asynchronous, on the current
+    stream."""
+    return ops.pcsaft_mix_bubble_t(params, comp, kij, eab, _owner(owner, P), P, x, T0)
+
+
+def mixture_dew_temperature(params: torch.Tensor, comp: torch.Tensor, y: torch.Tensor, P: torch.Tensor,
+                            owner: Optional[torch.Tensor] = None, kij: Optional[torch.Tensor] = None,
+                            eab: Optional[torch.Tensor] = None, T0: Optional[torch.Tensor] = None
+                            ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Tensor form on device tensors, arguments as ``mixture_bubble_temperature`` with the vapour y [n, nc] in place of
+    x -> (T [n] K, x [n, nc], rho_l [n], rho_v [n] mol/m³, status [n] int32): the temperature at which the vapour y
+    starts to condense at P.  A used slot with y = 0 is dropped (x = 0.0), a -1 slot has x = NaN; where status != 0, T
+    and the densities are 0.0 and the x row is NaN.  Asynchronous, on the current stream."""
+    return ops.pcsaft_mix_dew_t(params, comp, kij, eab, _owner(owner, P), P, y, T0)
+
+
 def mixture_tp_flash(params: torch.Tensor, comp: torch.Tensor, z: torch.Tensor, T: torch.Tensor, P: torch.Tensor,
                      owner: Optional[torch.Tensor] = None, kij: Optional[torch.Tensor] = None,
                      eab: Optional[torch.Tensor] = None
@@ -327,15 +359,22 @@ def mixture_stability(params: torch.Tensor, comp: torch.Tensor, z: torch.Tensor,
 
 
 def _run_mix(kind: str, params: np.ndarray, comp: np.ndarray, kij: Optional[np.ndarray], eab: Optional[np.ndarray],
-             owner: np.ndarray, states: np.ndarray) -> Tuple[List[Optional[np.ndarray]], np.ndarray]:
+             owner: np.ndarray, states: np.ndarray, start: Optional[np.ndarray] = None
+             ) -> Tuple[List[Optional[np.ndarray]], np.ndarray]:
     """states [n, 2 + nc] -> (values, status [n] int32); values is [rho [n]] for kind "density", [rho, lnphi [n, nc],
     None] for "lnphi", [rho, lnphi, lnphi_pure [n, nc]] for "lnphi_pure" and [P [n], y [n, nc], rho_l [n], rho_v [n]]
     for "bubble", which does not read the P column, [P [n], x [n, nc], rho_l [n], rho_v [n]] for "dew", whose composition
     columns hold the vapour and which does not read it either, and [beta [n], x [n, nc], y [n, nc], rho_l [n], rho_v [n]]
     for "flash", whose composition columns hold the feed, as do those of "stability": [tpd [n], w [n, nc]] of the points,
     their nc + 2 trials each expanded here into rows of the launch and reduced by ``_reduce_trials`` after the
-    download."""
+    download.  "bubble_t" and "dew_t" are "bubble" and "dew" at given pressure: they read the P column and not the T
+    column, values is [T [n], y or x [n, nc], rho_l [n], rho_v [n]], and ``start`` [n] (theirs alone) holds the
+    temperatures the solves start from, NaN or no array at all for the kernel's own start."""
     n, nc = owner.shape[0], comp.shape[1]
+    if kind in ("bubble_t", "dew_t"):
+        entry = ops._pcsaft_mix_bubble_t if kind == "bubble_t" else ops._pcsaft_mix_dew_t
+        return _run(entry, [params, comp, kij, eab, owner, states[:, 1], states[:, 2:], start], n,
+                    [(n,), (n, nc), (n,), (n,)])
     if kind == "stability":
         nt = nc + 2
         rows = [np.repeat(a, nt, axis=0) for a in (owner, states[:, 0], states[:, 1], states[:, 2:])]
@@ -427,11 +466,14 @@ def mix_rho_batch(mixtures: List[List[List[Any]]], states_batch: List[Any], kij:
 
 
 def _mix_point(what: str, kind: str, parameters: Sequence[Sequence[float]], state: Sequence[float],
-               kij_matrix: Optional[Any], epsilon_ab: Optional[Any]) -> Tuple[List[Optional[np.ndarray]], np.ndarray]:
-    """(values of ``_run_mix``, the state row [1, 2 + nc]) of one point; RuntimeError on a status != 0"""
+               kij_matrix: Optional[Any], epsilon_ab: Optional[Any], start: Optional[float] = None
+               ) -> Tuple[List[Optional[np.ndarray]], np.ndarray]:
+    """(values of ``_run_mix``, the state row [1, 2 + nc]) of one point; RuntimeError on a status != 0.  ``start``: the
+    start temperature of the kinds that take one."""
     params, comp, kij, eab = _pool([parameters], [kij_matrix], [epsilon_ab])
     states = _states([list(state)], len(parameters), comp.shape[1])
-    values, status = _run_mix(kind, params, comp, kij, eab, np.zeros(1, dtype=np.int64), states)
+    first = None if start is None else np.asarray([start], dtype=np.float64)
+    values, status = _run_mix(kind, params, comp, kij, eab, np.zeros(1, dtype=np.int64), states, first)
     _require_ok(status, f"mixture {what}", state)
     return values, states
 
@@ -593,6 +635,71 @@ def mix_vle_pxy(parameters: Sequence[Sequence[float]], temperature: float, kij_m
     if not keep.any():
         raise ValueError("No VLE found at the given conditions.")
     return {"temperature": states[keep, 0].tolist(), "pressure": P[keep].tolist(),
+            "density liquid": rho_l[keep].tolist(), "density vapor": rho_v[keep].tolist(),
+            "x0": x0[keep].tolist(), "x1": (1.0 - x0)[keep].tolist(),
+            "y0": y[keep, 0].tolist(), "y1": y[keep, 1].tolist()}
+
+
+def mix_bubble_t(parameters: Sequence[Sequence[float]], state: Sequence[float], kij_matrix: Optional[Any] = None,
+                 epsilon_ab: Optional[Any] = None, t_init: Optional[float] = None) -> Tuple[float, np.ndarray]:
+    """Bubble temperature of the liquid ``state = [T, P (Pa), x1, x2, ...]`` (T is ignored) of the components
+    ``parameters``: (T (K), y [k]), feos ``PhaseEquilibrium.bubble_point`` at given pressure.  ``t_init``: the temperature
+    the solve starts from (feos ``tp_init``), None for the kernel's own start.  Raises ``RuntimeError`` where no bubble
+    temperature is found at this P or the solve does not converge."""
+    (T, y, _, _), _ = _mix_point("bubble temperature", "bubble_t", parameters, state, kij_matrix, epsilon_ab, t_init)
+    return float(T[0]), y[0, :len(parameters)].copy()
+
+
+def mix_dew_t(parameters: Sequence[Sequence[float]], state: Sequence[float], kij_matrix: Optional[Any] = None,
+              epsilon_ab: Optional[Any] = None, t_init: Optional[float] = None) -> Tuple[float, np.ndarray]:
+    """Dew temperature of the vapour ``state = [T, P (Pa), y1, y2, ...]`` (T is ignored): (T (K), x [k]), feos
+    ``PhaseEquilibrium.dew_point`` at given pressure; arguments and errors as ``mix_bubble_t``.  A vapour can have more
+    than one dew temperature: the one reported is the one the start leads to."""
+    (T, x, _, _), _ = _mix_point("dew temperature", "dew_t", parameters, state, kij_matrix, epsilon_ab, t_init)
+    return float(T[0]), x[0, :len(parameters)].copy()
+
+
+def _t_batch(kind: str, mixtures, states_batch, kij) -> List[np.ndarray]:
+    def pick(values):
+        return _failed_nan(np.concatenate([values[0][:, None], values[1]], axis=1), values[0])
+
+    parts = _mix_batch(kind, mixtures, states_batch, kij, pick)
+    return [v[:, :1 + len(mixtures[i])].copy() for i, v in parts]
+
+
+def mix_bubble_t_batch(mixtures: List[List[List[Any]]], states_batch: List[Any], kij: Optional[List[Any]] = None
+                       ) -> List[np.ndarray]:
+    """Bubble temperatures of every state of every non-empty table in one launch, arguments as ``mix_bubble_batch`` (the
+    T column is ignored, the P column read): one fp64 array [rows, 1 + nc_i] of rows ``[T (K), y1..y_nc]`` per non-empty
+    table, a row of NaN where a point failed."""
+    return _t_batch("bubble_t", mixtures, states_batch, kij)
+
+
+def mix_dew_t_batch(mixtures: List[List[List[Any]]], states_batch: List[Any], kij: Optional[List[Any]] = None
+                    ) -> List[np.ndarray]:
+    """Dew temperatures of every state of every non-empty table in one launch, arguments as ``mix_bubble_t_batch`` (the
+    composition columns hold the vapour): rows ``[T (K), x1..x_nc]``, a row of NaN where a point failed."""
+    return _t_batch("dew_t", mixtures, states_batch, kij)
+
+
+def mix_vle_txy(parameters: Sequence[Sequence[float]], pressure: float, kij_matrix: Optional[Any] = None,
+                epsilon_ab: Optional[Any] = None, points: int = 51) -> dict:
+    """T-x-y diagram of a binary at ``pressure`` (Pa) (reference ``mix_vle_diagram_feos``): the bubble temperatures at
+    x_first = linspace(0, 1, points) in one launch, as a dict of the keys of ``mix_vle_pxy``.  Points without a bubble
+    temperature (a pressure above the critical one at that composition) are dropped; ``ValueError`` if none is left, and
+    for anything but two components.  The dew curve is y(x) along these points."""
+    if len(parameters) != 2:
+        raise ValueError(f"a T-x-y diagram needs a binary mixture, got {len(parameters)} components")
+    if int(points) < 2:
+        raise ValueError(f"a T-x-y diagram needs at least 2 points, got {points}")
+    params, comp, kij, eab = _pool([parameters], [kij_matrix], [epsilon_ab])
+    x0 = np.linspace(0.0, 1.0, int(points))
+    states = _states(np.stack([np.zeros_like(x0), np.full_like(x0, float(pressure)), x0, 1.0 - x0], axis=1), 2, 2)
+    (T, y, rho_l, rho_v), status = _run_mix("bubble_t", params, comp, kij, eab, np.zeros(len(x0), dtype=np.int64), states)
+    keep = status == STATUS_OK
+    if not keep.any():
+        raise ValueError("No VLE found at the given conditions.")
+    return {"temperature": T[keep].tolist(), "pressure": states[keep, 1].tolist(),
             "density liquid": rho_l[keep].tolist(), "density vapor": rho_v[keep].tolist(),
             "x0": x0[keep].tolist(), "x1": (1.0 - x0)[keep].tolist(),
             "y0": y[keep, 0].tolist(), "y1": y[keep, 1].tolist()}

@@ -595,6 +595,29 @@ int32_t gnx_pcsaft_mix_dew(gnx_handle* h, const double* params, int64_t B, const
                            const double* mix_kij, const double* mix_eab, int64_t M, int32_t nc, const int64_t* owner,
                            const double* T, const double* y, int64_t n, double* P, double* x, double* rho_l,
                            double* rho_v, int32_t* status);
+/* Bubble and dew temperatures at given pressure (ref: pcsaft/pcsaft_feos.py mix_vle_diagram_feos; feos
+ * PhaseEquilibrium.bubble_point / dew_point at given pressure, PhaseDiagram.binary_vle): the two entries above with P
+ * given and T looked for.  At P[i] (Pa) and the liquid composition x[i, :] the temperature T[i] (K) at which a first
+ * bubble of vapour forms and that vapour's y[i, :] (gnx_pcsaft_mix_bubble_t); at P[i] and the vapour composition
+ * y[i, :] the temperature at which a first drop of liquid forms and that liquid's x[i, :] (gnx_pcsaft_mix_dew_t); the
+ * molar densities rho_l[i], rho_v[i] of both phases (either may be NULL).  T0 [n] or NULL: the temperature the solve
+ * starts from (feos tp_init); NULL or a NaN entry: the entry's own start, a secant in 1/T on the first pressure estimate
+ * of the pressure entry (ideal vapour over the liquid at zero pressure; Raoult's law).  Then successive substitution on
+ * the unknown composition with one secant step in 1/T per step; the equations of the pressure entries hold to 1e-10
+ * at the numbers returned.  A dew temperature need not be unique: the one reported is the one the start leads to.  A
+ * used slot with zero given fraction is dropped (0.0 in the output row), a -1 slot has NaN.  A point with status != 0
+ * has T = 0.0, NaN in its whole composition row and densities 0.0.  status 1: no bubble or dew temperature found (no
+ * start: the pressure is above what the first estimate reaches, as close to a critical point; a root lost; no end
+ * within 400 steps; only the trivial solution); status 3: bad input (P not finite or <= 0, a T0 that is neither NaN nor
+ * positive and finite, an invalid mixture as in the other entries).  The launches have no kernel id (GNX_K_NONE). */
+int32_t gnx_pcsaft_mix_bubble_t(gnx_handle* h, const double* params, int64_t B, const int64_t* mix_comp,
+                                const double* mix_kij, const double* mix_eab, int64_t M, int32_t nc,
+                                const int64_t* owner, const double* P, const double* x, const double* T0, int64_t n,
+                                double* T, double* y, double* rho_l, double* rho_v, int32_t* status);
+int32_t gnx_pcsaft_mix_dew_t(gnx_handle* h, const double* params, int64_t B, const int64_t* mix_comp,
+                             const double* mix_kij, const double* mix_eab, int64_t M, int32_t nc, const int64_t* owner,
+                             const double* P, const double* y, const double* T0, int64_t n, double* T, double* x,
+                             double* rho_l, double* rho_v, int32_t* status);
 /* Isothermal two-phase flash (ref: pcsaft/pcsaft_feos.py mix_tp_flash_feos): at T[i], P[i] (Pa) the split of the feed
  * z[i, :] (normalised by its sum) into a liquid x[i, :] and a vapour y[i, :], the vapour mole fraction beta[i] in [0, 1]
  * and the molar densities rho_l[i], rho_v[i] of both phases (either may be NULL).  Equal mu_i^res/kT + ln(rho x_i) of

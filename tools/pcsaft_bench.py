@@ -24,7 +24,12 @@ With ``--stability`` it times the tangent-plane stability test of csrc/gnx_pcsaf
 ``pcsaft.mixture_stability`` (nc + 2 = 6 trial rows per point) on the 43 cases of tests/pcsaft_mix_stab_ref.py, repeated,
 the flash kernel on the 12 tie-line feeds among them in the same run, and that module's oracle on a sample.
 
-Usage: python tools/pcsaft_bench.py [--mixture | --bubble | --dew | --flash | --stability] [--reps 3] [--sizes 1000,100000,1000000] [--oracle-sample 20] [--out FILE.json]
+With ``--bubble-t`` / ``--dew-t`` it times the bubble- / dew-temperature kernel of csrc/gnx_pcsaft_mix_tvle.hip on the
+inverse problems of those 30 bubble points (the P and y the bubble kernel reports for them), repeated, from its own start
+and from T0 = 0.9 T, the bubble- / dew-pressure kernel on the same points in the same run for the ratio, and the oracle of
+tests/pcsaft_mix_tvle_ref.py on a sample.
+
+Usage: python tools/pcsaft_bench.py [--mixture | --bubble | --dew | --bubble-t | --dew-t | --flash | --stability] [--reps 3] [--sizes 1000,100000,1000000] [--oracle-sample 20] [--out FILE.json]
 """
 import argparse
 import json
@@ -160,6 +165,53 @@ def _dew(args, dev):
     return res
 
 
+def _tvle(args, dev):
+    """--bubble-t / --dew-t: the temperature kernels on the inverse problems of the 30 bubble points (P and y are what the
+    bubble-pressure kernel reports for them), beside the pressure kernel of the same kind on the same points"""
+    from tests import pcsaft_mix_tvle_ref as TR
+    from tests import pcsaft_mix_vle_ref as V
+    dew = args.dew_t
+    cases = list(V.NAMED) + V.fixture_cases()
+    params, comp, T, x = [], np.full((len(cases), 4), -1, dtype=np.int64), [], np.zeros((len(cases), 4))
+    for i, (_, rows, t, xi) in enumerate(cases):
+        comp[i, :len(rows)] = np.arange(len(params), len(params) + len(rows))
+        params.extend(np.asarray(rows, dtype=np.float64).tolist())
+        x[i, :len(rows)] = xi
+        T.append(t)
+    T = np.array(T)
+    d_params, d_comp = torch.from_numpy(np.array(params)).to(dev), torch.from_numpy(comp).to(dev)
+    every = torch.arange(len(cases), dtype=torch.int64, device=dev)
+    P, y, _, _, st = pcsaft.mixture_bubble_pressure(d_params, d_comp, torch.from_numpy(x).to(dev),
+                                                   torch.from_numpy(T).to(dev), every)
+    assert int((st != 0).sum().item()) == 0, "a bubble point failed: no pressure to start from"
+    P, y = P.cpu().numpy(), torch.nan_to_num(y).cpu().numpy()
+    z = y if dew else x
+    step = max(1, len(cases) // args.oracle_sample)
+    t0 = time.perf_counter()
+    sols = [TR.solve(rows, z[j, :len(rows)], P[j], dew=dew) for j, (_, rows, _, _) in list(enumerate(cases))[::step]]
+    oracle = (time.perf_counter() - t0) / len(sols)
+    name = "dew" if dew else "bubble"
+    solve = pcsaft.mixture_dew_temperature if dew else pcsaft.mixture_bubble_temperature
+    forward = pcsaft.mixture_dew_pressure if dew else pcsaft.mixture_bubble_pressure
+    res = []
+    for n in [int(s) for s in args.sizes.split(",")]:
+        idx = np.arange(n) % len(cases)
+        o, t, pp, zz = (torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+                        for a in (idx.astype(np.int64), T[idx], P[idx], z[idx]))
+        k = _kernel_ms(lambda: solve(d_params, d_comp, zz, pp, o))
+        st = solve(d_params, d_comp, zz, pp, o)[4]
+        kg = _kernel_ms(lambda: solve(d_params, d_comp, zz, pp, o, T0=0.9 * t))
+        stg = solve(d_params, d_comp, zz, pp, o, T0=0.9 * t)[4]
+        kf = _kernel_ms(lambda: forward(d_params, d_comp, zz, t, o))
+        rec = {"points": n, f"mix_{name}_t_kernel_ms": k, f"mix_{name}_t_points_per_s": n / k * 1e3,
+               "failed_points": int((st != 0).sum().item()), f"mix_{name}_t_from_0.9T_kernel_ms": kg,
+               "failed_points_from_0.9T": int((stg != 0).sum().item()), f"mix_{name}_pressure_same_points_kernel_ms": kf,
+               "temperature_over_pressure": k / kf, f"oracle_{name}_t_ms_est": oracle * n * 1e3}
+        print(json.dumps(rec), flush=True)
+        res.append(rec)
+    return res
+
+
 def _flash(args, dev):
     from tests import pcsaft_mix_flash_ref as F
     points = F.tie_line_points()
@@ -236,13 +288,15 @@ def main():
     ap.add_argument("--dew", action="store_true")
     ap.add_argument("--flash", action="store_true")
     ap.add_argument("--stability", action="store_true")
+    ap.add_argument("--bubble-t", action="store_true")
+    ap.add_argument("--dew-t", action="store_true")
     ap.add_argument("--reps", type=int, default=REPS, help="timed repetitions per kernel, the best of which counts")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     REPS = args.reps
-    if args.mixture or args.bubble or args.dew or args.flash or args.stability:
+    if args.mixture or args.bubble or args.dew or args.flash or args.stability or args.bubble_t or args.dew_t:
         dev = torch.device("cuda", torch.cuda.current_device())
-        res = (_stability if args.stability else _flash if args.flash else _dew if args.dew else _bubble if args.bubble else _mixture)(args, dev)
+        res = (_tvle if args.bubble_t or args.dew_t else _stability if args.stability else _flash if args.flash else _dew if args.dew else _bubble if args.bubble else _mixture)(args, dev)
         if args.out:
             with open(args.out, "w") as fh:
                 json.dump(dict(device=torch.cuda.get_device_name(dev), oracle_sample=args.oracle_sample, results=res), fh,
