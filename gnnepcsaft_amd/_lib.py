@@ -22,6 +22,9 @@ GEMM_RELU, GEMM_ACCUMULATE, GEMM_B_TRANS, GEMM_SPLIT_ONLY, GEMM_PRESPLIT = 1, 2,
 GEMM_KERNEL_NAMES = ("none", "k_gemm<vec>", "k_gemm<generic>", "k_gemm_ws", "k_gemm_ws3", "k_gemm_ws3<fast,8>",
                      "k_gemm_ws3<fast,4>", "k_gemm3", "k_gemm3p<96>", "k_gemm3p<128>", "k_gemm_as3", "k_gemm_mid",
                      "k_gemm_small_batched")
+# GNX_WGRAD_KERNEL_*, by value (gnx_gemm_wgrad_grouped_plan)
+WGRAD_KERNEL_NAMES = ("none", "k_gemm_wgrad<true,true>", "k_gemm_wgrad<false,true>", "k_gemm_wgrad3<true>",
+                      "k_gemm_wgrad3p_grouped")
 POOL_ADD, POOL_MEAN, POOL_MAX = 0, 1, 2
 K_NONE, K_PNA_AGG_FWD, K_PNA_AGG_BWD, K_GEMM_WS, K_GEMM_WGRAD, K_GINE_AGG_FWD, K_GINE_AGG_BWD, K_EDGE_COMBINE_FWD, \
     K_EDGE_COMBINE_BWD, K_BN_FWD, K_BN_BWD, K_GEMM_TILED, K_GEMM_SMALL, K_GEMM_WGRAD_BATCHED, K_KEY_SEGMENT_SUM, \
@@ -54,6 +57,11 @@ class GemmSeg(C.Structure):
 class GemmPlanInfo(C.Structure):
     _fields_ = [("kernel", C.c_int32), ("tile_rows", C.c_int32), ("grid_x", C.c_uint32), ("grid_y", C.c_uint32),
                 ("block", C.c_uint32), ("runs_split", C.c_int32), ("image_bytes", C.c_size_t)]
+
+
+class WgradGroupedPlanInfo(C.Structure):
+    _fields_ = [("kernel", C.c_int32), ("ranges", C.c_int32), ("chunks_per_range", C.c_int32), ("grid_x", C.c_uint32),
+                ("grid_y", C.c_uint32), ("grid_z", C.c_uint32), ("block", C.c_uint32)]
 
 
 class WgradProb(C.Structure):
@@ -186,6 +194,8 @@ SIGNATURES = {
                              _vp, _vp, _vp, _i64, _vp, _sz, _i32, C.POINTER(GemmPlanInfo)]),
     "gnx_gemm_wgrad_grouped": (_i32, [_vp, _vp, _i64, _vp, _i64, _i64, _i32, _i32, _vp, _i64, _i64, _vp, _vp, _vp,
                                       _i64]),
+    "gnx_gemm_wgrad_grouped_plan": (_i32, [_vp, _i64, _i64, _vp, _vp, _i64, _i32, _i32, _i64,
+                                           C.POINTER(WgradGroupedPlanInfo)]),
     "gnx_pna_weff": (_i32, [_vp, _vp, _i64, _i32, _i32, _f32, _vp]),
     "gnx_pna_weff_bwd": (_i32, [_vp, _vp, _i32, _i32, _f32, _vp, _i64]),
     "gnx_group_by_small_key": (_i32, [_vp, _vp, _i64, _i32, _vp, _vp, _vp, _sz]),

@@ -1,6 +1,9 @@
 // Weight gradients of the dense products (gnx_gemm.hip): the fp32-MFMA kernel, the split-operand kernels (two-barrier and
 // wave-specialised) and their batched forms, which run several same-shaped problems in one launch.
 #include "gnx_split.hpp"
+#include "gnx_wgrad_plan.hpp"
+
+static_assert(WGRAD_PLAN_BN == BN, "gnx_wgrad_plan.hpp: dW tile");
 
 // ---------------------------------------------------------------------------------------------------------------
 // Weight gradient  dW[n,k] += sum_m dC[m,n] * rs[m]*A[m,k]   (both operands k-row images: the contraction index m is the
@@ -382,8 +385,10 @@ __global__ void __launch_bounds__(256, 2) k_gemm_wgrad3(wgrad_args g) {
 //     being masked), split column by column and written as 16-byte LDS words into the [column][32 m] bf16 images of
 //     step j + 1 (two-stage ring, 120 KB); they also accumulate the bias gradient;
 //   * ONE barrier per step joins the two groups.
-// Rows gathered by degree class stay on wgrad3_body: the same structure with LDS-staged row offsets was built, correct, and
-// SLOWER there (145 vs 123 us per launch: the per-class chunks are 1024 rows = 32 steps, too short for its prologue).
+// Rows gathered by degree class: a first grouped form of this structure (one workgroup per 1024-row chunk, LDS-staged row
+// offsets) was built, correct, and SLOWER than wgrad3_body<true> (145 vs 123 us per launch: 1024 rows = 32 steps are too
+// short for its prologue).  k_gemm_wgrad3p_grouped below walks merged runs of consecutive chunks instead; its figures
+// are at its launch in wgrad_launch.
 // Measured (tools/wgrad_ab.py, a layer's eight 81 920 x 128 x 128 problems in one launch = 671 MB): 235 -> 205 us (3.4 -> 3.9
 // TB/s); K = 512: 111 -> 94 us.  Ablations of this kernel: the loads alone 124 us (the HBM floor), + the multiply waves
 // 132 us, + the staging waves' split and stores instead 138 us, both 195-205 us: the two groups slow each other down.
@@ -394,6 +399,66 @@ __global__ void __launch_bounds__(256, 2) k_gemm_wgrad3(wgrad_args g) {
 // ---------------------------------------------------------------------------------------------------------------
 #define WG3P_LDS (4 * G3_OP)
 #define WG3P_NST 4  // register stages of the staging waves (must be 4: the prologue and the unrolled loop assume it)
+
+// The three pieces of wgrad3p_body that k_gemm_wgrad3p_grouped below runs unchanged.  wgrad3p_body keeps its own inline
+// copy: routed through these functions the batched kernel comes out with a different schedule of its fragment waits
+// (38 more s_waitcnt), and that schedule has not been measured.
+// A staging thread's eight rows of one column: split and written as one 16-byte word per bf16 image
+__device__ __forceinline__ void wg3p_store_column(const float (&xa)[8], unsigned char* dst) {
+  bf16x8 p1, p2, p3;
+  split3(xa, p1, p2, p3);
+  *reinterpret_cast<bf16x8*>(dst) = p1;
+  *reinterpret_cast<bf16x8*>(dst + G3_PIECE) = p2;
+  *reinterpret_cast<bf16x8*>(dst + 2 * G3_PIECE) = p3;
+}
+
+// One 32-row step of a multiply wave (wave 0..3 owns the 64 x 64 quadrant (wave >> 1, wave & 1) of the 128 x 128 tile):
+// fragment reads + 48 MFMAs out of the LDS stage `stage` = [dC images | A images].
+__device__ __forceinline__ void wg3p_multiply_step(f32x16 (&acc)[2][2], const unsigned char* stage, const int wave,
+                                                   const int lane) {
+  const int wm = wave >> 1, wn = wave & 1;
+  const int li = lane & 31, lh = lane >> 5;
+  const unsigned char* const A3 = stage;
+  const unsigned char* const B3 = A3 + G3_OP;
+#pragma unroll
+  for (int sl = 0; sl < 2; ++sl) {
+    bf16x8 a[2][3], b[2][3];
+#pragma unroll
+    for (int mi = 0; mi < 2; ++mi)
+#pragma unroll
+      for (int p = 0; p < 3; ++p)
+        a[mi][p] = *reinterpret_cast<const bf16x8*>(A3 + p * G3_PIECE + (wm * 64 + mi * 32 + li) * G3_LDB + 32 * sl + 16 * lh);
+#pragma unroll
+    for (int ni = 0; ni < 2; ++ni)
+#pragma unroll
+      for (int p = 0; p < 3; ++p)
+        b[ni][p] = *reinterpret_cast<const bf16x8*>(B3 + p * G3_PIECE + (wn * 64 + ni * 32 + li) * G3_LDB + 32 * sl + 16 * lh);
+#pragma unroll
+    for (int mi = 0; mi < 2; ++mi)
+#pragma unroll
+      for (int ni = 0; ni < 2; ++ni) mfma_3x3(acc[mi][ni], a[mi], b[ni]);
+  }
+}
+
+// fp32 atomics of a multiply wave's quadrant into dW (rows n0.., columns c0..)
+__device__ __forceinline__ void wg3p_flush(const f32x16 (&acc)[2][2], const wgrad_args& g, float* dW, const int n0,
+                                           const int c0, const int wave, const int lane) {
+  const int wm = wave >> 1, wn = wave & 1;
+  const int li = lane & 31, lh = lane >> 5;
+#pragma unroll
+  for (int mi = 0; mi < 2; ++mi)
+#pragma unroll
+    for (int ni = 0; ni < 2; ++ni) {
+      int gc = c0 + wn * 64 + ni * 32 + li;
+      if (gc >= g.K) continue;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        int gr = n0 + wm * 64 + mi * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+        if (gr >= g.N) continue;
+        atomicAdd(dW + (int64_t)gr * g.lddw + gc, acc[mi][ni][r]);
+      }
+    }
+}
 
 __device__ __forceinline__ void wgrad3p_body(const wgrad_args& g, const int bx, const int by, const int bz,
                                              unsigned char* lds) {
@@ -541,6 +606,163 @@ __global__ void __launch_bounds__(512, 1) k_gemm_wgrad3p(wgrad_args g) {
   wgrad3p_body(g, blockIdx.x, blockIdx.y, blockIdx.z, lds_w);
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// Per-degree-class form of the wave-specialised kernel (no row scale, no bias gradient; 16-byte aligned operands, N and K
+// multiples of 4, M * ld < 2^32).  Workgroup (w, by, bz) owns the chunks [w S, min((w + 1) S, nchunks)) of the chunk table
+// (S = chunks_per_range, fixed on the host from max_chunks; nchunks is read here, on the device).  Chunks of one class
+// are consecutive ranges of row_index, so consecutive owned chunks of the same class whose positions touch form ONE run
+// [p0, p0 + len): per run the accumulators are zeroed, wgrad3p_body's prologue and pipelined loop run over
+// ceil(len / 32) steps, and the tile is flushed once into dW + class * dw_cls_stride.
+//
+// Barriers: both wave roles derive the run list from the same scalars (readfirstlane of the chunk table), and per run
+// both pass 2 + nsteps barriers: A (the ring below is filled), B (the staging prologue: step 0 is in LDS stage 0), one
+// per step.  The barrier that ends a run's last step orders every fragment read of that run before the next run's
+// prologue stores into LDS stage 0 and before its ring fill.
+//
+// Row gather: the staging waves read row row_index[p0 + i] for position i of the run.  Vector-memory loads return in
+// order, so a staging wave that waited for an index load would also wait for the four steps of row loads in front of
+// it.  The row numbers therefore reach the staging waves through LDS (its own counter): a ring of WG3G_RING = 16 steps x
+// 32 row numbers.  The staging waves fill steps 0..15 at the start of a run (barrier A); after that the MULTIPLY waves,
+// which have no other load in flight, fetch eight steps at a time: step 8m + 3 loads the row numbers of steps
+// 8m + 16 .. 8m + 23 (thread = position), step 8m + 4 stores them over steps 8m .. 8m + 7, last read (by the loads of step
+// i + 5 in step i) in step 8m + 2 and next needed in step 8m + 11.  Positions at or past the end of the run read the
+// zero line, as rows past r_end do in wgrad3p_body; the ring entry of such a position is a valid row that nobody loads.
+// ---------------------------------------------------------------------------------------------------------------
+#define WG3G_RING 16
+#define WG3G_LDS (WG3P_LDS + WG3G_RING * BK * 4)
+
+struct wgrad_grouped_args {
+  wgrad_args g;
+  int chunks_per_range;  // S: blockIdx.x = range of this many consecutive chunks
+  int max_chunks;        // ... of a table of this many chunks (nchunks[0] is clamped to it)
+};
+
+__global__ void __launch_bounds__(512, 1) k_gemm_wgrad3p_grouped(wgrad_grouped_args ga) {
+  const wgrad_args& g = ga.g;
+  extern __shared__ __attribute__((aligned(16))) unsigned char lds_wg[];
+  unsigned char* const lds = lds_wg;
+  unsigned* const ring = reinterpret_cast<unsigned*>(lds_wg + WG3P_LDS);
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wave = tid >> 6;
+  const int n0 = blockIdx.y * BN;  // dW row tile (output features)
+  const int c0 = blockIdx.z * BN;  // dW col tile (input features)
+  if (n0 >= g.N || c0 >= g.K) return;
+  const int c_begin = (int)blockIdx.x * ga.chunks_per_range;
+  int nch = __builtin_amdgcn_readfirstlane(g.nchunks[0]);
+  nch = nch < ga.max_chunks ? nch : ga.max_chunks;
+  const int c_end = c_begin + ga.chunks_per_range < nch ? c_begin + ga.chunks_per_range : nch;
+  auto info = [&](int i) { return __builtin_amdgcn_readfirstlane(g.chunk_info[i]); };
+  // the run that starts at chunk c: [p0, p0 + len) of row_index, class cls; c moves to the first chunk behind it
+  auto next_run = [&](int& c, int& p0, int& len, int& cls) {
+    p0 = info(3 * c);
+    len = info(3 * c + 1);
+    cls = info(3 * c + 2);
+    for (++c; c < c_end && info(3 * c + 2) == cls && info(3 * c) == p0 + len; ++c) len += info(3 * c + 1);
+  };
+  // row number of position i of the run (clamped: the row of a position past the run is never loaded)
+  auto row_at = [&](int p0, int len, int i) { return (unsigned)g.row_index[p0 + (i < len ? i : 0)]; };
+
+  if (wave < 4) {
+    // ================================================================ multiply waves
+    for (int c = c_begin; c < c_end;) {
+      int p0, len, cls;
+      next_run(c, p0, len, cls);
+      if (len <= 0) continue;
+      const int nsteps = (len + BK - 1) / BK;
+      f32x16 acc[2][2];
+#pragma unroll
+      for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+          for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+      __syncthreads();  // A
+      __syncthreads();  // B
+      unsigned pend = 0;
+      for (int j = 0; j < nsteps; ++j) {
+        if ((j & 7) == 3) pend = row_at(p0, len, (j + 13) * BK + tid);
+        wg3p_multiply_step(acc, lds + (j & 1) * 2 * G3_OP, wave, lane);
+        if ((j & 7) == 4) ring[((j + 12) & (WG3G_RING - 1)) * BK + tid] = pend;
+        __syncthreads();
+      }
+      wg3p_flush(acc, g, g.dW + (int64_t)cls * g.dw_cls_stride, n0, c0, wave, lane);
+    }
+    return;
+  }
+
+  // ================================================================== staging waves
+  const int lt = tid - 256;
+  const int role = lt >> 7;  // 0: dC (dW rows n0..), 1: A (dW columns c0..)
+  const int c4 = (lt & 31) * 4, rg = (lt >> 5) & 3;
+  const bool col_ok = role ? (c0 + c4 < g.K) : (n0 + c4 < g.N);  // N, K multiples of 4: the quad is valid as a whole
+  const float* const base = (role ? g.Y + (col_ok ? c0 + c4 : 0) : g.X + (col_ok ? n0 + c4 : 0));
+  const float* const zero = g.zero;
+  const unsigned ld = (unsigned)(role ? g.ldy : g.ldx);
+  const int img = role * G3_OP;
+  int len = 0;  // of the current run
+
+  f32x4 v[WG3P_NST][8];
+
+  auto load_step = [&](auto PC, int step) {
+    constexpr int P = decltype(PC)::value;
+    const int left = len - (step * BK + rg * 8);
+    const int nval = (left >= 8 && col_ok) ? 8 : ((left > 0 && col_ok) ? left : 0);
+    const unsigned* const rr = ring + (step & (WG3G_RING - 1)) * BK + rg * 8;
+    const split_u32x4 ra = *reinterpret_cast<const split_u32x4*>(rr);
+    const split_u32x4 rb = *reinterpret_cast<const split_u32x4*>(rr + 4);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const unsigned off = (j < 4 ? ra[j & 3] : rb[j & 3]) * ld;  // row * ld < 2^32 (host)
+      v[P][j] = *reinterpret_cast<const f32x4*>(j < nval ? base + off : zero);
+    }
+  };
+  auto store_step = [&](auto PC, unsigned char* stage) {
+    constexpr int P = decltype(PC)::value;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      float xa[8];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) xa[j] = v[P][j][q];
+      wg3p_store_column(xa, stage + img + (c4 + q) * G3_LDB + rg * 16);
+    }
+  };
+  // step j (K = j % NST): as in wgrad3p_body
+  auto iteration = [&](auto KC, int j) {
+    constexpr int K = decltype(KC)::value;
+    constexpr int P = (K + 1) % WG3P_NST;
+    store_step(std::integral_constant<int, P>{}, lds + ((K + 1) & 1) * 2 * G3_OP);
+    load_step(std::integral_constant<int, P>{}, j + 1 + WG3P_NST);
+    __syncthreads();
+  };
+
+  for (int c = c_begin; c < c_end;) {
+    int p0, cls;
+    next_run(c, p0, len, cls);
+    if (len <= 0) continue;
+    const int nsteps = (len + BK - 1) / BK;
+    ring[lt] = row_at(p0, len, lt);
+    ring[256 + lt] = row_at(p0, len, 256 + lt);
+    __syncthreads();  // A
+    load_step(std::integral_constant<int, 0>{}, 0);
+    load_step(std::integral_constant<int, 1>{}, 1);
+    load_step(std::integral_constant<int, 2>{}, 2);
+    load_step(std::integral_constant<int, 3>{}, 3);
+    store_step(std::integral_constant<int, 0>{}, lds);
+    load_step(std::integral_constant<int, 0>{}, 4);
+    __syncthreads();  // B
+    for (int j = 0; j < nsteps; j += 4) {
+      iteration(std::integral_constant<int, 0>{}, j);
+      if (j + 1 >= nsteps) break;
+      iteration(std::integral_constant<int, 1>{}, j + 1);
+      if (j + 2 >= nsteps) break;
+      iteration(std::integral_constant<int, 2>{}, j + 2);
+      if (j + 3 >= nsteps) break;
+      iteration(std::integral_constant<int, 3>{}, j + 3);
+    }
+  }
+}
+
 // Several independent weight gradients in ONE launch (a layer's same-shaped dW = g^T a products): blockIdx.x =
 // problem * chunks + chunk.  With P problems sharing the grid every workgroup owns a P x longer row range, so the
 // per-problem atomic flush shrinks P x at equal parallelism (a lone 128x128 dW over 82k rows flushes 33 MB of fp32
@@ -634,10 +856,8 @@ static wgrad_args wgrad_args_of(const gnx_handle* h, const gnx_wgrad_prob& q) {
   return g;
 }
 
-// the split-operand weight-gradient kernels take over for large row counts (GNX_GEMM_SPLIT=0: fp32 MFMA everywhere)
 static bool wgrad_split_enabled(const gnx_handle* h, int64_t M, bool any_rowscale) {
-  if (any_rowscale || M < 4096) return false;
-  return h->opt[GNX_OPT_GEMM_SPLIT] != 0;
+  return wgrad_plan_split_enabled(h->opt, M, any_rowscale);
 }
 
 static int32_t wgrad_launch(gnx_handle* h, const float* dC, int64_t lddc, const float* A, int64_t lda,
@@ -669,7 +889,24 @@ static int32_t wgrad_launch(gnx_handle* h, const float* dC, int64_t lddc, const 
   const double wfl = 2.0 * (double)M * N * K;
   gnx_prof_scope prof(h, GNX_K_GEMM_WGRAD, 4.0 * M * ((double)N + K) + 4.0 * N * K, wfl, wsplit ? 6.0 * wfl : 0.0);
   // (short row ranges -- the readout's 4096-row problems -- keep the two-barrier kernel: 14.7 vs 24 us)
-  if (wsplit && vec && !chunk_info && rows >= 512 && h->opt[GNX_OPT_WGRAD_PIPE] != 0) {
+  wgrad_grouped_plan p = {};
+  if (chunk_info) p = wgrad_grouped_plan_of(dC, lddc, A, lda, M, N, K, max_chunks, h->opt);
+  if (p.kernel == GNX_WGRAD_KERNEL_SPLIT3P_GROUPED) {
+    // Per-class gradient over merged class runs, at most WGRAD_GROUPED_WGS workgroups (ranges x output tiles).  Measured
+    // on one MI355X, builds alternating (profiles/wgrad_grouped_pipe_ab.json; cfg-2: 82 chunks in a table of 85, K = 512):
+    //   budget   grid      alone (tools/wgrad_ab.py | single-stream trace)   cfg-2 step   cfg-5 step
+    //   k_gemm_wgrad3<true>  85 x 4      107.9 | 122.4 us                       6.397 ms     55.97 ms
+    //       64   15 x 4, S = 6           241.6 us                               6.565        57.60
+    //      128   29 x 4, S = 3           127.3 | 136.5 us                       6.322        55.34
+    //      256   43 x 4, S = 2            93.8 | 104.6 us                       6.320        55.19
+    // A workgroup takes 1.3 - 1.5 us per 32-row step whatever the budget, so alone the launch is as fast as it has
+    // workgroups; at 128 it is slower alone than the kernel it replaces and the step is still faster, because it leaves
+    // the CUs to the main stream.  256 is the default: same cfg-2 step as 128, faster alone and at cfg-5.
+    grid.x = p.grid_x;
+    GNX_HIP(gnx_raise_lds_limit<&k_gemm_wgrad3p_grouped>((int)WG3G_LDS));
+    hipLaunchKernelGGL(k_gemm_wgrad3p_grouped, grid, dim3(512), WG3G_LDS, h->stream,
+                       wgrad_grouped_args{g, p.chunks_per_range, (int)max_chunks});
+  } else if (wsplit && vec && !chunk_info && rows >= 512 && h->opt[GNX_OPT_WGRAD_PIPE] != 0) {
     GNX_HIP(gnx_raise_lds_limit<&k_gemm_wgrad3p>((int)WG3P_LDS));
     hipLaunchKernelGGL(k_gemm_wgrad3p, grid, dim3(512), WG3P_LDS, h->stream, g);
   } else if (wsplit) {
@@ -705,6 +942,23 @@ extern "C" int32_t gnx_gemm_wgrad_grouped(gnx_handle* h, const float* dC, int64_
   GNX_CHECK_ARG(row_index && chunk_info && nchunks && max_chunks > 0, "gnx_gemm_wgrad_grouped: NULL argument");
   return wgrad_launch(h, dC, lddc, A, lda, nullptr, M, N, K, dW_cls, lddw, nullptr, row_index, chunk_info, nchunks,
                       max_chunks, dw_cls_stride);
+}
+
+extern "C" int32_t gnx_gemm_wgrad_grouped_plan(gnx_handle* h, int64_t lddc, int64_t lda, const float* dC, const float* A,
+                                               int64_t M, int32_t N, int32_t K, int64_t max_chunks,
+                                               gnx_wgrad_grouped_plan_info* out) {
+  GNX_CHECK_ARG(h && dC && A && out && max_chunks > 0, "gnx_gemm_wgrad_grouped_plan: NULL argument");
+  GNX_CHECK_ARG(M >= 0 && N > 0 && K > 0 && lddc >= N && lda >= K, "gnx_gemm_wgrad_grouped_plan: bad shape");
+  const wgrad_grouped_plan p = wgrad_grouped_plan_of(dC, lddc, A, lda, M, N, K, max_chunks, h->opt);
+  const bool pipe = p.kernel == GNX_WGRAD_KERNEL_SPLIT3P_GROUPED;
+  *out = gnx_wgrad_grouped_plan_info{p.kernel,
+                                     p.ranges,
+                                     p.chunks_per_range,
+                                     p.kernel == GNX_WGRAD_KERNEL_NONE ? 0u : p.grid_x,
+                                     (uint32_t)gnx_cdiv(N, BN),
+                                     (uint32_t)gnx_cdiv(K, BN),
+                                     pipe ? 512u : 256u};
+  return GNX_OK;
 }
 
 extern "C" int32_t gnx_gemm_wgrad_batched(gnx_handle* h, int32_t nprob, const gnx_wgrad_prob* probs) {

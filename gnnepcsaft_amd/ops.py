@@ -587,6 +587,18 @@ def gemm_wgrad_grouped(dC: torch.Tensor, A: torch.Tensor, dW_cls: torch.Tensor, 
                                              dc.max_chunks))
 
 
+def gemm_wgrad_grouped_plan(dC: torch.Tensor, A: torch.Tensor, max_chunks: int) -> Tuple[str, "_lib.WgradGroupedPlanInfo"]:
+    """Which kernel gemm_wgrad_grouped() takes for these operands and a chunk table of ``max_chunks`` entries, marshalled
+    as it marshals them: (its name, one of _lib.WGRAD_KERNEL_NAMES, and the gnx_wgrad_grouped_plan_info).  Launches
+    nothing."""
+    xp, ldx = _mat(dC, "dC")
+    ap, lda = _mat(A, "A")
+    info = _lib.WgradGroupedPlanInfo()
+    check(_lib.load().gnx_gemm_wgrad_grouped_plan(handle(dC.device), ldx, lda, xp, ap, dC.size(0), dC.size(1), A.size(1),
+                                                  int(max_chunks), C.byref(info)))
+    return _lib.WGRAD_KERNEL_NAMES[info.kernel], info
+
+
 def pna_weff(W: torch.Tensor, F: int, D: int, avg_deg_log: float) -> torch.Tensor:
     """Weff fp32[D, F, 4F] from post_nns[t][0].weight ([F, 13F])."""
     wp, ldw = _mat(W, "W")

@@ -332,6 +332,27 @@ int32_t gnx_gemm_wgrad_grouped(gnx_handle* h, const float* dC, int64_t lddc, con
                                int32_t N, int32_t K, float* dW_cls, int64_t lddw, int64_t dw_cls_stride,
                                const int32_t* row_index, const int32_t* chunk_info, const int32_t* nchunks,
                                int64_t max_chunks);
+/* Which kernel that call takes and how it shares out the chunk table, without launching anything or touching device
+ * memory.  k_gemm_wgrad3p_grouped takes the calls on the split-operand path (M >= 4096, GNX_OPT_GEMM_SPLIT) whose operands
+ * are 16-byte aligned with lddc, lda, N, K multiples of 4 and M * ld < 2^32, unless GNX_OPT_WGRAD_PIPE is 0.  Its workgroup
+ * (w, n tile, k tile) walks the chunks [w S, (w + 1) S) and merges consecutive chunks of one class into one row range:
+ * ranges = max(1, budget / (n tiles * k tiles)), S = ceil(max_chunks / ranges), grid_x = ceil(max_chunks / S); the budget
+ * is GNX_OPT_WGRAD_WGS when that is > 0.  The other kernels run one workgroup per chunk (grid_x = max_chunks). */
+enum {
+  GNX_WGRAD_KERNEL_NONE = 0,            /* nothing is launched (M = 0) */
+  GNX_WGRAD_KERNEL_F32_VEC = 1,         /* k_gemm_wgrad<true, true> */
+  GNX_WGRAD_KERNEL_F32_GENERIC = 2,     /* k_gemm_wgrad<false, true> */
+  GNX_WGRAD_KERNEL_SPLIT3 = 3,          /* k_gemm_wgrad3<true> */
+  GNX_WGRAD_KERNEL_SPLIT3P_GROUPED = 4, /* k_gemm_wgrad3p_grouped */
+  GNX_WGRAD_KERNEL_COUNT = 5
+};
+typedef struct {
+  int32_t kernel;                          /* GNX_WGRAD_KERNEL_* */
+  int32_t ranges, chunks_per_range;        /* as above (whichever kernel is taken) */
+  uint32_t grid_x, grid_y, grid_z, block;  /* launch dimensions */
+} gnx_wgrad_grouped_plan_info;
+int32_t gnx_gemm_wgrad_grouped_plan(gnx_handle* h, int64_t lddc, int64_t lda, const float* dC, const float* A, int64_t M,
+                                    int32_t N, int32_t K, int64_t max_chunks, gnx_wgrad_grouped_plan_info* out);
 /* Weff[d][o][j] = W[o][F+j] + amp(d) W[o][5F+j] + att(d) W[o][9F+j]  (W = post_nns[t][0].weight [F,13F], ld ldw);
  * gnx_pna_weff_bwd: dW[:,F:5F] += sum_d dWeff[d]; dW[:,5F:9F] += sum_d amp(d) dWeff[d]; dW[:,9F:13F] += sum_d att(d).. */
 int32_t gnx_pna_weff(gnx_handle* h, const float* W, int64_t ldw, int32_t F, int32_t D, float avg_deg_log, float* Weff);
