@@ -1177,18 +1177,21 @@ _PCSAFT_MIX = {"pcsaft_mix_state": ("gnx_pcsaft_mix_state", (0, 0, 0)),
                "pcsaft_mix_bubble_t": ("gnx_pcsaft_mix_bubble_t", (0, 1, 0, 0)),
                "pcsaft_mix_dew_t": ("gnx_pcsaft_mix_dew_t", (0, 1, 0, 0)),
                "pcsaft_mix_flash": ("gnx_pcsaft_mix_flash", (0, 1, 1, 0, 0)),
-               "pcsaft_mix_stability": ("gnx_pcsaft_mix_stability", (0, 1, 0, 0))}
+               "pcsaft_mix_stability": ("gnx_pcsaft_mix_stability", (0, 1, 0, 0)),
+               "pcsaft_mix_lle": ("gnx_pcsaft_mix_lle", (0, 1, 1, 0, 0))}
 
 
 _NO_START = object()  # an entry without a start column (None there is the NULL of one that has it)
 
 
-def _pcsaft_mix(params, comp, kij, eab, owner, T, second, x, name, out=None, last=True, trial=None, start=_NO_START):
+def _pcsaft_mix(params, comp, kij, eab, owner, T, second, x, name, out=None, last=True, trial=None, start=_NO_START,
+                w0=None):
     """The mixture form ``name`` of ``_PCSAFT_MIX``: validate, take ``out`` or make the outputs, call.  ``second`` is the
     state beside T (rho or P), None for the bubble point, which has none.  ``last`` False leaves the last fp64 output
     (lnphi_pure) out: None in the result, NULL for the entry.  ``trial``: the int64 column that the stability entry
     takes beside ``owner``, and it alone.  ``start``: the fp64 column of start values that the bubble- and dew-temperature
-    entries take after ``x`` (there ``T`` holds the pressures), None for NULL."""
+    entries take after ``x`` (there ``T`` holds the pressures), None for NULL.  ``w0``: the [n, nc] fp64 start
+    compositions that the liquid-liquid entry takes after ``x``, and it alone."""
     entry, widths = _PCSAFT_MIX[name]
     params, owner, T = _pcsaft_args(params, owner, T, name)
     dev = params.device
@@ -1223,6 +1226,11 @@ def _pcsaft_mix(params, comp, kij, eab, owner, T, second, x, name, out=None, las
                 raise _lib.GnxError(_lib.GNX_E_INVALID, f"{name}: start {tuple(start.shape)} and the state "
                                                         f"{tuple(T.shape)} differ")
         after.append(_ptr(start))
+    if w0 is not None:
+        w0 = _f64_on(w0, f"{name}: w0", dev)
+        if w0.shape != x.shape:
+            raise _lib.GnxError(_lib.GNX_E_INVALID, f"{name}: w0 {tuple(w0.shape)} and the feed {tuple(x.shape)} differ")
+        after.append(w0.data_ptr())
     specs = [((n, nc) if w else (n,), _F64) for w in widths] + [((n,), _ST)]
     if not last:
         specs[-2] = None
@@ -1368,6 +1376,25 @@ def pcsaft_mix_stability(params: torch.Tensor, comp: torch.Tensor, kij: Optional
     A used slot with z = 0 is dropped (w = 0.0), a -1 slot has NaN; where status != 0 (3 also for a trial outside
     [0, nc + 2)), tpd is NaN, the densities are 0.0 and the w row is NaN."""
     return _pcsaft_mix_stability(params, comp, kij, eab, owner, trial, T, P, z)
+
+
+def _pcsaft_mix_lle(params, comp, kij, eab, owner, T, P, z, w0, out=None):
+    """``pcsaft_mix_lle`` writing into ``out`` = (beta, x, y, rho_x, rho_y, status) where given; rho_x and rho_y may be
+    None there."""
+    return _pcsaft_mix(params, comp, kij, eab, owner, T, P, z, "pcsaft_mix_lle", out=out, w0=w0)
+
+
+def pcsaft_mix_lle(params: torch.Tensor, comp: torch.Tensor, kij: Optional[torch.Tensor],
+                   eab: Optional[torch.Tensor], owner: torch.Tensor, T: torch.Tensor, P: torch.Tensor, z: torch.Tensor,
+                   w0: torch.Tensor
+                   ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Mixture PC-SAFT liquid-liquid flash at (T, P, z) started from w0 (gnx_pcsaft_mix_lle): arguments as
+    ``pcsaft_mix_flash`` with w0 [n, nc], the composition the second phase starts from (in practice the w of the
+    stability test) -> (beta [n], x [n, nc], y [n, nc], rho_x [n], rho_y [n] mol/m^3, status [n] int32; 4 = no split).  x is
+    the phase of higher molar density, beta the mole fraction of the other one.  A used slot with z = 0 is dropped (x = y =
+    0.0), a -1 slot has NaN; where status != 0 (3 also for a w0 that is not a positive number in a slot where z > 0), beta
+    and the densities are 0.0 and the x and y rows are NaN."""
+    return _pcsaft_mix_lle(params, comp, kij, eab, owner, T, P, z, w0)
 
 
 _POOL = {"add": _lib.POOL_ADD, "sum": _lib.POOL_ADD, "mean": _lib.POOL_MEAN, "max": _lib.POOL_MAX}

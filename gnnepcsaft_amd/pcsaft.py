@@ -54,6 +54,14 @@ Tangent-plane stability of a feed z at (T, P), the test the reference runs on ev
 point runs nc + 2 trial phases as rows of one launch; a negative tangent-plane distance comes back with the composition w
 that proves it, also where the split is liquid-liquid and the flash reports none.  No flash is started from w here.
 
+Liquid-liquid flashes, the split of a feed z at (T, P) that starts from the w of the stability test
+(csrc/gnx_pcsaft_mix_lle.hip): ``mix_lle`` for one point (the reference's ``mix_lle_feos``), ``mix_lle_diagram`` for the
+feed at T .. T + 50 K (``mix_lle_diagram_feos``), ``mix_lle_batch`` for every point of every system in two launches,
+``mixture_lle_flash`` on device tensors.  x is the phase of higher molar density, beta the mole fraction of the other
+one.  Each phase is in the state the stability test gives it, the one of its liquid and vapour roots with the lower Gibbs
+energy, so a split whose lighter phase sits on a vapour root is returned as it is: the same tie line ``mix_tp_flash``
+finds.  A stable feed reports ``STATUS_SINGLE_PHASE``.  Three-phase (VLLE) states are not looked for.
+
 Parameter rows are ``[m, sigma (Å), epsilon/k (K), kappa_ab, epsilon_ab/k (K), mu (D), na, nb, mw]``; state rows are
 ``[T (K), P (Pa), phase, tp, value]`` (only T and P are read).  Densities are in mol/m³, pressures in Pa.
 """
@@ -358,6 +366,26 @@ def mixture_stability(params: torch.Tensor, comp: torch.Tensor, z: torch.Tensor,
     return _reduce_trials(tpd.view(n, nt), w.view(n, nt, nc), status.view(n, nt))
 
 
+def mixture_lle_flash(params: torch.Tensor, comp: torch.Tensor, z: torch.Tensor, T: torch.Tensor, P: torch.Tensor,
+                      owner: Optional[torch.Tensor] = None, kij: Optional[torch.Tensor] = None,
+                      eab: Optional[torch.Tensor] = None, w0: Optional[torch.Tensor] = None
+                      ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Tensor form on device tensors, arguments as ``mixture_tp_flash`` -> (beta [n], x [n, nc], y [n, nc], rho_x [n],
+    rho_y [n] mol/m³, status [n] int32): the split of z at (T, P) into two phases, x the one of higher molar density, beta
+    the mole fraction of the other one, z = (1 - beta) x + beta y.  w0 [n, nc]: the composition the second phase starts
+    from, one launch of ``ops.pcsaft_mix_lle``.  Without it ``mixture_stability`` runs first and the split starts from
+    its w: a stable feed ends at once with status 4 (``STATUS_SINGLE_PHASE``), and where the stability test is
+    inconclusive its status is the point's.  A used slot with z = 0 is dropped (x = y = 0.0), a -1 slot has NaN; where
+    status != 0, beta and the densities are 0.0 and the x and y rows are NaN.  Asynchronous, on the current stream."""
+    owner = _owner(owner, T)
+    if w0 is not None:
+        return ops.pcsaft_mix_lle(params, comp, kij, eab, owner, T, P, z, w0)
+    _, tpd, w, st = mixture_stability(params, comp, z, T, P, owner, kij, eab)
+    # w only where it proves the feed unstable; the feed itself (no split: status 4, or the feed's own status 3) elsewhere
+    out = ops.pcsaft_mix_lle(params, comp, kij, eab, owner, T, P, z, torch.where((tpd < 0)[:, None], w, z))
+    return (*out[:5], torch.where(st != STATUS_OK, st, out[5]))
+
+
 def _run_mix(kind: str, params: np.ndarray, comp: np.ndarray, kij: Optional[np.ndarray], eab: Optional[np.ndarray],
              owner: np.ndarray, states: np.ndarray, start: Optional[np.ndarray] = None
              ) -> Tuple[List[Optional[np.ndarray]], np.ndarray]:
@@ -367,8 +395,9 @@ def _run_mix(kind: str, params: np.ndarray, comp: np.ndarray, kij: Optional[np.n
     columns hold the vapour and which does not read it either, and [beta [n], x [n, nc], y [n, nc], rho_l [n], rho_v [n]]
     for "flash", whose composition columns hold the feed, as do those of "stability": [tpd [n], w [n, nc]] of the points,
     their nc + 2 trials each expanded here into rows of the launch and reduced by ``_reduce_trials`` after the
-    download.  "bubble_t" and "dew_t" are "bubble" and "dew" at given pressure: they read the P column and not the T
-    column, values is [T [n], y or x [n, nc], rho_l [n], rho_v [n]], and ``start`` [n] (theirs alone) holds the
+    download.  "lle" is "stability" and then the liquid-liquid entry started from its w, two launches: [beta [n], x
+    [n, nc], y [n, nc], rho_x [n], rho_y [n]].  "bubble_t" and "dew_t" are "bubble" and "dew" at given pressure: they
+    read the P column and not the T column, values is [T [n], y or x [n, nc], rho_l [n], rho_v [n]], and ``start`` [n] (theirs alone) holds the
     temperatures the solves start from, NaN or no array at all for the kernel's own start."""
     n, nc = owner.shape[0], comp.shape[1]
     if kind in ("bubble_t", "dew_t"):
@@ -384,6 +413,12 @@ def _run_mix(kind: str, params: np.ndarray, comp: np.ndarray, kij: Optional[np.n
         _, tpd, w, status = _reduce_trials(torch.from_numpy(tpd).view(n, nt), torch.from_numpy(w).view(n, nt, nc),
                                            torch.from_numpy(status).view(n, nt))
         return [tpd.numpy(), w.numpy()], status.numpy()
+    if kind == "lle":
+        (tpd, w), st = _run_mix("stability", params, comp, kij, eab, owner, states)
+        first = np.where((tpd < 0)[:, None], w, states[:, 2:])  # as ``mixture_lle_flash`` starts it
+        values, status = _run(ops._pcsaft_mix_lle, [params, comp, kij, eab, owner, states[:, 0], states[:, 1],
+                                                    states[:, 2:], first], n, [(n,), (n, nc), (n, nc), (n,), (n,)])
+        return values, np.where(st != STATUS_OK, st, status)
     if kind == "flash":
         return _run(ops._pcsaft_mix_flash, [params, comp, kij, eab, owner, states[:, 0], states[:, 1], states[:, 2:]], n,
                     [(n,), (n, nc), (n, nc), (n,), (n,)])
@@ -785,3 +820,63 @@ def mix_stability_batch(mixtures: List[List[List[Any]]], states_batch: List[Any]
     parts = _mix_batch("stability", mixtures, states_batch, kij,
                        lambda values: np.concatenate([values[0][:, None], values[1]], axis=1))
     return [v[:, :1 + len(mixtures[i])].copy() for i, v in parts]
+
+
+def _lle_dict(k: int, states: np.ndarray, values: List[np.ndarray], keep: np.ndarray) -> dict:
+    """the reference's LLE dict of the points ``keep``: the keys of ``mix_vle_txy`` for k components, and ``beta``"""
+    beta, x, y, rho_x, rho_y = values
+    out = {"temperature": states[keep, 0].tolist(), "pressure": states[keep, 1].tolist(),
+           "density liquid": rho_x[keep].tolist(), "density vapor": rho_y[keep].tolist()}
+    out.update({f"x{j}": x[keep, j].tolist() for j in range(k)})
+    out.update({f"y{j}": y[keep, j].tolist() for j in range(k)})
+    out["beta"] = beta[keep].tolist()
+    return out
+
+
+def mix_lle(parameters: Sequence[Sequence[float]], state: Sequence[float], kij_matrix: Optional[Any] = None,
+            epsilon_ab: Optional[Any] = None) -> dict:
+    """Liquid-liquid split of the feed ``state = [T (K), P (Pa), z1, z2, ...]`` of the components ``parameters``
+    (reference ``mix_lle_feos``): the stability test, then the split started from its w.  A dict of one-element lists
+    under the keys of ``mix_vle_txy`` for k components (``temperature``, ``pressure``, ``density liquid``, ``density
+    vapor`` in mol/m³, ``x0..x{k-1}``, ``y0..y{k-1}``) and ``beta``, the mole fraction of phase 2.  As in the reference,
+    "vapor" and y name liquid phase 2; "liquid" and x are the phase of higher molar density.  Raises ``ValueError`` where
+    no split is found (a stable feed, or a solve that does not end)."""
+    return mix_lle_diagram(parameters, state, kij_matrix, epsilon_ab, points=1)
+
+
+def mix_lle_diagram(parameters: Sequence[Sequence[float]], state: Sequence[float], kij_matrix: Optional[Any] = None,
+                    epsilon_ab: Optional[Any] = None, points: int = 200) -> dict:
+    """Liquid-liquid diagram of the feed ``state = [T (K), P (Pa), z1, z2, ...]`` at P and T = linspace(T, T + 50,
+    points) (reference ``mix_lle_diagram_feos``): one stability launch and one split launch for all temperatures, as a
+    dict of equally long lists under the keys of ``mix_lle``.  Points without a split are dropped; ``ValueError`` if none
+    is left.  ``points`` = 1 is the feed's own temperature alone."""
+    if int(points) < 1:
+        raise ValueError(f"a liquid-liquid diagram needs at least 1 point, got {points}")
+    params, comp, kij, eab = _pool([parameters], [kij_matrix], [epsilon_ab])
+    k = len(parameters)
+    one = _states([list(state)], k, comp.shape[1])
+    states = np.repeat(one, int(points), axis=0)
+    if int(points) > 1:
+        states[:, 0] = np.linspace(one[0, 0], one[0, 0] + 50.0, int(points))
+    values, status = _run_mix("lle", params, comp, kij, eab, np.zeros(len(states), dtype=np.int64), states)
+    keep = status == STATUS_OK
+    if not keep.any():
+        raise ValueError("No LLE found at the given conditions.")
+    return _lle_dict(k, states, values, keep)
+
+
+def mix_lle_batch(mixtures: List[List[List[Any]]], states_batch: List[Any], kij: Optional[List[Any]] = None
+                  ) -> List[np.ndarray]:
+    """Liquid-liquid splits of every state of every non-empty table in two launches (the stability test, then the
+    split), arguments as ``mix_tp_flash_batch``: one fp64 array [rows, 1 + 2 nc_i] of rows ``[beta, x1..x_nc, y1..y_nc]``
+    per non-empty table, x the phase of higher molar density; a row of NaN where a point has no split or failed."""
+    def pick(values):
+        row = np.concatenate([values[0][:, None], values[1], values[2]], axis=1)
+        return np.where(np.isnan(values[1][:, :1]), np.nan, row)  # the first slot is always used: NaN there = failed
+
+    parts = _mix_batch("lle", mixtures, states_batch, kij, pick)
+    out = []
+    for i, v in parts:
+        k, nc = len(mixtures[i]), (v.shape[1] - 1) // 2
+        out.append(np.concatenate([v[:, :1 + k], v[:, 1 + nc:1 + nc + k]], axis=1))
+    return out

@@ -670,6 +670,25 @@ int32_t gnx_pcsaft_mix_stability(gnx_handle* h, const double* params, int64_t B,
                                  const double* mix_kij, const double* mix_eab, int64_t M, int32_t nc, const int64_t* owner,
                                  const int64_t* trial, const double* T, const double* P, const double* z, int64_t n,
                                  double* tpd, double* w, double* rho_w, double* rho_z, int32_t* status);
+/* Liquid-liquid flash started from the stability test (ref: pcsaft/pcsaft_feos.py mix_lle_feos / mix_lle_diagram_feos,
+ * and feos's tp_flash after is_stable_feos at pcsaft/kij.py:37, whose caller takes the denser phase): at T[i], P[i] (Pa)
+ * the split of the feed z[i, :] (normalised by its sum) into two phases x[i, :] and y[i, :], started from ln K = ln(w0 / z)
+ * with w0[i, :] the composition the second phase starts from, in practice the w of gnx_pcsaft_mix_stability with the most
+ * negative distance.  Equal mu_i^res/kT + ln(rho x_i) of every component, both phases at P and z = (1 - beta) x + beta y,
+ * by successive substitution on ln K with a Rachford-Rice solve per step; the state of each phase is the stability
+ * entry's (of its liquid and its lowest vapour root at P the one with the lower sum_i x_i ln f_i), so a feed whose stable
+ * split is vapour-liquid comes out as that split.  The equations hold to 1e-10 at the numbers returned.  x is the phase of
+ * higher molar density, beta[i] in [0, 1] the mole fraction of the other one, rho_x[i] >= rho_y[i] the molar densities
+ * (either may be NULL).  A used slot with z = 0 is dropped (x = y = 0.0), a -1 slot has NaN in x and y, and neither z nor
+ * w0 is read there.  status 4: no split: one component, every K on one side of 1 (w0 = z is that), or a converged split
+ * with beta outside [0, 1] or with equal phases.  status 3 also covers a non-finite or non-positive P and a w0 that is
+ * non-finite or <= 0 in a slot where z > 0.  status 1: no end within 200 steps, a non-finite value, or a phase without a
+ * root at P.  A point with status != 0 has beta = 0.0, NaN in its whole x and y rows and densities 0.0.  Three-phase
+ * states are not looked for.  The launch has no kernel id (GNX_K_NONE). */
+int32_t gnx_pcsaft_mix_lle(gnx_handle* h, const double* params, int64_t B, const int64_t* mix_comp,
+                           const double* mix_kij, const double* mix_eab, int64_t M, int32_t nc, const int64_t* owner,
+                           const double* T, const double* P, const double* z, const double* w0, int64_t n, double* beta,
+                           double* x, double* y, double* rho_x, double* rho_y, int32_t* status);
 
 /* ---- contiguous segment reduce: global pool (ref: train/models.py:218-225, 587-595) ------------------------ */
 enum { GNX_POOL_ADD = 0, GNX_POOL_MEAN = 1, GNX_POOL_MAX = 2 };

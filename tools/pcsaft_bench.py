@@ -24,12 +24,17 @@ With ``--stability`` it times the tangent-plane stability test of csrc/gnx_pcsaf
 ``pcsaft.mixture_stability`` (nc + 2 = 6 trial rows per point) on the 43 cases of tests/pcsaft_mix_stab_ref.py, repeated,
 the flash kernel on the 12 tie-line feeds among them in the same run, and that module's oracle on a sample.
 
+With ``--lle`` it times the liquid-liquid flash of csrc/gnx_pcsaft_mix_lle.hip through ``pcsaft.mixture_lle_flash`` with
+the stability start (two launches) on the 11 points of tests/pcsaft_mix_lle_ref.py that split, repeated; in the same run
+the kernel alone from the pinned w0, ``mixture_stability`` on the same points, ``mixture_tp_flash`` and
+``mixture_lle_flash`` on the three vapour-liquid feeds among them, and that module's oracle loop on a sample.
+
 With ``--bubble-t`` / ``--dew-t`` it times the bubble- / dew-temperature kernel of csrc/gnx_pcsaft_mix_tvle.hip on the
 inverse problems of those 30 bubble points (the P and y the bubble kernel reports for them), repeated, from its own start
 and from T0 = 0.9 T, the bubble- / dew-pressure kernel on the same points in the same run for the ratio, and the oracle of
 tests/pcsaft_mix_tvle_ref.py on a sample.
 
-Usage: python tools/pcsaft_bench.py [--mixture | --bubble | --dew | --bubble-t | --dew-t | --flash | --stability] [--reps 3] [--sizes 1000,100000,1000000] [--oracle-sample 20] [--out FILE.json]
+Usage: python tools/pcsaft_bench.py [--mixture | --bubble | --dew | --bubble-t | --dew-t | --flash | --stability | --lle] [--reps 3] [--sizes 1000,100000,1000000] [--oracle-sample 20] [--out FILE.json]
 """
 import argparse
 import json
@@ -278,6 +283,46 @@ def _stability(args, dev):
     return res
 
 
+def _lle(args, dev):
+    from tests import pcsaft_mix_lle_ref as L
+    points = [p for p in L.points() if p[0] in ("liquid-liquid", "vapour-liquid")]
+    params, comp = [], np.full((len(points), 4), -1, dtype=np.int64)
+    z, w0 = np.zeros((len(points), 4)), np.zeros((len(points), 4))
+    for i, (_, _, rows, _, _, zi, wi) in enumerate(points):
+        comp[i, :len(rows)] = np.arange(len(params), len(params) + len(rows))
+        params.extend(np.asarray(rows, dtype=np.float64).tolist())
+        z[i, :len(rows)], w0[i, :len(rows)] = zi, wi
+    T, P = np.array([p[3] for p in points]), np.array([p[4] for p in points])
+    vle = [i for i, p in enumerate(points) if p[0] == "vapour-liquid"]
+    step = max(1, len(points) // args.oracle_sample)
+    t0 = time.perf_counter()
+    sols = [L.lle(rows, zi, wi, t, p) for _, _, rows, t, p, zi, wi in points[::step]]
+    oracle = (time.perf_counter() - t0) / len(sols)
+    d_params, d_comp = torch.from_numpy(np.array(params)).to(dev), torch.from_numpy(comp).to(dev)
+    res = []
+    for n in [int(s) for s in args.sizes.split(",")]:
+        idx = np.arange(n) % len(points)
+        o, t, pp, zz, ww = (torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+                            for a in (idx.astype(np.int64), T[idx], P[idx], z[idx], w0[idx]))
+        k = _kernel_ms(lambda: pcsaft.mixture_lle_flash(d_params, d_comp, zz, t, pp, o))
+        st = pcsaft.mixture_lle_flash(d_params, d_comp, zz, t, pp, o)[5]
+        kw = _kernel_ms(lambda: pcsaft.mixture_lle_flash(d_params, d_comp, zz, t, pp, o, w0=ww))
+        ks = _kernel_ms(lambda: pcsaft.mixture_stability(d_params, d_comp, zz, t, pp, o))
+        fidx = np.array(vle)[np.arange(n) % len(vle)]
+        fo, ft, fp, fz = (torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+                          for a in (fidx.astype(np.int64), T[fidx], P[fidx], z[fidx]))
+        kf = _kernel_ms(lambda: pcsaft.mixture_tp_flash(d_params, d_comp, fz, ft, fp, fo))
+        kl = _kernel_ms(lambda: pcsaft.mixture_lle_flash(d_params, d_comp, fz, ft, fp, fo))
+        rec = dict(points=n, mix_lle_ms=k, mix_lle_points_per_s=n / k * 1e3, failed_points=int((st != 0).sum().item()),
+                   mix_lle_given_w0_kernel_ms=kw, mix_stability_same_points_ms=ks, lle_over_stability=k / ks,
+                   lle_kernel_over_stability=kw / ks, mix_flash_vapour_liquid_feeds_kernel_ms=kf,
+                   mix_lle_vapour_liquid_feeds_ms=kl, lle_over_flash_vapour_liquid_feeds=kl / kf,
+                   oracle_lle_ms_est=oracle * n * 1e3)
+        print(json.dumps(rec), flush=True)
+        res.append(rec)
+    return res
+
+
 def main():
     global REPS
     ap = argparse.ArgumentParser()
@@ -288,15 +333,16 @@ def main():
     ap.add_argument("--dew", action="store_true")
     ap.add_argument("--flash", action="store_true")
     ap.add_argument("--stability", action="store_true")
+    ap.add_argument("--lle", action="store_true")
     ap.add_argument("--bubble-t", action="store_true")
     ap.add_argument("--dew-t", action="store_true")
     ap.add_argument("--reps", type=int, default=REPS, help="timed repetitions per kernel, the best of which counts")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     REPS = args.reps
-    if args.mixture or args.bubble or args.dew or args.flash or args.stability or args.bubble_t or args.dew_t:
+    if args.mixture or args.bubble or args.dew or args.flash or args.stability or args.lle or args.bubble_t or args.dew_t:
         dev = torch.device("cuda", torch.cuda.current_device())
-        res = (_tvle if args.bubble_t or args.dew_t else _stability if args.stability else _flash if args.flash else _dew if args.dew else _bubble if args.bubble else _mixture)(args, dev)
+        res = (_tvle if args.bubble_t or args.dew_t else _lle if args.lle else _stability if args.stability else _flash if args.flash else _dew if args.dew else _bubble if args.bubble else _mixture)(args, dev)
         if args.out:
             with open(args.out, "w") as fh:
                 json.dump(dict(device=torch.cuda.get_device_name(dev), oracle_sample=args.oracle_sample, results=res), fh,
