@@ -16,7 +16,7 @@ ABI_VERSION = 7
 GNX_OK, GNX_E_INVALID, GNX_E_HIP, GNX_E_RANGE, GNX_E_WORKSPACE = 0, -1, -2, -3, -4
 # gnx_set_option ids (include/gnx.h)
 OPT_GEMM_SPLIT, OPT_WGRAD_WGS, OPT_EMBED_BWD_MFMA, OPT_STD_BWD_CENTERED, OPT_GEMM_PIPE, OPT_WGRAD_PIPE, OPT_GEMM_AS, \
-    OPT_GEMM_WS_FAST, OPT_GEMM_TILE_ROWS, OPT_GEMM_MID = range(10)
+    OPT_GEMM_WS_FAST, OPT_GEMM_TILE_ROWS, OPT_GEMM_MID, OPT_DA_AGG_FUSED = range(11)
 GEMM_RELU, GEMM_ACCUMULATE, GEMM_B_TRANS, GEMM_SPLIT_ONLY, GEMM_PRESPLIT = 1, 2, 4, 8, 16
 # GNX_GEMM_KERNEL_*, by value (gnx_gemm_plan)
 GEMM_KERNEL_NAMES = ("none", "k_gemm<vec>", "k_gemm<generic>", "k_gemm_ws", "k_gemm_ws3", "k_gemm_ws3<fast,8>",
@@ -266,6 +266,8 @@ SIGNATURES = {
     "gnx_gemm_split_counts": (_i32, [_vp, C.POINTER(_i64), C.POINTER(_i64)]),
     "gnx_pna_conv_fwd_images": (_i32, [_vp, C.POINTER(PnaFwdArgs), C.POINTER(PnaLayerImages)]),
     "gnx_pna_conv_bwd_images": (_i32, [_vp, C.POINTER(PnaBwdArgs), C.POINTER(PnaLayerImages)]),
+    "gnx_pna_da_aggregate_bwd": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp,
+                                        _i64, _vp, C.POINTER(GemmImage), _vp, _sz, C.POINTER(_i32)]),
     "gnx_pna_weight_only_all": (_i32, [_vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _i32, C.POINTER(_f32), C.POINTER(_vp),
                                        _i32, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp)]),
     "gnx_pna_stack_finish": (_i32, [_vp, C.POINTER(PnaFinishArgs)]),

@@ -7,6 +7,7 @@
 // destination row; G = H/VEC threads cover a row, so a 64-lane wave reads whole 1 KiB-aligned runs of a row-major
 // [rows, H] array with 16-byte lane accesses.
 #include "gnx_common.hpp"
+#include "gnx_pna_agg_item.hpp"
 
 #include <cmath>
 #include <cstdlib>
@@ -25,36 +26,10 @@ struct vec_t<1> {
   typedef float type;
 };
 
-template <int VEC>
-__device__ __forceinline__ void vload(float (&r)[VEC], const float* p) {
-  if constexpr (VEC == 4) {
-    f32x4 v = *reinterpret_cast<const f32x4*>(p);
-    r[0] = v.x;
-    r[1] = v.y;
-    r[2] = v.z;
-    r[3] = v.w;
-  } else {
-    r[0] = p[0];
-  }
-}
-template <int VEC>
-__device__ __forceinline__ void vstore(float* p, const float (&r)[VEC]) {
-  if constexpr (VEC == 4) {
-    f32x4 v = {r[0], r[1], r[2], r[3]};
-    *reinterpret_cast<f32x4*>(p) = v;
-  } else {
-    p[0] = r[0];
-  }
-}
-
 // ReLU and running maximum that keep a NaN, as torch.relu and scatter_reduce_(amax) do: fmaxf returns its other operand,
 // so fmaxf(NaN, 0) is 0 and a NaN activation would vanish from the message sum / the pooled maximum
 __device__ __forceinline__ float relu_keep_nan(float r) { return (r < 0.f) ? 0.f : r; }
 __device__ __forceinline__ float max_keep_nan(float s, float a) { return (a > s || a != a) ? a : s; }
-
-// clamp / mask constants of [3P] StdAggregation: var.clamp(min=1e-5).sqrt(), masked to 0 where <= sqrt(1e-5)
-#define STD_VAR_MIN 1e-5f
-#define STD_MASK_AT 0.0031622776601683794f
 
 // ---------------------------------------------------------------------------------------------------------------
 // PNA multi-aggregate forward: m[E, H] (CSR order) -> A[N, T, 4F] = per tower [mean | min | max | std]
@@ -171,152 +146,7 @@ __global__ void __launch_bounds__(256) k_pna_agg_bwd_rc(const float* __restrict_
   vload<VEC>(gmn, dA + ao + F);
   vload<VEC>(gmx, dA + ao + 2 * F);
   vload<VEC>(gsd, dA + ao + 3 * F);
-  float s[VEC], s2[VEC], mn[VEC], mx[VEC];
-#pragma unroll
-  for (int v = 0; v < VEC; ++v) {
-    s[v] = 0.f;
-    s2[v] = 0.f;
-    mn[v] = INFINITY;
-    mx[v] = -INFINITY;
-  }
-  // (measured and rejected, round 2: keeping the node's first 8 messages in registers for the three passes -- 71 vs 67 us at
-  // cfg-2, 0.43 vs 0.59 of HBM as run at cfg-5: the extra 32 VGPRs cost more occupancy than the L1-resident re-reads cost)
-  // (the same treatment of k_edge_combine_bwd's dQ gather and of k_gine_fwd / k_gine_bwd_dx -- indices, then rows, four at a time
-  // -- was measured and rejected: cfg-3 20.15-20.23 vs 19.99-20.00 ms, cfg-2 neutral; those kernels sit at 0.76 of HBM with
-  // one row in flight per thread and lose more occupancy to the 32 extra VGPRs than the loads gain)
-  if (p1 - p0 <= 4) {
-    // in-degree <= 4 (every atom of an organic molecule): the row's messages are loaded ONCE, all four loads in flight
-    // together (clamped addresses past the row's end), and the three passes run on registers -- same operations in the
-    // same order per element as the loops below
-    const int deg = p1 - p0;
-    float a[4][VEC];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) vload<VEC>(a[e], m + (int64_t)(p0 + (e < deg ? e : 0)) * H + c);
-#pragma unroll
-    for (int e = 0; e < 4; ++e)
-      if (e < deg) {
-#pragma unroll
-        for (int v = 0; v < VEC; ++v) {
-          s[v] = __fadd_rn(s[v], a[e][v]);
-          s2[v] = __fadd_rn(s2[v], __fmul_rn(a[e][v], a[e][v]));
-          mn[v] = fminf(mn[v], a[e][v]);
-          mx[v] = fmaxf(mx[v], a[e][v]);
-        }
-      }
-    const float cnt = (float)deg;
-    float mean[VEC], sd[VEC], nmn[VEC], nmx[VEC], c2[VEC];
-#pragma unroll
-    for (int v = 0; v < VEC; ++v) {
-      c2[v] = 0.f;
-      mean[v] = __fdiv_rn(s[v], cnt);
-      float mean2 = __fdiv_rn(s2[v], cnt);
-      float var = __fsub_rn(mean2, __fmul_rn(mean[v], mean[v]));
-      float o = __fsqrt_rn(fmaxf(var, STD_VAR_MIN));
-      sd[v] = (o <= STD_MASK_AT) ? 0.f : o;
-      nmn[v] = (mn[v] == 0.f) ? 1.f : 0.f;
-      nmx[v] = (mx[v] == 0.f) ? 1.f : 0.f;
-    }
-#pragma unroll
-    for (int e = 0; e < 4; ++e)
-      if (e < deg) {
-#pragma unroll
-        for (int v = 0; v < VEC; ++v) {
-          nmn[v] += (a[e][v] == mn[v]) ? 1.f : 0.f;
-          nmx[v] += (a[e][v] == mx[v]) ? 1.f : 0.f;
-          const float dv = a[e][v] - mean[v];
-          c2[v] = fmaf(dv, dv, c2[v]);
-        }
-      }
-    float k_mean[VEC], k_mn[VEC], k_mx[VEC], k_sd[VEC];
-#pragma unroll
-    for (int v = 0; v < VEC; ++v) {
-      k_mean[v] = gmean[v] / cnt;
-      k_mn[v] = gmn[v] / nmn[v];
-      k_mx[v] = gmx[v] / nmx[v];
-      const float sdiv = (centered && c2[v] > 0.f) ? sqrtf(c2[v] / cnt) : sd[v];
-      k_sd[v] = (sd[v] > 0.f) ? gsd[v] / (cnt * sdiv) : 0.f;
-    }
-    float* dp = dm + (int64_t)p0 * H + c;
-#pragma unroll
-    for (int e = 0; e < 4; ++e)
-      if (e < deg) {
-        float o[VEC];
-#pragma unroll
-        for (int v = 0; v < VEC; ++v) {
-          float r = k_mean[v] + k_sd[v] * (a[e][v] - mean[v]);
-          r += (a[e][v] == mn[v]) ? k_mn[v] : 0.f;
-          r += (a[e][v] == mx[v]) ? k_mx[v] : 0.f;
-          o[v] = r;
-        }
-        vstore<VEC>(dp + (int64_t)e * H, o);
-      }
-    return;
-  }
-  const float* mp = m + (int64_t)p0 * H + c;
-  for (int p = p0; p < p1; ++p, mp += H) {  // same order and roundings as k_pna_agg_fwd
-    float a[VEC];
-    vload<VEC>(a, mp);
-#pragma unroll
-    for (int v = 0; v < VEC; ++v) {
-      s[v] = __fadd_rn(s[v], a[v]);
-      s2[v] = __fadd_rn(s2[v], __fmul_rn(a[v], a[v]));
-      mn[v] = fminf(mn[v], a[v]);
-      mx[v] = fmaxf(mx[v], a[v]);
-    }
-  }
-  const float cnt = (float)(p1 - p0);
-  float mean[VEC], sd[VEC], nmn[VEC], nmx[VEC], c2[VEC];
-#pragma unroll
-  for (int v = 0; v < VEC; ++v) {
-    c2[v] = 0.f;
-    mean[v] = __fdiv_rn(s[v], cnt);
-    float mean2 = __fdiv_rn(s2[v], cnt);
-    float var = __fsub_rn(mean2, __fmul_rn(mean[v], mean[v]));
-    float o = __fsqrt_rn(fmaxf(var, STD_VAR_MIN));
-    sd[v] = (o <= STD_MASK_AT) ? 0.f : o;
-    // torch's scatter_reduce(amin/amax) backward divides by (#src ties + [self == result]) with self = the zero-filled
-    // output buffer, also under include_self=False: an extremum that is exactly 0 counts one extra tie.  The reference's
-    // CPU path behaves that way (verified on torch 2.10: src [0,-1,0] -> grads [1/3,0,1/3]); reproduced here.
-    nmn[v] = (mn[v] == 0.f) ? 1.f : 0.f;
-    nmx[v] = (mx[v] == 0.f) ? 1.f : 0.f;
-  }
-  mp = m + (int64_t)p0 * H + c;
-  for (int p = p0; p < p1; ++p, mp += H) {
-    float a[VEC];
-    vload<VEC>(a, mp);
-#pragma unroll
-    for (int v = 0; v < VEC; ++v) {
-      nmn[v] += (a[v] == mn[v]) ? 1.f : 0.f;
-      nmx[v] += (a[v] == mx[v]) ? 1.f : 0.f;
-      const float dv = a[v] - mean[v];
-      c2[v] = fmaf(dv, dv, c2[v]);
-    }
-  }
-  float k_mean[VEC], k_mn[VEC], k_mx[VEC], k_sd[VEC];
-#pragma unroll
-  for (int v = 0; v < VEC; ++v) {
-    k_mean[v] = gmean[v] / cnt;
-    k_mn[v] = gmn[v] / nmn[v];
-    k_mx[v] = gmx[v] / nmx[v];
-    // masked or not is the forward's decision (sd, bit for bit); the divisor is the centred two-pass std, free of the
-    // cancellation error of mean(x^2) - mean(x)^2 (centered = 0: the forward's value, like the CPU path's backward)
-    const float sdiv = (centered && c2[v] > 0.f) ? sqrtf(c2[v] / cnt) : sd[v];
-    k_sd[v] = (sd[v] > 0.f) ? gsd[v] / (cnt * sdiv) : 0.f;
-  }
-  mp = m + (int64_t)p0 * H + c;
-  float* dp = dm + (int64_t)p0 * H + c;
-  for (int p = p0; p < p1; ++p, mp += H, dp += H) {
-    float a[VEC], o[VEC];
-    vload<VEC>(a, mp);
-#pragma unroll
-    for (int v = 0; v < VEC; ++v) {
-      float r = k_mean[v] + k_sd[v] * (a[v] - mean[v]);
-      r += (a[v] == mn[v]) ? k_mn[v] : 0.f;
-      r += (a[v] == mx[v]) ? k_mx[v] : 0.f;
-      o[v] = r;
-    }
-    vstore<VEC>(dp, o);
-  }
+  pna_agg_bwd_item<VEC>(gmean, gmn, gmx, gsd, p0, p1, m + c, dm + c, H, centered);
 }
 
 extern "C" int32_t gnx_pna_aggregate_bwd(gnx_handle* h, const float* dA, const float* m, const float* A,

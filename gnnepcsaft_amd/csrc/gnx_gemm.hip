@@ -23,6 +23,7 @@
 //   "k-row" image  T[k][col]  (B when the weight is [k][n], i.e. NN; both operands of the weight gradient):
 //        row stride 128 floats, read with ds_read_b32 (32 consecutive columns per half-wave: conflict-free).
 #include "gnx_gemm_plan.hpp"
+#include "gnx_pna_agg_item.hpp"
 #include "gnx_split.hpp"
 
 #include <cstdlib>
@@ -1763,6 +1764,201 @@ __global__ void __launch_bounds__(256, 3) k_gemm_as3(gemm_args g) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------
+// dA product + PNA scatter-aggregate backward of one tower in ONE launch: dA = g Weff(d) ([N, 4F], the layer backward's
+// largest intermediate) is consumed by exactly one kernel, k_pna_agg_bwd_rc, which reads it straight back.  Here the
+// k_gemm_as3 product runs on a 32-ROW tile (one 32 x 32 accumulator per wave and column tile instead of two), the
+// quad-transposed result of each of the FOUR column tiles -- column tile nt = aggregator nt (mean | min | max | std) of
+// the tower's F = 128 channels -- stays in registers (64 per lane), and after the last column tile a lane holds, for each
+// of its four (row 8 gq + 4 lh + j, channels 32 wave + 4 (li >> 2) .. +3) items, exactly the four inputs one thread of
+// k_pna_agg_bwd_rc<4> loads from dA: it runs pna_agg_bwd_item on them and writes ge.  dA is never written.
+// Same MFMAs, same operands, same order per accumulator, the same bias / floor operations behind them as k_gemm_as3, the
+// same item arithmetic as k_pna_agg_bwd_rc: bit-identical to the pair.  The row's degree is read from rowptr.
+// Price: the weight image streams from L2 once per 32 rows instead of once per 64; two workgroups per CU (<= 256
+// registers per lane) so that one's aggregate phase (loads and stores) runs beside the other's matrix phase.
+// Grouped calls only; a table's 96- or 128-row class tile is taken as up to four 32-row parts.
+// ---------------------------------------------------------------------------------------------------------------
+#define DAF_BM 32
+#define DAF_PIECE (DAF_BM * AS_LDA)
+#define DAF_LDS (3 * DAF_PIECE + DAF_BM * 4)
+
+struct daf_args {
+  const float* m;     // messages fp32[E, H] in CSR order, already offset to the tower's first channel
+  const int* rowptr;  // int32[N + 1]
+  float* ge;          // message gradient fp32[E, H], offset like m
+  int H;              // row stride of m and ge
+  int centered;       // GNX_OPT_STD_BWD_CENTERED
+};
+
+__global__ void __launch_bounds__(256, 2) k_pna_dA_agg_bwd(gemm_args g, daf_args x) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char lds_daf[];
+  unsigned char* const A3 = lds_daf;
+  int* const rown = reinterpret_cast<int*>(lds_daf + 3 * DAF_PIECE);  // node of every tile row (a partial tile repeats its last)
+
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wave = tid >> 6;
+  const int li = lane & 31, lh = lane >> 5;
+  constexpr int NT = 4;
+
+  const int t = blockIdx.x >> 2, part = blockIdx.x & 3;
+  if (t >= g.ntiles[0]) return;
+  const int p0 = g.tile_info[3 * t] + DAF_BM * part;
+  int pr = g.tile_info[3 * t + 1] - DAF_BM * part;
+  const int cls = g.tile_info[3 * t + 2];
+  if (pr <= 0) return;
+  pr = pr < DAF_BM ? pr : DAF_BM;
+
+  // ---- A tile: 32 lanes cover one 512-byte row, 8 rows per pass, 4 passes; B ring: K-tile 0 of column tile 0
+  const seg_dev& s = g.seg[0];
+  const int lr = tid >> 5, k4 = (tid & 31) * 4;
+  f32x4 ra[4];
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const int r = lr + 8 * q;
+    const int row = g.row_index[p0 + (r < pr ? r : pr - 1)];
+    ra[q] = *reinterpret_cast<const f32x4*>(s.a + (int64_t)row * s.lda + k4);
+  }
+  if (tid < DAF_BM) rown[tid] = g.row_index[p0 + (tid < pr ? tid : pr - 1)];
+
+  constexpr int total_kt = NT * 4;
+  const __bf16* const bbase = g.bsplit + ((int64_t)cls * NT * 4 * 3) * (BN * BK) + (wave * 64 + lane) * 8;
+  bf16x8 bq[2][2][3];  // [K-tile parity][slab][piece]
+  auto load_b = [&](int slot, int sl, int j) {
+    const __bf16* p = bbase + (int64_t)(j < total_kt ? j : total_kt - 1) * (3 * BN * BK);
+#pragma unroll
+    for (int pc = 0; pc < 3; ++pc) bq[slot][sl][pc] = *reinterpret_cast<const bf16x8*>(p + ((sl * 3 + pc) * 4 * 64) * 8);
+  };
+  load_b(0, 0, 0);
+  load_b(0, 1, 0);
+
+  typedef __attribute__((ext_vector_type(2))) float f32x2;
+#pragma unroll
+  for (int q = 0; q < 4; q += 2) {
+    float xa[8];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      xa[j] = ra[q][j];
+      xa[4 + j] = ra[q + 1][j];
+    }
+    bf16x8 pc[3];
+    split3(xa, pc[0], pc[1], pc[2]);
+#pragma unroll
+    for (int p = 0; p < 3; ++p) {
+      const f32x4 w = *reinterpret_cast<const f32x4*>(&pc[p]);
+      unsigned char* qa = A3 + p * DAF_PIECE + (lr + 8 * q) * AS_LDA + k4 * 2;
+      *reinterpret_cast<f32x2*>(qa) = f32x2{w.x, w.y};
+      *reinterpret_cast<f32x2*>(qa + 8 * AS_LDA) = f32x2{w.z, w.w};
+    }
+  }
+  load_b(1, 0, 1);
+  load_b(1, 1, 1);
+  __syncthreads();
+
+  // this lane's four items: tile row 8 gq + 4 lh + (li & 3), channels lc .. lc + 3; their message runs, fetched now so
+  // that the aggregate phase starts with its addresses known (rows past the tile's end: an empty run)
+  const int qj = li & 3;
+  const int lc = wave * 32 + (li >> 2) * 4;
+  int e0[4], e1[4];
+#pragma unroll
+  for (int gq = 0; gq < 4; ++gq) {
+    const int r = 8 * gq + 4 * lh + qj;
+    const int node = rown[r];
+    e0[gq] = x.rowptr[node];
+    e1[gq] = r < pr ? x.rowptr[node + 1] : e0[gq];
+  }
+#pragma unroll
+  for (int gq = 0; gq < 4; ++gq) asm volatile("" ::"v"(e0[gq]), "v"(e1[gq]));  // waited for HERE, not inside the ring
+
+  int afrag = li * AS_LDA + 16 * lh;
+  bf16x8 af[2][3];  // [slab parity][piece]
+  auto read_a = [&](int slot, int off, int ks) {  // ks = 16-deep slab 0..7 of the K = 128 tile
+    const unsigned char* base = A3 + off;
+#pragma unroll
+    for (int p = 0; p < 3; ++p) af[slot][p] = *reinterpret_cast<const bf16x8*>(base + p * DAF_PIECE + ks * 32);
+  };
+  read_a(0, afrag, 0);
+
+  const f32x4 bv = *reinterpret_cast<const f32x4*>(c_zero4);  // (k_gemm_as3's bias add and floor: -0 + 0 = +0 like there)
+  const float floor_v = g.relu ? 0.f : -__builtin_inff();
+  asm volatile("" ::"v"(bv));
+  auto quad_swap = [&](float& a, float& b, auto CTRL, bool hi) {
+    const float send = hi ? a : b;
+    const float got = __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, send), decltype(CTRL)::value, 0xf, 0xf, true));
+    a = hi ? got : a;
+    b = hi ? b : got;
+  };
+  using XOR1 = std::integral_constant<int, 0xB1>;  // quad_perm [1,0,3,2]
+  using XOR2 = std::integral_constant<int, 0x4E>;  // quad_perm [2,3,0,1]
+
+  // the messages of the four items, register form (1 <= degree <= 4; a node without messages reads row 0, a longer run its
+  // first four rows: never used).  Offsets fit 32 bits (launch condition).
+  const float* const mc = x.m + lc;
+  float am[4][4][4];  // [item][message][channel]
+  auto load_messages = [&]() {
+#pragma unroll
+    for (int gq = 0; gq < 4; ++gq) {
+      const int deg = e1[gq] - e0[gq];
+#pragma unroll
+      for (int e = 0; e < 4; ++e) vload<4>(am[gq][e], mc + (deg > 0 ? (e0[gq] + (e < deg ? e : 0)) * x.H : 0));
+    }
+  };
+
+  f32x4 kept[NT][4];  // [aggregator][item]: the transposed dA tile
+#pragma unroll
+  for (int nt = 0; nt < NT; ++nt) {
+    asm volatile("" : "+v"(afrag));
+    f32x16 acc;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+#pragma unroll
+    for (int ks = 0; ks < 8; ++ks) {
+      const int kt = ks >> 1, sl = ks & 1;
+      read_a((ks + 1) & 1, afrag, (ks + 1) & 7);
+      __builtin_amdgcn_sched_barrier(0);
+      mfma_3x3(acc, af[ks & 1], bq[kt & 1][sl]);
+      load_b(kt & 1, sl, nt * 4 + kt + 2);
+      __builtin_amdgcn_sched_barrier(0);
+    }
+#pragma unroll
+    for (int gq = 0; gq < 4; ++gq) {
+      float c0 = acc[4 * gq], c1 = acc[4 * gq + 1], c2 = acc[4 * gq + 2], c3 = acc[4 * gq + 3];
+      quad_swap(c0, c1, XOR1{}, (qj & 1) != 0);
+      quad_swap(c2, c3, XOR1{}, (qj & 1) != 0);
+      quad_swap(c0, c2, XOR2{}, (qj & 2) != 0);
+      quad_swap(c1, c3, XOR2{}, (qj & 2) != 0);
+      f32x4 v = {c0 + bv.x, c1 + bv.y, c2 + bv.z, c3 + bv.w};
+#pragma unroll
+      for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], floor_v);
+      kept[nt][gq] = v;
+    }
+  }
+
+  // ---- aggregate backward on the kept tile: the messages of all four items are fetched at once (16 loads of 16 bytes in
+  // flight per lane; the ring's and the accumulators' registers are free by now).  (measured: one item at a time 116.4 us per
+  // launch at the cfg-2 layer shape, all four here 113.7, all four in front of the last column tile's MFMAs 114.6 at 250
+  // VGPRs, in front of the third tile 3 VGPRs spilled; the two launches 147.2)
+  load_messages();
+  float* const gec = x.ge + lc;
+#pragma unroll
+  for (int gq = 0; gq < 4; ++gq) {
+    const int deg = e1[gq] - e0[gq];
+    if (deg <= 0) continue;
+    float gmean[4], gmn[4], gmx[4], gsd[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      gmean[e] = kept[0][gq][e];
+      gmn[e] = kept[1][gq][e];
+      gmx[e] = kept[2][gq][e];
+      gsd[e] = kept[3][gq][e];
+    }
+    if (deg <= 4)
+      pna_agg_bwd_item_loaded<4>(gmean, gmn, gmx, gsd, deg, am[gq], gec + (int64_t)e0[gq] * x.H, x.H, x.centered);
+    else
+      pna_agg_bwd_item_loop<4>(gmean, gmn, gmx, gsd, e0[gq], e1[gq], mc, gec, x.H, x.centered);
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------
 // Mid-size product (M < 4096 rows and few 128 x 128 tiles: a 32-graph batch's 640 atoms / 1 280 bonds): the whole gnx_gemm
 // contract (segments, row scale, degree-class grouping, every epilogue) on 16 x 16 output patches, one output per thread,
 // the k-ordered fp32 fmaf chain of k_gemm_small_batched.  The tiled kernel gives such a problem 5-10 workgroups that walk K
@@ -2232,6 +2428,64 @@ extern "C" int32_t gnx_gemm_grouped(gnx_handle* h, int32_t nseg, const gnx_gemm_
   GNX_CHECK_ARG(num_classes >= 1 && num_classes <= 4096, "gnx_gemm_grouped: num_classes=%d not in [1,4096]", num_classes);
   return gemm_launch(h, nseg, segs, cls_strides, num_classes, M, N, bias, mask, ldmask, C, ldc, flags, row_index,
                      tile_info, ntiles, max_tiles, ws, ws_bytes);
+}
+
+static_assert(PLAN_DAF_BM == DAF_BM && PLAN_DAF_LDS == DAF_LDS, "plan / k_pna_dA_agg_bwd");
+
+extern "C" int32_t gnx_pna_da_aggregate_bwd(gnx_handle* h, const float* weff_t, int32_t T, int32_t F, int32_t D, int32_t t,
+                                            const float* g, const float* dA, const float* m, const int32_t* rowptr, int64_t N,
+                                            int64_t E, float* ge, const int32_t* dperm, const int32_t* tiles,
+                                            const int32_t* ntiles, int64_t max_tiles, void* image, const gnx_gemm_image* rec,
+                                            void* ws, size_t ws_bytes, int32_t* fused) {
+  GNX_CHECK_ARG(h && fused, "gnx_pna_da_aggregate_bwd: NULL argument");
+  *fused = 0;
+  GNX_CHECK_ARG(T >= 1 && F >= 1 && D >= 1 && D <= 4096 && t >= 0 && t < T && N >= 0 && E >= 0,
+                "gnx_pna_da_aggregate_bwd: bad shape T=%d F=%d D=%d t=%d N=%lld E=%lld", T, F, D, t, (long long)N, (long long)E);
+  GNX_CHECK_ARG(weff_t && g && dA && rowptr && dperm && tiles && ntiles && max_tiles > 0, "gnx_pna_da_aggregate_bwd: NULL argument");
+  GNX_CHECK_ARG(E == 0 || (m && ge), "gnx_pna_da_aggregate_bwd: NULL messages");
+  if (N == 0 || E == 0) return GNX_OK;
+  const int64_t H = (int64_t)T * F;
+  const pna_product q = pna_dA_product(weff_t, T, F, D, t, g, const_cast<float*>(dA));
+  // the images: gnx_pna_split_all's where this call's plan gives the record they were written under, else split into ws
+  int32_t extra = 0;
+  void* img = ws;
+  size_t img_bytes = ws_bytes;
+  if (image != nullptr && rec != nullptr && rec->image_bytes > 0) {
+    const gemm_plan p = pna_product_plan(q, N, GNX_GEMM_PRESPLIT, image, max_tiles, h->opt, h->num_cus);
+    if (p.images && gemm_image_equal(gemm_image_of(p), *rec)) {
+      extra = GNX_GEMM_PRESPLIT;
+      img = image;
+      img_bytes = (size_t)rec->image_bytes;
+    }
+  }
+  const pna_dA_agg_plan f = pna_dA_agg_plan_of(q, N, E, H, m, ge, extra, img, max_tiles, h->opt, h->num_cus);
+  if (!f.fused) return GNX_OK;
+  const gemm_plan& p = f.product;
+  if (img_bytes < p.image_bytes) {
+    gnx_set_error("gnx_pna_da_aggregate_bwd: workspace of %zu bytes, the split weight images need %zu", img_bytes, p.image_bytes);
+    return GNX_E_WORKSPACE;
+  }
+  GNX_CHECK_ARG(aligned16(img), "gnx_pna_da_aggregate_bwd: workspace must be 16-byte aligned");
+  if (p.run_split) {
+    const int32_t st = gemm_launch(h, q.nseg, q.seg, q.stride, q.classes, N, q.N, nullptr, nullptr, 0, q.C, q.ldc, GNX_GEMM_SPLIT_ONLY,
+                                   dperm, tiles, ntiles, max_tiles, img, img_bytes);
+    if (st != GNX_OK) return st;
+  }
+  gemm_args ga = {{},    1,     N,      q.N,    nullptr, nullptr,
+                  0,     q.C,   q.ldc,  0,      dperm,   tiles,
+                  ntiles, p.ny, reinterpret_cast<__bf16*>(img), p.Npad, p.Kpad, {}, p.Kpad / BK};
+  for (int s = 0; s < MAX_SEGS; ++s) {
+    ga.seg[s] = seg_dev{nullptr, nullptr, nullptr, 0, 0, 0, 0, 0, 0};
+    ga.koff[s] = p.koff[s];
+  }
+  const gnx_gemm_seg& in = q.seg[0];
+  ga.seg[0] = seg_dev{in.a, nullptr, in.b, in.lda, in.ldb, q.stride[0], in.k, plan_vec_a(in), plan_vec_b(in, q.stride[0])};
+  const daf_args x = {m + (int64_t)t * F, rowptr, ge + (int64_t)t * F, (int)H, h->opt[GNX_OPT_STD_BWD_CENTERED]};
+  gnx_prof_scope prof(h, GNX_K_PNA_AGG_BWD, f.bytes, f.flops, f.mfma, true);
+  GNX_LAUNCH_TIMED(prof, k_pna_dA_agg_bwd, dim3(f.grid_x), dim3(256), f.lds, h->stream, ga, x);
+  GNX_LAUNCH_CHECK();
+  *fused = 1;
+  return GNX_OK;
 }
 
 extern "C" int32_t gnx_gemm_grouped_rows(gnx_handle* h, int32_t nseg, const gnx_gemm_seg* segs, const int64_t* cls_strides,

@@ -379,3 +379,45 @@ static inline size_t pna_images_layout(int L, int T, int F, int pre, int post, i
   if (nprobs) *nprobs = n;
   return off;
 }
+
+// ---------------------------------------------------------------------------------------------------------------
+// dA product + scatter-aggregate backward in ONE launch (k_pna_dA_agg_bwd, gnx_gemm.hip): whether a tower's call takes it.
+// The fused kernel is k_gemm_as3's product on 32-row tiles with the four column tiles (mean | min | max | std of the
+// tower's F = 128 channels) kept in registers, so it is eligible only where the dA product itself takes k_gemm_as3 from
+// split images, grouped by degree class, with exactly four column tiles and the plain epilogue; the message operands must
+// allow 16-byte lane accesses, and every element offset must fit 32 bits.  Everything else keeps the two launches.
+// ---------------------------------------------------------------------------------------------------------------
+constexpr int PLAN_DAF_BM = 32;                                        // rows per workgroup of k_pna_dA_agg_bwd
+constexpr size_t PLAN_DAF_LDS = 3 * PLAN_DAF_BM * 272 + PLAN_DAF_BM * 4;  // three bf16 images of the tile + its row ids
+
+struct pna_dA_agg_plan {
+  bool fused = false;
+  gemm_plan product;  // the plan of the dA product alone (what the two-launch path runs; its images are the fused kernel's)
+  unsigned grid_x = 0;
+  size_t lds = 0;
+  double bytes = 0.0, flops = 0.0, mfma = 0.0;
+};
+
+// q = pna_dA_product(...) of one tower; N nodes, E messages, H = T F = row stride of m and ge.  extra_flags / ws as
+// pna_product_plan's.
+static inline pna_dA_agg_plan pna_dA_agg_plan_of(const pna_product& q, int64_t N, int64_t E, int64_t H, const float* m,
+                                                 const float* ge, int32_t extra_flags, const void* ws, int64_t max_tiles,
+                                                 const int* opt, int num_cus) {
+  pna_dA_agg_plan f;
+  f.product = pna_product_plan(q, N, extra_flags, ws, max_tiles, opt, num_cus);
+  const gemm_plan& p = f.product;
+  const int F = q.seg[0].k;
+  f.fused = opt[GNX_OPT_DA_AGG_FUSED] != 0 && p.kernel == GNX_GEMM_KERNEL_AS3 && p.images && !p.stop_after_split && q.grouped &&
+            max_tiles > 0 && F == PLAN_BN && q.N == 4 * PLAN_BN && p.epi == PLAN_EPI_PLAIN && q.bias == nullptr &&
+            (q.flags & GNX_GEMM_RELU) == 0 && m != nullptr && ge != nullptr && plan_aligned16(m) && plan_aligned16(ge) &&
+            H % 4 == 0 && H >= F && (double)(E + 1) * (double)H < 2147483648.0 && (double)N * (double)q.seg[0].lda < 2147483648.0 &&
+            max_tiles * (PLAN_BM / PLAN_DAF_BM) < 2147483648LL;
+  if (!f.fused) return f;
+  f.grid_x = (unsigned)(max_tiles * (PLAN_BM / PLAN_DAF_BM));
+  f.lds = PLAN_DAF_LDS;
+  // the gradient rows 4NF, the messages read and their gradient written 8EF, row pointers and the class permutation
+  f.bytes = 4.0 * N * F + 8.0 * E * F + 4.0 * E + 8.0 * N;
+  f.flops = p.flops;
+  f.mfma = p.mfma;
+  return f;
+}

@@ -176,6 +176,16 @@ extern "C" int32_t gnx_pna_conv_bwd_images(gnx_handle* h, const gnx_pna_bwd_args
     g = a->gbuf[++gi];
   }
   // ---- post layer 0: x-part weight gradient (queued), per-class weight gradient (side stream 0), dA
+  // dA and the scatter-aggregate backward behind it run as ONE launch per tower (gnx_pna_da_aggregate_bwd: dA stays in
+  // registers) as long as every tower's call is eligible; the first that is not sends the whole layer down the two-launch path
+  int ei = 0;
+  float* ge = a->gebuf[ei];
+  const float* m_last = a->hs[a->n_h - 1];
+  bool fused_agg = true;
+  auto dA_product = [&](int t) -> int32_t {
+    return run_with_image(h, pna_dA_product(a->weff[t], T, F, D, t, g, a->dA), N, ct, im ? im->dA[t] : nullptr,
+                          im ? &im->dA_rec[t] : nullptr, a->ws, a->ws_bytes);
+  };
   for (int t = 0; t < T; ++t) {
     const int k = pidx(t, false, 0);
     const float* gt = g + t * F;
@@ -193,16 +203,22 @@ extern "C" int32_t gnx_pna_conv_bwd_images(gnx_handle* h, const gnx_pna_bwd_args
       class_wgrads.push_back(class_wgrad);
     else
       GNX_TRY(class_wgrad());
-    GNX_TRY(run_with_image(h, pna_dA_product(a->weff[t], T, F, D, t, g, a->dA), N, ct, im ? im->dA[t] : nullptr,
-                           im ? &im->dA_rec[t] : nullptr, a->ws, a->ws_bytes));
+    if (fused_agg) {
+      int32_t took = 0;
+      GNX_TRY(gnx_pna_da_aggregate_bwd(h, a->weff[t], T, F, D, t, g, a->dA, m_last, a->rowptr, N, E, ge, a->dperm, a->tiles,
+                                       a->ntiles, a->max_tiles, im ? im->dA[t] : nullptr, im ? &im->dA_rec[t] : nullptr, a->ws,
+                                       a->ws_bytes, &took));
+      fused_agg = took != 0;
+      if (!fused_agg)
+        for (int u = 0; u < t; ++u) GNX_TRY(dA_product(u));  // (towers already done wrote their columns of ge: rewritten below)
+    }
+    if (!fused_agg) GNX_TRY(dA_product(t));
   }
   const float* g_post0 = g;  // gradient w.r.t. post-layer 0's output: also an operand of dx below
   // (the last layer of the pass keeps the weight gradients queued so far for the end of the layer as well: launched HERE,
   // beside the edge backward, they compete with it on the main stream: 6.612 vs 6.554 ms)
   // ---- scatter-aggregate backward, then the pre layers last..1
-  int ei = 0;
-  float* ge = a->gebuf[ei];
-  GNX_TRY(gnx_pna_aggregate_bwd(h, a->dA, a->hs[a->n_h - 1], a->A, a->rowptr, N, E, T, F, ge));
+  if (!fused_agg) GNX_TRY(gnx_pna_aggregate_bwd(h, a->dA, m_last, a->A, a->rowptr, N, E, T, F, ge));
   for (auto& fn : class_wgrads) GNX_TRY(on_side(h, 0, side, fn));
   // With two pre layers (the reference's default) the masked input gradient of pre-layer 1, the destination sums dP and the
   // bond-table sums dTe come from ONE pass over the message gradient (gnx_pna_edge_bwd); only dQ is a pass of its own.

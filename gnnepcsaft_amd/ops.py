@@ -1000,6 +1000,42 @@ def pna_aggregate_bwd(dA: torch.Tensor, m: torch.Tensor, A: torch.Tensor, g: Gra
     return dm
 
 
+def pna_dA_aggregate_bwd(gout: torch.Tensor, weffs: Sequence[torch.Tensor], m: torch.Tensor, A: torch.Tensor, g: GraphPack,
+                         dc: DegreeClasses, T: int, F: int, *, dA: Optional[torch.Tensor] = None,
+                         dm: Optional[torch.Tensor] = None, forward_tiles: bool = False) -> Tuple[torch.Tensor, bool]:
+    """dm = pna_aggregate_bwd(dA) with dA[:, t] = gout[:, tF:(t+1)F] @ weffs[t][class], and whether every tower took the
+    fused launch (gnx_pna_da_aggregate_bwd: dA is then neither written nor read).  A tower whose call is not eligible sends
+    the whole call down the two launches (gemm_grouped per tower into ``dA``, pna_aggregate_bwd).  ``weffs[t]``: fp32
+    [D, F, 4F]; ``dA`` (fp32 [N, T 4F]) and ``dm`` (like ``m``) are allocated when not given."""
+    N = gout.size(0)
+    if dA is None:
+        dA = torch.empty(N, T * 4 * F, dtype=torch.float32, device=m.device)
+    if dm is None:
+        dm = torch.empty_like(m)
+    lib, h = _lib.load(), handle(m.device)
+    nbytes = lib.gnx_pna_conv_bwd_workspace_bytes(T, F, dc.D)
+    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=m.device)
+    if forward_tiles:
+        table = (dc.dperm.data_ptr(), dc.tiles_p.data_ptr(), dc.ntiles_p.data_ptr(), dc.max_tiles_p)
+    else:
+        table = (dc.dperm.data_ptr(), dc.tiles.data_ptr(), dc.ntiles.data_ptr(), dc.max_tiles)
+    took = C.c_int32(0)
+    for t in range(T):
+        check(lib.gnx_pna_da_aggregate_bwd(h, weffs[t].data_ptr(), T, F, dc.D, t, gout.data_ptr(), dA.data_ptr(), m.data_ptr(),
+                                           g.rowptr.data_ptr(), N, g.E, dm.data_ptr(), *table, None, None, ws.data_ptr(), nbytes,
+                                           C.byref(took)))
+        if not took.value:
+            break
+    else:
+        return dm, True
+    for t in range(T):
+        gemm_grouped([(gout[:, t * F:(t + 1) * F], None, weffs[t][0], 4 * F * F)], dA[:, t * 4 * F:(t + 1) * 4 * F], dc,
+                     b_trans=False, forward_tiles=forward_tiles)
+    check(lib.gnx_pna_aggregate_bwd(h, dA.data_ptr(), m.data_ptr(), A.data_ptr(), g.rowptr.data_ptr(), N, g.E, T, F,
+                                    dm.data_ptr()))
+    return dm, False
+
+
 def gine_aggregate_fwd(x: torch.Tensor, Le: torch.Tensor, g: GraphPack, eps: float) -> torch.Tensor:
     out = torch.empty_like(x)
     check(_lib.load().gnx_gine_aggregate_fwd(handle(x.device), x.data_ptr(), Le.data_ptr(), g.rowptr.data_ptr(),

@@ -66,7 +66,8 @@ enum {
   GNX_OPT_GEMM_WS_FAST = 7,      /* the weights-stationary split kernel's predicate-free form (quad-transposed 16-byte stores, exact waits) for N = 128, aligned operands, no accumulate: 2 = as two 4-wave workgroups per CU on 32-row tiles (default), 1 = one 8-wave workgroup per CU on 64-row tiles, 0 = the predicated kernel; bit-identical results */
   GNX_OPT_GEMM_TILE_ROWS = 8,    /* 96 / 128: row-tile height of the pipelined tiled product (0: chosen per launch; bit-identical results) */
   GNX_OPT_GEMM_MID = 9,          /* 1: products with M < 4096 rows and <= 48 tiles of 128 x 128 run on 16 x 16 patches (k_gemm_mid) instead of the latency-bound tiled kernel */
-  GNX_OPT_COUNT = 10
+  GNX_OPT_DA_AGG_FUSED = 10,     /* 1: a PNA layer's dA product and scatter-aggregate backward run as one launch per tower where eligible (gnx_pna_da_aggregate_bwd; bit-identical results) */
+  GNX_OPT_COUNT = 11
 };
 int32_t gnx_set_option(gnx_handle* h, int32_t opt, int32_t value);
 int32_t gnx_get_option(gnx_handle* h, int32_t opt, int32_t* value);
@@ -893,6 +894,20 @@ int32_t gnx_pna_split_all(gnx_handle* h, int32_t L, int32_t T, int32_t F, int32_
 int32_t gnx_gemm_split_counts(gnx_handle* h, int64_t* per_call, int64_t* batched);
 int32_t gnx_pna_conv_fwd_images(gnx_handle* h, const gnx_pna_fwd_args* args, const gnx_pna_layer_images* images);
 int32_t gnx_pna_conv_bwd_images(gnx_handle* h, const gnx_pna_bwd_args* args, const gnx_pna_layer_images* images);
+
+/* ---- dA product + scatter-aggregate backward of one tower in one launch --------------------------------------- */
+/* ge[:, t F .. (t+1) F) = gnx_pna_aggregate_bwd(dA = g[:, tF..] Weff_t(d))[:, tF..] without writing dA: k_pna_dA_agg_bwd
+ * computes the tower's dA tile (k_gemm_as3's product, same MFMAs in the same order) and runs the aggregate backward on the
+ * accumulators.  Bit-identical to gnx_gemm_grouped + gnx_pna_aggregate_bwd.  Taken (*fused = 1) only where that product
+ * takes k_gemm_as3 from split images with F = 128, m and ge are 16-byte aligned with (T F) % 4 == 0, every offset fits 32
+ * bits and GNX_OPT_DA_AGG_FUSED is not 0; otherwise NOTHING is launched, *fused = 0, and the caller runs the two launches.
+ * g, m, ge fp32 with row stride T F; dA is looked at for alignment only (never written); dperm / tiles / ntiles /
+ * max_tiles: the 96- or 128-row degree-class table (gnx_class_tiles).  image + rec (gnx_pna_split_all) are used under the
+ * record-equality rule of gnx_pna_conv_bwd_images, else the weights are split into ws first. */
+int32_t gnx_pna_da_aggregate_bwd(gnx_handle* h, const float* weff_t, int32_t T, int32_t F, int32_t D, int32_t t, const float* g,
+                                 const float* dA, const float* m, const int32_t* rowptr, int64_t N, int64_t E, float* ge,
+                                 const int32_t* dperm, const int32_t* tiles, const int32_t* ntiles, int64_t max_tiles,
+                                 void* image, const gnx_gemm_image* rec, void* ws, size_t ws_bytes, int32_t* fused);
 
 /* ---- small elementwise helpers used by the host module ----------------------------------------------------- */
 int32_t gnx_fill(gnx_handle* h, float* p, int64_t n, float v);

@@ -41,6 +41,7 @@ VARIANTS = {
     "ws8waves": lambda dev: ops.set_option(dev, _lib.OPT_GEMM_WS_FAST, 1),
     "rows128": lambda dev: ops.set_option(dev, _lib.OPT_GEMM_TILE_ROWS, 128),
     "rows96": lambda dev: ops.set_option(dev, _lib.OPT_GEMM_TILE_ROWS, 96),
+    "nodafused": lambda dev: ops.set_option(dev, _lib.OPT_DA_AGG_FUSED, 0),
 }
 
 
@@ -53,6 +54,7 @@ def reset(dev):
     ops.set_option(dev, _lib.OPT_EMBED_BWD_MFMA, 1)
     ops.set_option(dev, _lib.OPT_GEMM_WS_FAST, 2)
     ops.set_option(dev, _lib.OPT_GEMM_TILE_ROWS, 0)
+    ops.set_option(dev, _lib.OPT_DA_AGG_FUSED, 1)
     ops.set_option(dev, _lib.OPT_WGRAD_WGS, 0); ops.DegreeClasses.WGRAD_ROWS = 1024; ops.set_wgrad_batching(True)
     for k, v in EXTRA_RESET.items():
         v(dev)
