@@ -246,6 +246,9 @@ SIGNATURES = {
                                         _vp, _vp, _vp]),
     "gnx_pcsaft_mix_lle": (_i32, [_vp, _vp, _i64, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp,
                                   _vp, _vp, _vp]),
+    "gnx_pcsaft_kij_x1": (_i32, [_vp, _vp, _i64, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp,
+                                 _vp, _vp]),
+    "gnx_pcsaft_kij_sums": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, C.c_double, _vp]),
     "gnx_segment_pool_fwd": (_i32, [_vp, _vp, _vp, _i64, _i32, _i32, _vp]),
     "gnx_segment_pool_bwd": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp]),
     "gnx_batchnorm_workspace_bytes": (_sz, [_i64, _i32]),

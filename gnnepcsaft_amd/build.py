@@ -16,7 +16,7 @@ CSRC = PKG / "csrc"
 INCLUDE = PKG.parent / "include"
 LIB = PKG / "libgnnepcsaft_hip.so"
 OBJ_DIR = PKG / "csrc" / "build"
-SOURCES = ["gnx_api.hip", "gnx_pack.hip", "gnx_embed.hip", "gnx_gemm.hip", "gnx_wgrad.hip", "gnx_aggregate.hip", "gnx_norm.hip", "gnx_optim.hip", "gnx_layer.hip", "gnx_fused.hip", "gnx_attn.hip", "gnx_pcsaft.hip", "gnx_pcsaft_mix.hip", "gnx_pcsaft_mix_phi.hip", "gnx_pcsaft_mix_vle.hip", "gnx_pcsaft_mix_dew.hip", "gnx_pcsaft_mix_tvle.hip","gnx_pcsaft_mix_flash.hip", "gnx_pcsaft_mix_stab.hip", "gnx_pcsaft_mix_lle.hip", "gnx_collate.hip"]
+SOURCES = ["gnx_api.hip", "gnx_pack.hip", "gnx_embed.hip", "gnx_gemm.hip", "gnx_wgrad.hip", "gnx_aggregate.hip", "gnx_norm.hip", "gnx_optim.hip", "gnx_layer.hip", "gnx_fused.hip", "gnx_attn.hip", "gnx_pcsaft.hip", "gnx_pcsaft_mix.hip", "gnx_pcsaft_mix_phi.hip", "gnx_pcsaft_mix_vle.hip", "gnx_pcsaft_mix_dew.hip", "gnx_pcsaft_mix_tvle.hip","gnx_pcsaft_mix_flash.hip", "gnx_pcsaft_mix_stab.hip", "gnx_pcsaft_mix_lle.hip", "gnx_pcsaft_kij.hip", "gnx_collate.hip"]
 # -fno-slp-vectorize: the SLP vectoriser turns the fp32 -> 3 x bf16 split into packed-f32 VALU (v_pk_add_f32), which issues
 # badly beside MFMAs (tools/ubench/wave_specialised_overlap.hip: 1.41 -> 1.24 us per step without it); cfg-2 step 7.89 -> 7.77 ms
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-slp-vectorize", "-Wall",

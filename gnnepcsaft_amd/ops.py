@@ -1433,6 +1433,77 @@ def pcsaft_mix_lle(params: torch.Tensor, comp: torch.Tensor, kij: Optional[torch
     return _pcsaft_mix_lle(params, comp, kij, eab, owner, T, P, z, w0)
 
 
+def _pcsaft_kij_x1(params, comp, kij, eab, owner, T, P, x1_exp, feeds, out=None):
+    """``pcsaft_kij_x1`` writing into ``out`` = (x1, feed, residual, status) where given: the one call site of the
+    entry."""
+    name = "pcsaft_kij_x1"
+    params, owner, T = _pcsaft_args(params, owner, T, name)
+    dev = params.device
+    if comp.dtype != torch.int64 or comp.device != dev or comp.dim() != 2 or comp.size(1) != 2:
+        raise _lib.GnxError(_lib.GNX_E_INVALID, f"{name}: comp must be an int64 [M, 2] tensor on {dev} (binaries only)")
+    comp = comp.contiguous()
+    M = comp.size(0)
+    mats = []
+    for label, t in (("kij", kij), ("eab", eab)):
+        if t is not None:
+            t = _f64_on(t, f"{name}: {label}", dev)
+            if tuple(t.shape) != (M, 2, 2):
+                raise _lib.GnxError(_lib.GNX_E_INVALID, f"{name}: {label} must be [{M}, 2, 2], got {tuple(t.shape)}")
+        mats.append(t)
+    P, x1_exp, feeds = (_f64_on(t, f"{name}: {label}", dev) for label, t in (("P", P), ("x1_exp", x1_exp), ("feeds", feeds)))
+    if P.shape != T.shape or x1_exp.shape != T.shape or feeds.dim() != 1 or feeds.numel() < 1:
+        raise _lib.GnxError(_lib.GNX_E_INVALID, f"{name}: T {tuple(T.shape)}, P {tuple(P.shape)} and x1_exp "
+                                                f"{tuple(x1_exp.shape)} must be [n] and feeds {tuple(feeds.shape)} [F], F >= 1")
+    n = T.numel()
+    out = _pcsaft_outs(out, [((n,), _F64), ((n,), _ST), ((n,), _F64), ((n,), _ST)], dev, name)
+    check(_lib.load().gnx_pcsaft_kij_x1(handle(dev), params.data_ptr(), params.size(0), comp.data_ptr(), _ptr(mats[0]),
+                                        _ptr(mats[1]), M, 2, owner.data_ptr(), T.data_ptr(), P.data_ptr(),
+                                        x1_exp.data_ptr(), feeds.data_ptr(), feeds.numel(), n, *map(_ptr, out)))
+    return out
+
+
+def pcsaft_kij_x1(params: torch.Tensor, comp: torch.Tensor, kij: Optional[torch.Tensor], eab: Optional[torch.Tensor],
+                  owner: torch.Tensor, T: torch.Tensor, P: torch.Tensor, x1_exp: torch.Tensor, feeds: torch.Tensor
+                  ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Liquid x_1 of a binary at every row over a list of trial feeds, and its residual (gnx_pcsaft_kij_x1): params,
+    comp [M, 2], kij, eab, owner as ``pcsaft_mix_flash``, T [n] K, P [n] Pa, x1_exp [n] the measured x_1, feeds [F] the
+    trial z_1 -> (x1 [n] of the first feed that splits, feed [n] int32 its index, residual [n] = log((x1 + 1e-6) /
+    (x1_exp + 1e-6)), status [n] int32); NaN, -1, 10.0 and a status != 0 where no feed splits.  One wave per row, one
+    launch, no host synchronisation."""
+    return _pcsaft_kij_x1(params, comp, kij, eab, owner, T, P, x1_exp, feeds)
+
+
+def _pcsaft_kij_sums(residual, x1, x1_exp, status, seg, h, out=None):
+    """``pcsaft_kij_sums`` writing into ``out`` = (sums,) where given: the one call site of the entry."""
+    name = "pcsaft_kij_sums"
+    dev = residual.device
+    residual, x1, x1_exp = (_f64_on(t, f"{name}: {label}", dev)
+                            for label, t in (("residual", residual), ("x1", x1), ("x1_exp", x1_exp)))
+    n = residual.numel()
+    if residual.dim() != 1 or x1.shape != residual.shape or x1_exp.shape != residual.shape or \
+            status.dtype != _ST or status.device != dev or status.shape != residual.shape:
+        raise _lib.GnxError(_lib.GNX_E_INVALID, f"{name}: residual, x1, x1_exp (float64) and status (int32) must be [n] "
+                                                f"tensors on {dev}")
+    if seg.dtype != torch.int64 or seg.device != dev or seg.dim() != 1 or seg.numel() < 1:
+        raise _lib.GnxError(_lib.GNX_E_INVALID, f"{name}: seg must be an int64 [S + 1] tensor on {dev}")
+    S = seg.numel() - 1
+    (sums,) = _pcsaft_outs(out, [((S, 8), _F64)], dev, name)
+    check(_lib.load().gnx_pcsaft_kij_sums(handle(dev), residual.data_ptr(), x1.data_ptr(), x1_exp.data_ptr(),
+                                          status.contiguous().data_ptr(), seg.contiguous().data_ptr(), S, n, float(h),
+                                          sums.data_ptr()))
+    return sums
+
+
+def pcsaft_kij_sums(residual: torch.Tensor, x1: torch.Tensor, x1_exp: torch.Tensor, status: torch.Tensor,
+                    seg: torch.Tensor, h: float) -> torch.Tensor:
+    """The sums of one Levenberg-Marquardt step in k_12 (gnx_pcsaft_kij_sums) over the [n] rows of a ``pcsaft_kij_x1``
+    launch laid out [system][candidate][point], candidate 0 at k and candidate 1 at k + ``h``; seg [S + 1] int64 the
+    point ranges of the systems (system s owns the rows 2 seg[s] .. 2 seg[s + 1]) -> sums [S, 8] fp64: sum r0^2, penalised
+    rows of candidate 0, sum |r0| and sum |x1_0 - x1_exp| / x1_exp over its other rows, sum r1^2, sum J r0, sum J^2, rows
+    with J = (r1 - r0) / h defined (neither row penalised; J = 0 elsewhere).  One wave per system, one launch."""
+    return _pcsaft_kij_sums(residual, x1, x1_exp, status, seg, h)
+
+
 _POOL = {"add": _lib.POOL_ADD, "sum": _lib.POOL_ADD, "mean": _lib.POOL_MEAN, "max": _lib.POOL_MAX}
 
 

@@ -62,6 +62,11 @@ one.  Each phase is in the state the stability test gives it, the one of its liq
 energy, so a split whose lighter phase sits on a vapour root is returned as it is: the same tie line ``mix_tp_flash``
 finds.  A stable feed reports ``STATUS_SINGLE_PHASE``.  Three-phase (VLLE) states are not looked for.
 
+The k_ij fit of binaries to measured liquid compositions (csrc/gnx_pcsaft_kij.hip; the reference's pcsaft/kij.py):
+``optimize_kij`` for a VLE table (the reference's ``optimize_kij``), ``fit_kij`` for the fit alone, every binary in
+lockstep with two launches and one small download per Levenberg-Marquardt iteration, ``mix_kij_x1`` for the predicted
+x_1 and residuals of one binary under several k_12 in one launch.  Vapour-liquid data only.
+
 Parameter rows are ``[m, sigma (Å), epsilon/k (K), kappa_ab, epsilon_ab/k (K), mu (D), na, nb, mw]``; state rows are
 ``[T (K), P (Pa), phase, tp, value]`` (only T and P are read).  Densities are in mol/m³, pressures in Pa.
 """
@@ -102,24 +107,32 @@ def _upload(dev: torch.device, arrays: Sequence[Optional[np.ndarray]]) -> List[O
     return [None if a is None else next(views) for a in arrays]
 
 
-def _run(entry, inputs: Sequence[Optional[np.ndarray]], n: int, shapes: Sequence[Optional[Tuple[int, ...]]], **kw
-         ) -> Tuple[List[Optional[np.ndarray]], np.ndarray]:
+def _run_packed(entry, inputs: Sequence[Optional[np.ndarray]], n: int, shapes: Sequence[Optional[Tuple[int, ...]]],
+                ints: int = 1, **kw) -> Tuple[List[Optional[np.ndarray]], List[np.ndarray]]:
     """One upload, one launch, one download for host arrays.  ``entry`` is a call site of gnnepcsaft_amd.ops that takes
-    ``out``, ``inputs`` its arguments in order, ``shapes`` the shape of each of its fp64 outputs (None: not asked for).
-    Every output lives in one buffer, the fp64 ones followed by the status (int32, padded to 8 bytes) -> ([fp64
-    arrays], status [n])."""
+    ``out``, ``inputs`` its arguments in order, ``shapes`` the shape of each of its fp64 outputs (None: not asked for),
+    ``ints`` the number of int32 [n] outputs that follow them in ``out``.  Every output lives in one buffer, the fp64 ones
+    followed by the int32 ones (each padded to 8 bytes) -> ([fp64 arrays], [int32 arrays [n]])."""
     dev = _device()
     sizes = [0 if s is None else int(np.prod(s)) for s in shapes]
     ends = np.cumsum(sizes)
-    end = int(ends[-1])
-    out = torch.empty(end + (n + 1) // 2, dtype=torch.int64, device=dev)
+    end, half = int(ends[-1]), (n + 1) // 2
+    out = torch.empty(end + ints * half, dtype=torch.int64, device=dev)
     flt = out.view(torch.float64)
     views = [None if s is None else flt[e - k:e].view(s) for s, k, e in zip(shapes, sizes, ends)]
-    entry(*_upload(dev, inputs), out=(*views, out[end:].view(torch.int32)[:n]), **kw)
+    tails = [out[end + j * half:end + (j + 1) * half].view(torch.int32)[:n] for j in range(ints)]
+    entry(*_upload(dev, inputs), out=(*views, *tails), **kw)
     host = out.cpu().numpy()
     val = host[:end].view(np.float64)
     return ([None if s is None else val[e - k:e].reshape(s).copy() for s, k, e in zip(shapes, sizes, ends)],
-            host[end:].view(np.int32)[:n].copy())
+            [host[end + j * half:end + (j + 1) * half].view(np.int32)[:n].copy() for j in range(ints)])
+
+
+def _run(entry, inputs: Sequence[Optional[np.ndarray]], n: int, shapes: Sequence[Optional[Tuple[int, ...]]], **kw
+         ) -> Tuple[List[Optional[np.ndarray]], np.ndarray]:
+    """``_run_packed`` for an entry whose one int32 output is the status -> ([fp64 arrays], status [n])."""
+    values, (status,) = _run_packed(entry, inputs, n, shapes, **kw)
+    return values, status
 
 
 def _run_pure(kind: str, params: np.ndarray, owner: np.ndarray, T: np.ndarray, P: Optional[np.ndarray]
@@ -879,4 +892,252 @@ def mix_lle_batch(mixtures: List[List[List[Any]]], states_batch: List[Any], kij:
     for i, v in parts:
         k, nc = len(mixtures[i]), (v.shape[1] - 1) // 2
         out.append(np.concatenate([v[:, :1 + k], v[:, 1 + nc:1 + nc + k]], axis=1))
+    return out
+
+
+# ---- the k_ij fit of binaries (csrc/gnx_pcsaft_kij.hip, DESIGN.md §4c; reference pcsaft/kij.py) --------------------------
+KIJ_COLUMNS = ("inchi1", "inchi2", "T_K", "P_kPa", "mole_fraction_c1p2")
+KIJ_KEYS = ("inchi1", "inchi2", "k_12", "loss", "loss_nonan", "mape", "n_nan")
+CO2_INCHI = "InChI=1S/CO2/c2-1-3"
+_CO2_TC, _CO2_PC_KPA = 304.2, 7377.3  # the reference's CO2 check: below Tc the vapour pressure, from Tc on this
+
+
+def _kij_matrices(k12: np.ndarray) -> np.ndarray:
+    """[C] values of k_12 -> [C, 2, 2] symmetric matrices with a zero diagonal"""
+    out = np.zeros((k12.shape[0], 2, 2), dtype=np.float64)
+    out[:, 0, 1] = out[:, 1, 0] = k12
+    return out
+
+
+def _run_kij_x1(inputs: Sequence[Optional[np.ndarray]], n: int
+                ) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+    """One upload, one ``ops._pcsaft_kij_x1`` launch and one download of (x1, feed, residual, status) [n]"""
+    def entry(*args, out):  # the buffer of _run_packed holds the fp64 outputs first; the entry has the feed between them
+        return ops._pcsaft_kij_x1(*args, out=(out[0], out[2], out[1], out[3]))
+
+    (x1, residual), (feed, status) = _run_packed(entry, inputs, n, [(n,), (n,)], ints=2)
+    return x1, feed, residual, status
+
+
+def mix_kij_x1(parameters: Sequence[Sequence[float]], states: Any, x1_exp: Any, feed_x1s: Any, k12s: Any,
+               epsilon_ab: Optional[Any] = None) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+    """``mix_flash_x1`` of one binary under every candidate k_12 of ``k12s`` [C] in one launch, with the residual of the
+    fit: ``states`` [n, 2] rows ``[T (K), P (Pa)]``, ``x1_exp`` [n] the measured liquid x_1, ``feed_x1s`` [F] the trial
+    feeds -> (x1 [C, n] of the first feed, in order, that splits; feed [C, n] int32 its index; residual [C, n] =
+    log((x1 + 1e-6) / (x1_exp + 1e-6)); status [C, n] int32).  Where no feed splits: NaN, -1, the reference's penalty 10.0
+    and a status != 0.  One wave per (candidate, state) and one lane per feed (csrc/gnx_pcsaft_kij.hip); x1 is bit for bit
+    what ``mix_flash_x1`` returns under that k_12.  Like ``mix_flash_x1`` and unlike the reference's ``_pred_x1_worker``,
+    no stability test runs before a flash: a stable feed has no split with beta in [0, 1] and the flash reports it as single
+    phase.  Liquid-liquid splits are not looked for.  ``ValueError`` for anything but two components."""
+    if len(parameters) != 2:
+        raise ValueError(f"mix_kij_x1 needs a binary mixture, got {len(parameters)} components")
+    st = np.asarray(states, dtype=np.float64)
+    xe = np.asarray(x1_exp, dtype=np.float64)
+    feeds = np.ascontiguousarray(feed_x1s, dtype=np.float64)
+    ks = np.asarray(k12s, dtype=np.float64)
+    if st.ndim != 2 or st.shape[1] != 2:
+        raise ValueError(f"states must be [n, 2] rows of [T, P], got shape {st.shape}")
+    if xe.shape != (st.shape[0],):
+        raise ValueError(f"x1_exp must be [{st.shape[0]}], one value per state, got shape {xe.shape}")
+    if feeds.ndim != 1 or feeds.size == 0:
+        raise ValueError(f"feed_x1s must be a non-empty 1-d array, got shape {feeds.shape}")
+    if ks.ndim != 1:
+        raise ValueError(f"k12s must be a 1-d array, got shape {ks.shape}")
+    params = _rows(parameters)
+    eab = None if epsilon_ab is None else np.repeat(_square(epsilon_ab, 2, 2, np.nan, "epsilon_ab")[None], ks.size, axis=0)
+    n, C = st.shape[0], ks.size
+    if n * C == 0:
+        return (np.zeros((C, n)), np.zeros((C, n), dtype=np.int32), np.zeros((C, n)), np.zeros((C, n), dtype=np.int32))
+    comp = np.tile(np.arange(2, dtype=np.int64), (C, 1))
+    owner = np.repeat(np.arange(C, dtype=np.int64), n)
+    out = _run_kij_x1([params, comp, _kij_matrices(ks), eab, owner, np.tile(st[:, 0], C), np.tile(st[:, 1], C),
+                       np.tile(xe, C), feeds], n * C)
+    return tuple(v.reshape(C, n) for v in out)
+
+
+def _fit_kij_core(evaluate, npts: Any, k0: float = 0.2, xtol: float = 1e-8, ftol: float = 1e-8, max_iter: int = 50
+                  ) -> dict:
+    """Levenberg-Marquardt in one parameter for S independent problems in lockstep.  ``evaluate(index [A] int64, k [A])``
+    -> sums [A, 8] fp64 of ``ops.pcsaft_kij_sums`` for the systems ``index`` at k (and at k plus the difference step,
+    which is the evaluator's business): slot 0 sum r^2, 1 the penalised rows, 2 sum |r| and 3 sum |pred - x1| / x1 of the
+    others, 5 sum J r, 6 sum J^2.  ``npts`` [S]: the rows of each system.
+
+    lambda starts at 1e-3; the trial step is -sum J r / (sum J^2 (1 + lambda)).  A trial whose cost 0.5 sum r^2 does not
+    rise is accepted with lambda / 10, and its Jacobian came with it; a rejected one sets lambda * 10 and the step is
+    taken again from the kept Jacobian.  A system ends, and is in no later call of ``evaluate``, with the reason "cost 0",
+    "flat" (sum J^2 == 0: nothing to differentiate), "xtol" (|step| < xtol (xtol + |k|)), "ftol" (an accepted decrease <=
+    ftol cost), "lambda" (lambda > 1e12) or "max_iter" (evaluations after the first).  Everything is elementwise over the
+    systems: one fitted with others gets the bits it gets alone.  -> dict of [S] arrays ``k_12``, ``loss`` (mean r^2),
+    ``loss_nonan`` (mean |r| of the unpenalised rows, 1.0 without any), ``mape`` (mean |pred - x1| / x1 likewise),
+    ``n_nan``, ``iterations``, ``reason``, all of the last accepted evaluation."""
+    npts = np.asarray(npts, dtype=np.int64)
+    S = npts.shape[0]
+    k = np.full(S, float(k0), dtype=np.float64)
+    lam = np.full(S, 1e-3, dtype=np.float64)
+    iters = np.zeros(S, dtype=np.int64)
+    reason = np.full(S, "", dtype=object)
+    sums = np.zeros((S, 8), dtype=np.float64)
+    if S:
+        sums[:] = np.asarray(evaluate(np.arange(S, dtype=np.int64), k.copy()), dtype=np.float64).reshape(S, 8)
+    reason[sums[:, 6] == 0.0] = "flat"
+    reason[sums[:, 0] == 0.0] = "cost 0"
+    while True:
+        idx = np.flatnonzero(reason == "")
+        late = idx[iters[idx] >= max_iter]
+        reason[late] = "max_iter"
+        idx = idx[iters[idx] < max_iter]
+        if idx.size == 0:
+            break
+        cost = 0.5 * sums[idx, 0]
+        step = -sums[idx, 5] / (sums[idx, 6] * (1.0 + lam[idx]))
+        trial = np.asarray(evaluate(idx, k[idx] + step), dtype=np.float64).reshape(idx.size, 8)
+        iters[idx] += 1
+        new = 0.5 * trial[:, 0]
+        ok = new <= cost  # False for a NaN cost
+        small = np.abs(step) < xtol * (xtol + np.abs(k[idx]))
+        acc, rej = idx[ok], idx[~ok]
+        k[acc] += step[ok]
+        sums[acc] = trial[ok]
+        lam[acc] /= 10.0
+        lam[rej] *= 10.0
+        why = np.full(idx.size, "", dtype=object)
+        why[~ok & (lam[idx] > 1e12)] = "lambda"
+        why[ok & (cost - new <= ftol * cost)] = "ftol"
+        why[small] = "xtol"  # accepted or not: a larger lambda only shortens the step
+        why[ok & (trial[:, 6] == 0.0)] = "flat"
+        why[ok & (new == 0.0)] = "cost 0"
+        reason[idx] = why
+    good = npts - sums[:, 1]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return {"k_12": k, "loss": sums[:, 0] / npts,
+                "loss_nonan": np.where(good > 0, sums[:, 2] / good, 1.0), "mape": np.where(good > 0, sums[:, 3] / good, 1.0),
+                "n_nan": np.where(np.isfinite(sums[:, 1]), sums[:, 1], npts).astype(np.int64),  # NaN sums: no row counts
+                "iterations": iters, "reason": reason}
+
+
+def _kij_systems(systems: Sequence[Any]) -> Tuple[np.ndarray, List[np.ndarray], List[np.ndarray], List[np.ndarray]]:
+    """(params [2 S, 9], T, P, x1: one [n_s] fp64 array per system) of ``fit_kij``'s systems, checked"""
+    rows, Ts, Ps, xs = [], [], [], []
+    for s, (parameters, T, P, x1) in enumerate(systems):
+        if len(parameters) != 2:
+            raise ValueError(f"system {s}: the k_ij fit needs a binary mixture, got {len(parameters)} components")
+        rows.append(_rows(parameters))
+        T, P, x1 = (np.asarray(a, dtype=np.float64).reshape(-1) for a in (T, P, x1))
+        if not T.size or T.shape != P.shape or T.shape != x1.shape:
+            raise ValueError(f"system {s}: T, P and x1 must be equally long and not empty, got {T.size}, {P.size}, {x1.size}")
+        Ts.append(T)
+        Ps.append(P)
+        xs.append(x1)
+    return (np.concatenate(rows) if rows else np.zeros((0, 9))), Ts, Ps, xs
+
+
+def _kij_evaluator(systems: Sequence[Any], feeds: np.ndarray, diff_step: float):
+    """(evaluate, npts) for ``_fit_kij_core`` on the GPU: parameters and feeds are uploaded once; ``evaluate(index, k)`` is
+    one upload of the rows [system][k, k + diff_step][point] of the systems ``index``, one ``ops.pcsaft_kij_x1`` and one
+    ``ops.pcsaft_kij_sums`` launch and one download of [len(index), 8]."""
+    params, Ts, Ps, xs = _kij_systems(systems)
+    npts = np.array([t.size for t in Ts], dtype=np.int64)
+    if not len(Ts):
+        return None, npts
+    dev = _device()
+    d_params, d_feeds = _upload(dev, [params, feeds])
+    h = float(diff_step)
+
+    def evaluate(index: np.ndarray, k: np.ndarray) -> np.ndarray:
+        A = index.size
+        comp = np.repeat(2 * index, 2)[:, None] + np.arange(2, dtype=np.int64)  # candidates share their component rows
+        kij = _kij_matrices(np.stack([k, k + h], axis=1).reshape(-1))
+        n_a = npts[index]
+        owner = np.repeat(np.arange(2 * A, dtype=np.int64), np.repeat(n_a, 2))
+        T, P, xe = (np.concatenate([np.tile(col[s], 2) for s in index]) for col in (Ts, Ps, xs))
+        seg = np.concatenate([np.zeros(1, dtype=np.int64), np.cumsum(n_a)])
+        d = _upload(dev, [comp, kij, owner, T, P, xe, seg])
+        x1, _, res, st = ops.pcsaft_kij_x1(d_params, d[0], d[1], None, d[2], d[3], d[4], d[5], d_feeds)
+        return ops.pcsaft_kij_sums(res, x1, d[5], st, d[6], h).cpu().numpy()
+
+    return evaluate, npts
+
+
+def fit_kij(systems: Sequence[Any], feed_x1s: Optional[Any] = None, n: int = 50, k0: float = 0.2, diff_step: float = 1e-5,
+            xtol: float = 1e-8, ftol: float = 1e-8, max_iter: int = 50) -> dict:
+    """One k_12 per binary, fitted to measured liquid compositions by Levenberg-Marquardt on the residuals
+    log((x1_pred + 1e-6) / (x1 + 1e-6)), all binaries in lockstep (the ``least_squares`` call of the reference's
+    pcsaft/kij.py ``optimize_kij``, which fits one pair after the other).  ``systems``: a list of (parameters [2 rows],
+    T [n_s] K, P [n_s] Pa, x1 [n_s]); ``feed_x1s``: the trial feeds of ``mix_kij_x1``, by default the reference's
+    ``np.linspace(1e-5, 0.99, n)``.  Every iteration is one ``ops.pcsaft_kij_x1`` and one ``ops.pcsaft_kij_sums`` launch over
+    the rows (k_trial, k_trial + diff_step) of the systems still active, and one download of [active, 8]; a system that has
+    ended is in no later launch.  A point without a predicted x1 has the reference's penalty 10.0 as its residual and,
+    unlike there, 0 as its derivative.  The forward difference is taken over ``diff_step`` = 1e-5, not scipy's 1.5e-8: the
+    flash ends at 1e-10 in ln f.  -> the dict of ``_fit_kij_core``: [S] arrays ``k_12``, ``loss``, ``loss_nonan``, ``mape``,
+    ``n_nan``, ``iterations``, ``reason``.  Liquid-liquid systems are not handled; no stability test runs (``mix_kij_x1``)."""
+    feeds = np.linspace(1e-5, 0.99, int(n)) if feed_x1s is None else np.ascontiguousarray(feed_x1s, dtype=np.float64)
+    if feeds.ndim != 1 or feeds.size == 0:
+        raise ValueError(f"feed_x1s must be a non-empty 1-d array, got shape {feeds.shape}")
+    if not (np.isfinite(diff_step) and diff_step != 0.0):
+        raise ValueError(f"diff_step must be finite and not 0, got {diff_step}")
+    evaluate, npts = _kij_evaluator(systems, feeds, diff_step)
+    return _fit_kij_core(evaluate, npts, k0=k0, xtol=xtol, ftol=ftol, max_iter=max_iter)
+
+
+def _kij_table(binary_vle: Any) -> List[Tuple[str, str, np.ndarray, np.ndarray, np.ndarray]]:
+    """The VLE table of ``optimize_kij`` split by pair, on the host: (inchi1, inchi2, T_K, P_kPa, x1) of every pair in
+    order of first appearance, rows with a null or NaN x1 dropped, pairs without a row left included (empty arrays).
+    ``ValueError`` for a missing column or columns of unequal length."""
+    missing = [c for c in KIJ_COLUMNS if c not in binary_vle]
+    if missing:
+        raise ValueError(f"binary_vle lacks the columns {missing}; it needs {list(KIJ_COLUMNS)}")
+    cols = [list(binary_vle[c]) for c in KIJ_COLUMNS]
+    if len({len(c) for c in cols}) != 1:
+        raise ValueError(f"the columns of binary_vle differ in length: {[len(c) for c in cols]}")
+    pairs: dict = {}
+    for a, b, T, P, x in zip(*cols):
+        rows = pairs.setdefault((a, b), [])
+        if x is not None and not np.isnan(x):
+            rows.append((np.nan if T is None else T, np.nan if P is None else P, x))
+    out = []
+    for (a, b), rows in pairs.items():
+        t = np.asarray(rows, dtype=np.float64).reshape(-1, 3)
+        out.append((a, b, t[:, 0].copy(), t[:, 1].copy(), t[:, 2].copy()))
+    return out
+
+
+def _kij_co2_pressure_kpa(T: np.ndarray, vp_pa: np.ndarray) -> np.ndarray:
+    """the pressure scale of the reference's CO2 check in kPa: ``vp_pa``, the CO2 vapour pressure at the T below 304.2 K in
+    their order, there, and 7377.3 kPa elsewhere"""
+    out = np.full(T.shape, _CO2_PC_KPA, dtype=np.float64)
+    out[T < _CO2_TC] = np.asarray(vp_pa, dtype=np.float64) / 1e3
+    return out
+
+
+def optimize_kij(binary_vle: Any, inchi_to_params: Any, n: int = 50, co2_check: bool = True) -> dict:
+    """The reference's pcsaft/kij.py ``optimize_kij``: one k_12 for every binary of a VLE table, all fitted at once by
+    ``fit_kij``.  ``binary_vle`` is a mapping of column name to sequence (``polars.DataFrame.to_dict(as_series=False)``,
+    ``pandas.DataFrame.to_dict("list")``) with the columns ``inchi1, inchi2, T_K, P_kPa, mole_fraction_c1p2``;
+    ``inchi_to_params`` maps an InChI to its parameter row; ``n`` trial feeds ``np.linspace(1e-5, 0.99, n)``.  Rows with a
+    null or NaN x1 are dropped and pairs are taken in order of first appearance.  With ``co2_check`` only rows with
+    P_kPa / vp < 0.85 are kept, vp the CO2 vapour pressure (kPa) of ``inchi_to_params["InChI=1S/CO2/c2-1-3"]`` below
+    304.2 K (one ``vp_batch`` launch for the whole table) and 7377.3 kPa from there on; ``KeyError`` without that key, as in
+    the reference.  Pairs left without rows are skipped.  -> a dict of lists under the reference's keys ``inchi1, inchi2,
+    k_12, loss, loss_nonan, mape, n_nan`` (``polars.DataFrame(result)`` is the reference's return value)."""
+    table = _kij_table(binary_vle)
+    co2 = inchi_to_params[CO2_INCHI] if co2_check else None
+    unknown = sorted({c for a, b, *_ in table for c in (a, b) if c not in inchi_to_params})
+    if unknown:
+        raise KeyError(f"inchi_to_params has no parameters for {unknown}")  # before any launch
+    if co2_check and table:
+        T_all = np.concatenate([t[2] for t in table])
+        cold = T_all[T_all < _CO2_TC]
+        vp = vp_batch([co2], [cold[:, None]])[0] if cold.size else np.zeros(0)
+        keep = np.concatenate([t[3] for t in table]) / _kij_co2_pressure_kpa(T_all, vp) < 0.85
+        cuts = np.cumsum([t[2].size for t in table])[:-1]
+        table = [(a, b, T[m], P[m], x[m]) for (a, b, T, P, x), m in zip(table, np.split(keep, cuts))]
+    table = [t for t in table if t[2].size]
+    out: dict = {key: [] for key in KIJ_KEYS}
+    if not table:
+        return out
+    fit = fit_kij([([inchi_to_params[a], inchi_to_params[b]], T, P * 1e3, x) for a, b, T, P, x in table], n=n)
+    out["inchi1"] = [t[0] for t in table]
+    out["inchi2"] = [t[1] for t in table]
+    for key in KIJ_KEYS[2:]:
+        out[key] = fit[key].tolist()
     return out

@@ -690,6 +690,34 @@ int32_t gnx_pcsaft_mix_lle(gnx_handle* h, const double* params, int64_t B, const
                            const double* mix_kij, const double* mix_eab, int64_t M, int32_t nc, const int64_t* owner,
                            const double* T, const double* P, const double* z, const double* w0, int64_t n, double* beta,
                            double* x, double* y, double* rho_x, double* rho_y, int32_t* status);
+/* Predicted liquid x_1 of a binary over a list of trial feeds, and its residual against a measurement (ref:
+ * pcsaft/kij.py:20-49 _pred_x1_worker and :52-82 _loss_fn): row i is the state T[i], P[i] (Pa) of mixture owner[i] with
+ * the measured liquid mole fraction x1_exp[i] of slot 0.  Several candidate k_12 of one system are several mixtures whose
+ * mix_comp rows name the same parameter rows and whose mix_kij differ.  nc must be 2 and F >= 1.  Every feed z =
+ * (feeds[f], 1 - feeds[f]), f < F, is flashed as gnx_pcsaft_mix_flash flashes it, one wave of 64 lanes per row and one
+ * lane per feed, 64 feeds at a time in list order; the row takes the first feed that splits (status 0 of the flash):
+ * x1[i] is the bits of that flash's x[.., 0], feed[i] its index in feeds, residual[i] = log((x1 + 1e-6) / (x1_exp + 1e-6))
+ * and status[i] = 0.  Where no feed splits x1[i] = NaN, feed[i] = -1, residual[i] = 10.0 (the reference's penalty) and
+ * status[i] is 3 where every feed reports bad input (as gnx_pcsaft_mix_flash judges it) or x1_exp[i] is not finite, else 1
+ * where a feed ended without convergence, else 4.  Where a feed splits and the residual is not finite (x1_exp[i] not
+ * finite or below -1e-6), residual[i] = 10.0 and status[i] = 3 beside the x1 and feed of the split.  Unlike the reference
+ * no stability test runs before a flash: a stable feed has no split with beta in [0, 1] and counts as single phase.
+ * Liquid-liquid splits are not looked for.  Same input, same bits.  The launch has no kernel id (GNX_K_NONE). */
+int32_t gnx_pcsaft_kij_x1(gnx_handle* h, const double* params, int64_t B, const int64_t* mix_comp, const double* mix_kij,
+                          const double* mix_eab, int64_t M, int32_t nc, const int64_t* owner, const double* T,
+                          const double* P, const double* x1_exp, const double* feeds, int64_t F, int64_t n, double* x1,
+                          int32_t* feed, double* residual, int32_t* status);
+/* The sums of one Levenberg-Marquardt step in k_12 of S binaries (ref: pcsaft/kij.py:144-188, the least_squares call of
+ * optimize_kij with jac="2-point" and the scores after it) over the n rows of a gnx_pcsaft_kij_x1 launch laid out
+ * [system][candidate][point]: system s has the points seg[s] .. seg[s + 1], candidate 0 (at k) in the rows 2 seg[s] + j
+ * and candidate 1 (at k + hstep) in the rows 2 seg[s] + n_s + j.  A row is penalised where its status != 0.  sums[s, :]:
+ * 0 sum r0^2 (penalties included), 1 the number of penalised rows of candidate 0, 2 sum |r0| and 3 sum |x1_0 - x1_exp| /
+ * x1_exp over its other rows, 4 sum r1^2, 5 sum J r0, 6 sum J^2, 7 the number of rows with J defined; J = (r1 - r0) /
+ * hstep where neither row is penalised and 0 elsewhere (the reference differences the penalty too).  One wave per
+ * system, a fixed order of additions: same input, same bits.  A system whose range is not within the n rows has NaN in
+ * all eight.  hstep must be finite and not 0.  The launch has no kernel id (GNX_K_NONE). */
+int32_t gnx_pcsaft_kij_sums(gnx_handle* h, const double* residual, const double* x1, const double* x1_exp,
+                            const int32_t* status, const int64_t* seg, int64_t S, int64_t n, double hstep, double* sums);
 
 /* ---- contiguous segment reduce: global pool (ref: train/models.py:218-225, 587-595) ------------------------ */
 enum { GNX_POOL_ADD = 0, GNX_POOL_MEAN = 1, GNX_POOL_MAX = 2 };

@@ -34,7 +34,13 @@ inverse problems of those 30 bubble points (the P and y the bubble kernel report
 and from T0 = 0.9 T, the bubble- / dew-pressure kernel on the same points in the same run for the ratio, and the oracle of
 tests/pcsaft_mix_tvle_ref.py on a sample.
 
-Usage: python tools/pcsaft_bench.py [--mixture | --bubble | --dew | --bubble-t | --dew-t | --flash | --stability | --lle] [--reps 3] [--sizes 1000,100000,1000000] [--oracle-sample 20] [--out FILE.json]
+With ``--kij`` it times the k_ij fit of csrc/gnx_pcsaft_kij.hip on butane + hexane at the four states of
+tests/test_pcsaft_kij_gpu.py, replicated to ``--systems`` binaries, with the reference's 50 trial feeds: one iteration of
+``pcsaft.fit_kij`` (the row launch, the sums launch and the download, wall time), the route there was before it for the same
+work in the same run (2 S calls of ``pcsaft.mix_flash_x1``; at most ``--route-calls`` of them are timed and the rest
+scaled, the calls being equal and sequential), and a whole fit of data planted at k_12 = 0.05.
+
+Usage: python tools/pcsaft_bench.py [--mixture | --bubble | --dew | --bubble-t | --dew-t | --flash | --stability | --lle | --kij] [--reps 3] [--sizes 1000,100000,1000000] [--oracle-sample 20] [--out FILE.json]
 """
 import argparse
 import json
@@ -323,6 +329,45 @@ def _lle(args, dev):
     return res
 
 
+def _kij(args, dev):
+    from tests import pcsaft_mix_vle_ref as V
+    rows = [V.BUTANE, V.HEXANE]
+    states = np.array([(350.0, 3e5), (350.0, 4e5), (350.0, 5e5), (330.0, 2.5e5)])
+    feeds = np.linspace(1e-5, 0.99, 50)
+    h, k0, k_star = 1e-5, 0.2, 0.05
+    kmat = lambda k: [[0.0, k], [k, 0.0]]  # noqa: E731
+    data = pcsaft.mix_flash_x1(rows, states, feeds, kij_matrix=kmat(k_star))
+    res = []
+    for S in [int(s) for s in args.systems.split(",")]:
+        systems = [(rows, states[:, 0], states[:, 1], data)] * S
+        evaluate, _ = pcsaft._kij_evaluator(systems, feeds, h)
+        index, k = np.arange(S, dtype=np.int64), np.full(S, k0)
+        evaluate(index, k)
+        torch.cuda.synchronize()
+        it_ms = float("inf")
+        for _ in range(REPS):
+            t0 = time.perf_counter()
+            evaluate(index, k)
+            it_ms = min(it_ms, (time.perf_counter() - t0) * 1e3)
+        calls = min(2 * S, args.route_calls)
+        pcsaft.mix_flash_x1(rows, states, feeds, kij_matrix=kmat(k0))
+        t0 = time.perf_counter()
+        for c in range(calls):
+            pcsaft.mix_flash_x1(rows, states, feeds, kij_matrix=kmat(k0 + h * (c % 2)))
+        route_ms = (time.perf_counter() - t0) * 1e3 / calls * 2 * S
+        t0 = time.perf_counter()
+        fit = pcsaft.fit_kij(systems, n=50, k0=k0, diff_step=h)
+        fit_ms = (time.perf_counter() - t0) * 1e3
+        rec = dict(systems=S, states=len(states), feeds=len(feeds), rows_per_launch=2 * S * len(states),
+                   kij_iteration_ms=it_ms, flash_x1_route_ms=route_ms, flash_x1_route_calls_timed=calls,
+                   route_over_iteration=route_ms / it_ms, kij_fit_ms=fit_ms, fit_iterations=int(fit["iterations"].max()),
+                   fit_worst_k_error=float(np.max(np.abs(fit["k_12"] - k_star))),
+                   fit_reasons=sorted(set(fit["reason"].tolist())))
+        print(json.dumps(rec), flush=True)
+        res.append(rec)
+    return res
+
+
 def main():
     global REPS
     ap = argparse.ArgumentParser()
@@ -336,13 +381,16 @@ def main():
     ap.add_argument("--lle", action="store_true")
     ap.add_argument("--bubble-t", action="store_true")
     ap.add_argument("--dew-t", action="store_true")
+    ap.add_argument("--kij", action="store_true")
+    ap.add_argument("--systems", default="1,64,1024", help="--kij: binaries per fit")
+    ap.add_argument("--route-calls", type=int, default=16, help="--kij: mix_flash_x1 calls timed, of the 2 S of the old route")
     ap.add_argument("--reps", type=int, default=REPS, help="timed repetitions per kernel, the best of which counts")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     REPS = args.reps
-    if args.mixture or args.bubble or args.dew or args.flash or args.stability or args.lle or args.bubble_t or args.dew_t:
+    if args.mixture or args.bubble or args.dew or args.flash or args.stability or args.lle or args.bubble_t or args.dew_t or args.kij:
         dev = torch.device("cuda", torch.cuda.current_device())
-        res = (_tvle if args.bubble_t or args.dew_t else _lle if args.lle else _stability if args.stability else _flash if args.flash else _dew if args.dew else _bubble if args.bubble else _mixture)(args, dev)
+        res = (_kij if args.kij else _tvle if args.bubble_t or args.dew_t else _lle if args.lle else _stability if args.stability else _flash if args.flash else _dew if args.dew else _bubble if args.bubble else _mixture)(args, dev)
         if args.out:
             with open(args.out, "w") as fh:
                 json.dump(dict(device=torch.cuda.get_device_name(dev), oracle_sample=args.oracle_sample, results=res), fh,
