@@ -225,6 +225,8 @@ SIGNATURES = {
     "gnx_transformer_attn_dle": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp]),
     "gnx_pcsaft_density": (_i32, [_vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp]),
     "gnx_pcsaft_vapor_pressure": (_i32, [_vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp]),
+    "gnx_pcsaft_saturation": (_i32, [_vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "gnx_pcsaft_critical_point": (_i32, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "gnx_pcsaft_mix_state": (_i32, [_vp, _vp, _i64, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp,
                                     _vp]),
     "gnx_pcsaft_mix_density": (_i32, [_vp, _vp, _i64, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _vp]),

@@ -1,6 +1,6 @@
-// Second-order forward dual in one variable (value, first and second derivative), first-order forward dual in N
-// variables (value and gradient) and the closed-form site fraction of one associating component, shared by
-// gnx_pcsaft.hip (pure components) and gnx_pcsaft_mix.hpp (mixtures).
+// Second- and third-order forward duals in one variable (value and its first two or three derivatives), first-order
+// forward dual in N variables (value and gradient) and the closed-form site fraction of one associating component,
+// shared by gnx_pcsaft.hip (pure components) and gnx_pcsaft_mix.hpp (mixtures).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -46,6 +46,53 @@ __device__ __forceinline__ double value_of(double a) { return a; }
 __device__ __forceinline__ double exp(double a) { return ::exp(a); }
 __device__ __forceinline__ double log(double a) { return ::log(a); }
 __device__ __forceinline__ double sqrt(double a) { return ::sqrt(a); }
+__device__ __forceinline__ double expm1(double a) { return ::expm1(a); }
+
+// ---- third-order forward dual: (value, d, d2, d3) in one variable, the operator set of D2 ----------------------------
+// p_rho and p_rhorho of the critical-point conditions need a''' (gnx_pcsaft.hip).  Products and quotients by Leibniz's
+// rule, exp / log / sqrt from the derivatives of their defining relations (e' = e a', l' a = a', s s = a).
+struct D3 {
+  double v, d, dd, d3;
+};
+__device__ __forceinline__ D3 operator+(D3 a, D3 b) { return {a.v + b.v, a.d + b.d, a.dd + b.dd, a.d3 + b.d3}; }
+__device__ __forceinline__ D3 operator-(D3 a, D3 b) { return {a.v - b.v, a.d - b.d, a.dd - b.dd, a.d3 - b.d3}; }
+__device__ __forceinline__ D3 operator-(D3 a) { return {-a.v, -a.d, -a.dd, -a.d3}; }
+__device__ __forceinline__ D3 operator+(D3 a, double b) { return {a.v + b, a.d, a.dd, a.d3}; }
+__device__ __forceinline__ D3 operator+(double b, D3 a) { return {a.v + b, a.d, a.dd, a.d3}; }
+__device__ __forceinline__ D3 operator-(D3 a, double b) { return {a.v - b, a.d, a.dd, a.d3}; }
+__device__ __forceinline__ D3 operator-(double b, D3 a) { return {b - a.v, -a.d, -a.dd, -a.d3}; }
+__device__ __forceinline__ D3 operator*(D3 a, double b) { return {a.v * b, a.d * b, a.dd * b, a.d3 * b}; }
+__device__ __forceinline__ D3 operator*(double b, D3 a) { return {a.v * b, a.d * b, a.dd * b, a.d3 * b}; }
+__device__ __forceinline__ D3 operator*(D3 a, D3 b) {
+  return {a.v * b.v, a.d * b.v + a.v * b.d, a.dd * b.v + 2.0 * a.d * b.d + a.v * b.dd,
+          a.d3 * b.v + 3.0 * a.dd * b.d + 3.0 * a.d * b.dd + a.v * b.d3};
+}
+__device__ __forceinline__ D3 operator/(D3 a, D3 b) {
+  const double q = a.v / b.v;
+  const double qd = (a.d - q * b.d) / b.v;
+  const double qdd = (a.dd - 2.0 * qd * b.d - q * b.dd) / b.v;
+  return {q, qd, qdd, (a.d3 - 3.0 * qdd * b.d - 3.0 * qd * b.dd - q * b.d3) / b.v};
+}
+__device__ __forceinline__ D3 operator/(D3 a, double b) { return {a.v / b, a.d / b, a.dd / b, a.d3 / b}; }
+__device__ __forceinline__ D3 operator/(double a, D3 b) { return D3{a, 0.0, 0.0, 0.0} / b; }
+__device__ __forceinline__ D3 exp(D3 a) {
+  const double e = ::exp(a.v);
+  const double ed = e * a.d;
+  const double edd = ed * a.d + e * a.dd;
+  return {e, ed, edd, edd * a.d + 2.0 * ed * a.dd + e * a.d3};
+}
+__device__ __forceinline__ D3 log(D3 a) {
+  const double ld = a.d / a.v;
+  const double ldd = (a.dd - ld * a.d) / a.v;
+  return {::log(a.v), ld, ldd, (a.d3 - 2.0 * ldd * a.d - ld * a.dd) / a.v};
+}
+__device__ __forceinline__ D3 sqrt(D3 a) {
+  const double s = ::sqrt(a.v);
+  const double sd = a.d / (2.0 * s);
+  const double sdd = (a.dd - 2.0 * sd * sd) / (2.0 * s);
+  return {s, sd, sdd, (a.d3 - 6.0 * sd * sdd) / (2.0 * s)};
+}
+__device__ __forceinline__ double value_of(D3 a) { return a.v; }
 
 // ---- first-order forward "gradient" dual: a value and its partial derivatives in N independent variables -------------
 // The operator set of D2.  A double converts to a constant (all partials zero), so code written for double or D2
@@ -125,6 +172,8 @@ __device__ __forceinline__ DG<N> exp(const DG<N>& a) {
   const double e = ::exp(a.v);
   return dg_chain(e, e, a);
 }
+template <int N>
+__device__ __forceinline__ DG<N> expm1(const DG<N>& a) { return dg_chain(::expm1(a.v), ::exp(a.v), a); }
 template <int N>
 __device__ __forceinline__ DG<N> log(const DG<N>& a) { return dg_chain(::log(a.v), 1.0 / a.v, a); }
 template <int N>

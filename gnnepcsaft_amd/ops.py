@@ -1203,6 +1203,54 @@ def pcsaft_vapor_pressure(params: torch.Tensor, owner: torch.Tensor, T: torch.Te
     return _pcsaft_vapor_pressure(params, owner, T)
 
 
+def _pcsaft_saturation(params, owner, T, out=None):
+    """``pcsaft_saturation`` writing into ``out`` = (psat, rho_l, rho_v, h_l, h_v, s_l, s_v, status) where given; each of
+    the seven fp64 tensors may be None there: the one call site of the entry."""
+    params, owner, T = _pcsaft_args(params, owner, T, "pcsaft_saturation")
+    n, dev = T.numel(), params.device
+    out = _pcsaft_outs(out, [((n,), _F64)] * 7 + [((n,), _ST)], dev, "pcsaft_saturation")
+    if out[7] is None:
+        raise _lib.GnxError(_lib.GNX_E_INVALID, "pcsaft_saturation: out must hold a status tensor")
+    check(_lib.load().gnx_pcsaft_saturation(handle(dev), params.data_ptr(), params.size(0), owner.data_ptr(),
+                                            T.data_ptr(), n, *map(_ptr, out)))
+    return out
+
+
+def pcsaft_saturation(params: torch.Tensor, owner: torch.Tensor, T: torch.Tensor) -> Tuple[torch.Tensor, ...]:
+    """PC-SAFT saturation line (gnx_pcsaft_saturation): params [B, 9] fp64, owner [n] int64, T [n] K -> (psat [n] Pa,
+    rho_l [n], rho_v [n] mol/m^3, h_l [n], h_v [n] J/mol, s_l [n], s_v [n] J/mol/K, status [n] int32): the state of
+    ``pcsaft_vapor_pressure`` with the residual molar enthalpy and the residual molar entropy (at the same T and V) of
+    both phases; all 0.0 where status != 0 (2 = supercritical).  One launch, no host synchronisation."""
+    return _pcsaft_saturation(params, owner, T)
+
+
+def _pcsaft_critical_point(params, out=None):
+    """``pcsaft_critical_point`` writing into ``out`` = (Tc, Pc, rho_c, h_c, s_c, status) where given; h_c and s_c, the
+    residual molar enthalpy (J/mol) and entropy (J/mol/K) at the critical point, may be None there and are not computed
+    without ``out``: the one call site of the entry."""
+    dev = params.device
+    params = _f64_on(params, "pcsaft_critical_point: params", dev)
+    if params.dim() != 2 or params.size(1) != 9:
+        raise _lib.GnxError(_lib.GNX_E_INVALID, f"pcsaft_critical_point: params must be [B, 9], got {tuple(params.shape)}")
+    B = params.size(0)
+    if out is None:
+        out = [torch.empty((B,), dtype=_F64, device=dev) for _ in range(3)] + [None, None,
+                                                                               torch.empty((B,), dtype=_ST, device=dev)]
+    out = _pcsaft_outs(out, [((B,), _F64)] * 5 + [((B,), _ST)], dev, "pcsaft_critical_point")
+    if any(out[k] is None for k in (0, 1, 2, 5)):
+        raise _lib.GnxError(_lib.GNX_E_INVALID, "pcsaft_critical_point: out must hold Tc, Pc, rho_c and status")
+    check(_lib.load().gnx_pcsaft_critical_point(handle(dev), params.data_ptr(), B, *map(_ptr, out)))
+    return out
+
+
+def pcsaft_critical_point(params: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """PC-SAFT vapour-liquid critical points (gnx_pcsaft_critical_point): params [B, 9] fp64 -> (Tc [B] K, Pc [B] Pa,
+    rho_c [B] mol/m^3, status [B] int32), one lane per row; all 0.0 where status != 0 (1 = no loop found or the polish
+    did not converge, 3 = invalid row).  One launch, no host synchronisation."""
+    Tc, Pc, rho_c, _, _, status = _pcsaft_critical_point(params)
+    return Tc, Pc, rho_c, status
+
+
 # the mixture forms: entry point and fp64 outputs in argument order (0: [n], 1: [n, nc]); the status follows them
 _PCSAFT_MIX = {"pcsaft_mix_state": ("gnx_pcsaft_mix_state", (0, 0, 0)),
                "pcsaft_mix_density": ("gnx_pcsaft_mix_density", (0,)),

@@ -1,5 +1,6 @@
 """Pure-component PC-SAFT liquid density and vapour pressure on the GPU, for the validation metrics of
-``GNNePCSAFTL.validation_step`` (``mape_den`` / ``mape_vp``).
+``GNNePCSAFTL.validation_step`` (``mape_den`` / ``mape_vp``), with the saturation line's enthalpy and entropy, critical
+points and phase diagrams, and PC-SAFT mixtures.
 
 Stands in for the reference's feos calls (gnnepcsaft/train/utils.py:238-300 ``rho_batch`` / ``vp_batch`` and
 pcsaft/pcsaft_feos.py ``pure_den_feos`` / ``pure_vp_feos``), with the same arguments and results.  The arithmetic is
@@ -9,6 +10,14 @@ Enable the native evaluation on a model with::
 
     from gnnepcsaft_amd import pcsaft
     model.rho_batch, model.vp_batch = pcsaft.rho_batch, pcsaft.vp_batch
+
+The rest of the reference's pure-component entries sit on the same saturation line (csrc/gnx_pcsaft.hip):
+``critical_points`` (``critical_points_feos``: ``[Tc (K), Pc (Pa), Dc (mol/m³)]``), ``pure_h_lv`` (``pure_h_lv_feos``,
+kJ/mol), ``pure_s_lv`` (``pure_s_lv_feos``, J/mol/K) and ``phase_diagram`` (``phase_diagram_feos``) for one component,
+``critical_points_batch`` / ``h_lv_batch`` / ``s_lv_batch`` for every row or every point of every table in one launch,
+``saturation`` / ``critical_point`` on device tensors.  Enthalpies and entropies are residual ones, the entropy at the
+same T and V: ``pure_s_lv`` is the reference's function taken literally and equals h_lv / T - R ln(rho_L / rho_V), not
+h_lv / T.  The critical point is the one of the van der Waals loop that vanishes last as T rises.
 
 Binary (and up to quaternary) mixture densities, the reference's second score (demo/utils_binary.py ``binary_test`` ->
 pcsaft/pcsaft_feos.py ``mix_den_feos``), come from the mixture kernels of csrc/gnx_pcsaft_mix.hip:
@@ -236,6 +245,145 @@ def vapor_pressure(params: torch.Tensor, T: torch.Tensor, owner: Optional[torch.
     """Tensor form on device tensors: params [B, 9] fp64, T [n] fp64, owner [n] int64 (default: point i uses row i)
     -> (psat [n] Pa, rho_l [n], rho_v [n] mol/m³, status [n] int32).  Asynchronous, on the current stream."""
     return ops.pcsaft_vapor_pressure(params, _owner(owner, T), T)
+
+
+# ---- the saturation line and the critical point of a pure component (DESIGN.md §4b) ---------------------------------
+def saturation(params: torch.Tensor, T: torch.Tensor, owner: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, ...]:
+    """Tensor form on device tensors: params [B, 9] fp64, T [n] fp64, owner [n] int64 (default: point i uses row i)
+    -> (psat [n] Pa, rho_l [n], rho_v [n] mol/m³, h_l [n], h_v [n] J/mol, s_l [n], s_v [n] J/mol/K, status [n] int32).
+    h = R T (-T a_T + Z - 1) and s = -R (a + T a_T) are the residual molar enthalpy and the residual molar entropy at the
+    same T and V.  Asynchronous, on the current stream."""
+    return ops.pcsaft_saturation(params, _owner(owner, T), T)
+
+
+def critical_point(params: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Tensor form on device tensors: params [B, 9] fp64 -> (Tc [B] K, Pc [B] Pa, rho_c [B] mol/m³, status [B] int32),
+    the vapour-liquid critical point of every row.  Asynchronous, on the current stream."""
+    return ops.pcsaft_critical_point(params)
+
+
+def _run_saturation(params: np.ndarray, owner: np.ndarray, T: np.ndarray) -> Tuple[List[np.ndarray], np.ndarray]:
+    """([psat, rho_l, rho_v, h_l, h_v, s_l, s_v] [n] fp64, status [n] int32)"""
+    n = owner.shape[0]
+    return _run(ops._pcsaft_saturation, [params, owner, T], n, [(n,)] * 7)
+
+
+def _run_critical(params: np.ndarray, with_h_s: bool = False) -> Tuple[List[Optional[np.ndarray]], np.ndarray]:
+    """([Tc, Pc, rho_c, h_c, s_c] [B] fp64, the last two None unless asked for; status [B] int32)"""
+    B = params.shape[0]
+    return _run(ops._pcsaft_critical_point, [params], B, [(B,)] * 3 + [(B,) if with_h_s else None] * 2)
+
+
+def critical_points(parameters: Sequence[float]) -> List[float]:
+    """Vapour-liquid critical point ``[Tc (K), Pc (Pa), Dc (mol/m³)]`` of a pure component (reference
+    ``critical_points_feos``): the state with (dp/drho)_T = (d²p/drho²)_T = 0 on the van der Waals loop that vanishes last
+    as T rises.  Raises ``RuntimeError`` where it is not found."""
+    (Tc, Pc, Dc, _, _), status = _run_critical(_rows([parameters]))
+    _require_ok(status, "critical point", [])
+    return [float(Tc[0]), float(Pc[0]), float(Dc[0])]
+
+
+def critical_points_batch(parameters_batch: Sequence[Sequence[float]]) -> np.ndarray:
+    """``[Tc (K), Pc (Pa), Dc (mol/m³)]`` of every parameter row as a [B, 3] array in one launch, rows of 0.0 where a row
+    failed."""
+    if len(parameters_batch) == 0:
+        return np.zeros((0, 3), dtype=np.float64)
+    (Tc, Pc, Dc, _, _), _ = _run_critical(_rows(parameters_batch))
+    return np.stack([Tc, Pc, Dc], axis=1)
+
+
+def _lv(kind: str, values: List[np.ndarray]) -> np.ndarray:
+    """h_lv in kJ/mol (kind "h") or s_lv in J/mol/K (kind "s") from the outputs of the saturation entry"""
+    return (values[4] - values[3]) / 1e3 if kind == "h" else values[6] - values[5]
+
+
+def _single_lv(kind: str, parameters: Sequence[float], state: Sequence[float]) -> float:
+    values, status = _run_saturation(_rows([parameters]), np.zeros(1, dtype=np.int64),
+                                     np.asarray([state[0]], dtype=np.float64))
+    _require_ok(status, "enthalpy of vaporization" if kind == "h" else "entropy of vaporization", state)
+    return float(_lv(kind, values)[0])
+
+
+def pure_h_lv(parameters: Sequence[float], state: Sequence[float]) -> float:
+    """Enthalpy of vaporization h_V - h_L (kJ/mol) at ``state = [T (K), ...]`` (reference ``pure_h_lv_feos``).  The
+    ideal-gas part depends on T only, so the difference of the residual enthalpies is the full one.  Raises
+    ``RuntimeError`` at or above the critical temperature and where the phase equilibrium does not converge."""
+    return _single_lv("h", parameters, state)
+
+
+def pure_s_lv(parameters: Sequence[float], state: Sequence[float]) -> float:
+    """Difference s_V - s_L of the residual molar entropies (J/mol/K) at ``state = [T (K), ...]``: the reference's
+    ``pure_s_lv_feos`` taken literally.  The residual is the one at the same T and V (what feos's
+    ``Contributions.Residual`` means, as far as that can be told without feos), so this is **not** h_lv / T: at saturation
+    s_lv = h_lv / T - R ln(rho_L / rho_V), and the full entropy of vaporization is h_lv / T.  Raises ``RuntimeError`` as
+    ``pure_h_lv`` does."""
+    return _single_lv("s", parameters, state)
+
+
+def _lv_batch(kind: str, parameters_batch: List[List[Any]], states_batch: List[Any]) -> List[np.ndarray]:
+    tables = _nonempty("parameter rows", len(parameters_batch), states_batch)
+    if not tables:
+        return []
+    params = _rows(parameters_batch)
+    states = [np.asarray(s, dtype=np.float64).reshape(np.shape(s)[0], -1) for _, s in tables]
+
+    def run(owner, st):
+        return _lv(kind, _run_saturation(params, owner, np.ascontiguousarray(st[:, 0]))[0])
+
+    return [v.copy() for v in _run_tables([i for i, _ in tables], states, run)]
+
+
+def h_lv_batch(parameters_batch: List[List[Any]], states_batch: List[Any]) -> List[np.ndarray]:
+    """Enthalpies of vaporization (kJ/mol) at the temperature of every state of every non-empty table, one fp64 array per
+    such table, 0.0 where a point failed: ``vp_batch``'s form, one launch."""
+    return _lv_batch("h", parameters_batch, states_batch)
+
+
+def s_lv_batch(parameters_batch: List[List[Any]], states_batch: List[Any]) -> List[np.ndarray]:
+    """``pure_s_lv`` (J/mol/K) at the temperature of every state of every non-empty table, one fp64 array per such table,
+    0.0 where a point failed: ``vp_batch``'s form, one launch."""
+    return _lv_batch("s", parameters_batch, states_batch)
+
+
+PHASE_DIAGRAM_KEYS = ("temperature", "pressure", "density liquid", "density vapor", "mass density liquid",
+                      "mass density vapor", "molar enthalpy liquid", "molar enthalpy vapor", "molar entropy liquid",
+                      "molar entropy vapor", "specific enthalpy liquid", "specific enthalpy vapor",
+                      "specific entropy liquid", "specific entropy vapor")
+
+
+def phase_diagram(parameters: Sequence[float], state: Sequence[float], points: int = 200) -> dict:
+    """Phase diagram of a pure component from ``state[0]`` (K) to the critical point (reference ``phase_diagram_feos``;
+    feos ``PhaseDiagram.pure(eos, T, points).to_dict(Contributions.Residual)``) as a dict of equally long lists under
+    ``PHASE_DIAGRAM_KEYS``: ``temperature`` (K), ``pressure`` (Pa), ``density liquid`` / ``density vapor`` (mol/m³),
+    ``mass density ...`` (kg/m³, from mw in g/mol), ``molar enthalpy ...`` (kJ/mol), ``molar entropy ...`` (kJ/mol/K),
+    ``specific enthalpy ...`` (kJ/kg), ``specific entropy ...`` (kJ/kg/K); enthalpies and entropies are the residual ones
+    of ``saturation``.  Tc comes from the critical-point launch, then one saturation launch runs at
+    linspace(state[0], Tc, points)[:-1]; the last entry is the critical point itself, both phases at rho_c.  Points whose
+    status is not 0 are dropped.  ``ValueError`` if ``state[0] >= Tc``, if the critical point is not found, or if nothing
+    is left.  The key spelling and the placement of the points have not been checked against feos's ``to_dict``."""
+    if int(points) < 2:
+        raise ValueError(f"a phase diagram needs at least 2 points, got {points}")
+    params = _rows([parameters])
+    (Tc, Pc, Dc, hc, sc), cstatus = _run_critical(params, with_h_s=True)
+    if cstatus[0] != STATUS_OK:
+        raise ValueError(f"no critical point found: {_REASON.get(int(cstatus[0]), int(cstatus[0]))}")
+    t0 = float(state[0])
+    if not t0 < Tc[0]:
+        raise ValueError(f"the start temperature {t0} K is not below the critical temperature {float(Tc[0])} K")
+    T = np.linspace(t0, float(Tc[0]), int(points))[:-1]
+    values, status = _run_saturation(params, np.zeros(T.shape[0], dtype=np.int64), T)
+    keep = status == STATUS_OK
+    if not keep.any():
+        raise ValueError("No VLE found at the given conditions.")
+    P, rl, rv, hl, hv, sl, sv = (v[keep] for v in values)
+    T = np.append(T[keep], Tc[0])
+    P = np.append(P, Pc[0])
+    rl, rv = np.append(rl, Dc[0]), np.append(rv, Dc[0])
+    hl, hv = np.append(hl, hc[0]) / 1e3, np.append(hv, hc[0]) / 1e3      # kJ/mol
+    sl, sv = np.append(sl, sc[0]) / 1e3, np.append(sv, sc[0]) / 1e3      # kJ/mol/K
+    mw = float(params[0, 8]) / 1e3                                       # kg/mol
+    columns = (T, P, rl, rv, rl * mw, rv * mw, hl, hv, sl, sv, hl / mw, hv / mw, sl / mw, sv / mw)
+    return {key: col.tolist() for key, col in zip(PHASE_DIAGRAM_KEYS, columns)}
 
 
 # ---- mixtures of 1 to 4 components (csrc/gnx_pcsaft_mix.hip, DESIGN.md §4c) ------------------------------------------

@@ -545,6 +545,24 @@ int32_t gnx_pcsaft_density(gnx_handle* h, const double* params, int64_t B, const
  * PhaseEquilibrium.pure).  rho_l / rho_v may be NULL. */
 int32_t gnx_pcsaft_vapor_pressure(gnx_handle* h, const double* params, int64_t B, const int64_t* owner, const double* T,
                                   int64_t n, double* psat, double* rho_l, double* rho_v, int32_t* status);
+/* The saturation line at T[i] (ref: pcsaft/pcsaft_feos.py pure_h_lv_feos / pure_s_lv_feos / phase_diagram_feos; feos
+ * PhaseEquilibrium.pure and PhaseDiagram.pure with Contributions.Residual): the solve of gnx_pcsaft_vapor_pressure
+ * (same psat, rho_l, rho_v and status, bit for bit), then the residual molar enthalpy h = R T (-T a_T + Z - 1) [J/mol]
+ * and the residual molar entropy at the same T and V, s = -R (a + T a_T) [J/mol/K], of the liquid and of the vapour.
+ * h_v - h_l is the enthalpy of vaporization; s_v - s_l is (h_v - h_l) / T - R ln(rho_l / rho_v), not (h_v - h_l) / T.
+ * Each of the seven fp64 outputs may be NULL.  No kernel id (GNX_K_NONE). */
+int32_t gnx_pcsaft_saturation(gnx_handle* h, const double* params, int64_t B, const int64_t* owner, const double* T,
+                              int64_t n, double* psat, double* rho_l, double* rho_v, double* h_l, double* h_v,
+                              double* s_l, double* s_v, int32_t* status);
+/* Vapour-liquid critical point of every row of params (ref: pcsaft/pcsaft_feos.py critical_points_feos; feos
+ * State.critical_point): Tc[b] (K), Pc[b] (Pa), rho_c[b] (mol/m^3) with (dp/drho)_T = (d2p/drho2)_T = 0 on the van der
+ * Waals loop that vanishes last as T rises.  One lane per row; the bracket in T is found from above (from 20 eps/k
+ * down).  status per row: 0 = ok, 1 = no loop found down to 0.3 eps/k or the polish did not converge, 3 = invalid row;
+ * every value is exactly 0.0 where status != 0.  h_c [J/mol] and s_c [J/mol/K], each NULL or [B], are the residual molar
+ * enthalpy and entropy of gnx_pcsaft_saturation at (Tc, rho_c): the end point of both branches of a phase diagram.
+ * No kernel id (GNX_K_NONE). */
+int32_t gnx_pcsaft_critical_point(gnx_handle* h, const double* params, int64_t B, double* Tc, double* Pc, double* rho_c,
+                                  double* h_c, double* s_c, int32_t* status);
 
 /* ---- mixture PC-SAFT, 1 to 4 components (fp64) ------------------------------------------------------------------ */
 /* [3P] feos 0.8 PC-SAFT mixtures (ref: demo/utils_binary.py:116-160 binary_test -> pcsaft/pcsaft_feos.py:311-346

@@ -40,7 +40,15 @@ tests/test_pcsaft_kij_gpu.py, replicated to ``--systems`` binaries, with the ref
 work in the same run (2 S calls of ``pcsaft.mix_flash_x1``; at most ``--route-calls`` of them are timed and the rest
 scaled, the calls being equal and sequential), and a whole fit of data planted at k_12 = 0.05.
 
-Usage: python tools/pcsaft_bench.py [--mixture | --bubble | --dew | --bubble-t | --dew-t | --flash | --stability | --lle | --kij] [--reps 3] [--sizes 1000,100000,1000000] [--oracle-sample 20] [--out FILE.json]
+With ``--saturation`` it times the saturation kernel of csrc/gnx_pcsaft.hip (``pcsaft.saturation``: the vapour-pressure
+solve, then the residual enthalpy and entropy of both phases) on the vapour-pressure points of the ThermoML fixture,
+repeated, the vapour-pressure kernel on the same points in the same run for the ratio, ``h_lv_batch`` end to end, and the
+oracle of tests/pcsaft_sat_ref.py on a sample.
+
+With ``--critical`` it times the critical-point kernel (``pcsaft.critical_point``, one lane per parameter row) on the
+fixture's rows, repeated to each size, ``critical_points_batch`` end to end, and that oracle on a sample.
+
+Usage: python tools/pcsaft_bench.py [--mixture | --bubble | --dew | --bubble-t | --dew-t | --flash | --stability | --lle | --kij | --saturation | --critical] [--reps 3] [--sizes 1000,100000,1000000] [--oracle-sample 20] [--out FILE.json]
 """
 import argparse
 import json
@@ -368,6 +376,62 @@ def _kij(args, dev):
     return res
 
 
+def _fixture_rows():
+    mols = json.load(open(os.path.join(ROOT, "tests", "golden", "pcsaft_thermoml.json")))["molecules"]
+    rows = np.array([m["params"] for m in mols], dtype=np.float64)
+    vp_pts = np.array([(i, s[0]) for i, m in enumerate(mols) for s in m["vp"]])
+    return rows, vp_pts
+
+
+def _saturation(args, dev):
+    from tests import pcsaft_sat_ref as S
+    rows, vp_pts = _fixture_rows()
+    d_rows = torch.from_numpy(rows).to(dev)
+    t0 = time.perf_counter()
+    for i, T in vp_pts[:args.oracle_sample]:
+        S.saturation(rows[int(i)], T)
+    oracle = (time.perf_counter() - t0) / args.oracle_sample
+    res = []
+    for n in [int(s) for s in args.sizes.split(",")]:
+        pv = vp_pts[np.arange(n) % len(vp_pts)]
+        owner = torch.from_numpy(pv[:, 0].astype(np.int64)).to(dev)
+        T = torch.from_numpy(pv[:, 1].copy()).to(dev)
+        k_sat = _kernel_ms(lambda: pcsaft.saturation(d_rows, T, owner))
+        k_vp = _kernel_ms(lambda: pcsaft.vapor_pressure(d_rows, T, owner))
+        tabs = [np.column_stack([pv[pv[:, 0] == i][:, 1], np.ones(int(np.sum(pv[:, 0] == i)))]) for i in range(len(rows))]
+        pcsaft.h_lv_batch(rows.tolist(), tabs)
+        t0 = time.perf_counter()
+        pcsaft.h_lv_batch(rows.tolist(), tabs)
+        rec = dict(points=n, saturation_kernel_ms=k_sat, vp_kernel_ms=k_vp, ratio=k_sat / k_vp,
+                   h_lv_batch_ms=(time.perf_counter() - t0) * 1e3, oracle_ms_est=oracle * n * 1e3)
+        print(json.dumps(rec))
+        res.append(rec)
+    return res
+
+
+def _critical(args, dev):
+    from tests import pcsaft_sat_ref as S
+    rows, _ = _fixture_rows()
+    t0 = time.perf_counter()
+    for row in rows[:args.oracle_sample]:
+        S.critical_point(row)
+    oracle = (time.perf_counter() - t0) / min(args.oracle_sample, len(rows))
+    res = []
+    for n in [int(s) for s in args.sizes.split(",")]:
+        many = rows[np.arange(n) % len(rows)]
+        d_rows = torch.from_numpy(many).to(dev)
+        k_crit = _kernel_ms(lambda: pcsaft.critical_point(d_rows))
+        status = pcsaft.critical_point(d_rows)[3]
+        pcsaft.critical_points_batch(many)
+        t0 = time.perf_counter()
+        pcsaft.critical_points_batch(many)
+        rec = dict(rows=n, critical_kernel_ms=k_crit, critical_points_batch_ms=(time.perf_counter() - t0) * 1e3,
+                   failed=int((status != 0).sum().item()), oracle_ms_est=oracle * n * 1e3)
+        print(json.dumps(rec))
+        res.append(rec)
+    return res
+
+
 def main():
     global REPS
     ap = argparse.ArgumentParser()
@@ -382,15 +446,17 @@ def main():
     ap.add_argument("--bubble-t", action="store_true")
     ap.add_argument("--dew-t", action="store_true")
     ap.add_argument("--kij", action="store_true")
+    ap.add_argument("--saturation", action="store_true")
+    ap.add_argument("--critical", action="store_true")
     ap.add_argument("--systems", default="1,64,1024", help="--kij: binaries per fit")
     ap.add_argument("--route-calls", type=int, default=16, help="--kij: mix_flash_x1 calls timed, of the 2 S of the old route")
     ap.add_argument("--reps", type=int, default=REPS, help="timed repetitions per kernel, the best of which counts")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     REPS = args.reps
-    if args.mixture or args.bubble or args.dew or args.flash or args.stability or args.lle or args.bubble_t or args.dew_t or args.kij:
+    if args.mixture or args.bubble or args.dew or args.flash or args.stability or args.lle or args.bubble_t or args.dew_t or args.kij or args.saturation or args.critical:
         dev = torch.device("cuda", torch.cuda.current_device())
-        res = (_kij if args.kij else _tvle if args.bubble_t or args.dew_t else _lle if args.lle else _stability if args.stability else _flash if args.flash else _dew if args.dew else _bubble if args.bubble else _mixture)(args, dev)
+        res = (_saturation if args.saturation else _critical if args.critical else _kij if args.kij else _tvle if args.bubble_t or args.dew_t else _lle if args.lle else _stability if args.stability else _flash if args.flash else _dew if args.dew else _bubble if args.bubble else _mixture)(args, dev)
         if args.out:
             with open(args.out, "w") as fh:
                 json.dump(dict(device=torch.cuda.get_device_name(dev), oracle_sample=args.oracle_sample, results=res), fh,
